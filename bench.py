@@ -24,7 +24,16 @@ every rank builds exactly its rows and any rank can rebuild any other rank's.
 The points come from the engine's own scalar-multiplication kernels, kept in
 Jacobian form (z != 1) -- exactly the reference's `G * Fr` output images.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|4]
+A plain run sets up, warms up, times the K steps and prints the result line
+(`value`, `ms_per_step`, and the roofline of the timed steps' own phase
+times).  `--full` adds everything that takes runs of its own: the CPU oracle
+baseline and its bit-exact sample check, the cross-rank recompute, the
+host-buffer (PCIe-inclusive) figure, config 4's workload on one GPU, and for
+`--workload product` the roofline, two products in flight and affine inputs.
+`--dump-outputs DIR` writes what the last timed step computed as
+DIR/<name>.npy (float64, one value per 32-bit word, low word first).
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|4] [--full] [--dump-outputs DIR]
     python bench.py --workload g1mul|g2mul|product|g2validate|g2decompress|gtpow
     python bench.py --gpus 2 --dry-run-cpu   # control flow on CPU (gloo, stub engine)
 """
@@ -99,6 +108,36 @@ def emit(res):
         cb["build"] = ORACLE_BUILD
         cb["sample"] = cb.get("sample", "") + "; built " + ORACLE_BUILD.split(": ", 1)[1]
     print(json.dumps(res), flush=True)
+
+
+DUMP_BYTES = 56 << 20  # --dump-outputs: all files of one run together stay below this
+DUMP_SEED = 20240607   # the row sample of an output larger than that
+
+
+def dump_outputs(dirpath, tensors):
+    """--dump-outputs: write each (rows, words) integer tensor of `tensors` (name ->
+    tensor, device or host) as dirpath/<name>.npy in float64.  A 64-bit word becomes
+    its two 32-bit halves, low half first, so every value is exact in a double and
+    two builds compare bit for bit.  An output too large for DUMP_BYTES is written
+    as a fixed, seeded sample of its rows (sorted; the row numbers go to
+    <name>_rows.npy), the same rows in every run with the same arguments."""
+    import torch
+    os.makedirs(dirpath, exist_ok=True)
+    budget = DUMP_BYTES
+    for name, t in tensors.items():
+        assert t.dim() == 2 and not t.is_floating_point(), name
+        row_bytes = t.shape[1] * (2 if t.element_size() == 8 else 1) * 8 + 8
+        keep = max(1, budget // row_bytes)
+        if t.shape[0] > keep:
+            rows = np.sort(np.random.default_rng(DUMP_SEED).choice(t.shape[0], keep, replace=False))
+            t = t[torch.from_numpy(rows).to(t.device)]
+            np.save(os.path.join(dirpath, name + "_rows.npy"), rows.astype(np.float64))
+            budget -= rows.size * 8
+        a = np.ascontiguousarray(t.cpu().numpy())
+        a = (a.view(np.uint32) if a.itemsize == 8 else a).astype(np.float64)
+        np.save(os.path.join(dirpath, name + ".npy"), a)
+        budget -= a.nbytes
+        log("dumped %s: %s float64 to %s" % (name, "x".join(map(str, a.shape)), dirpath))
 
 
 def host_cpus():
@@ -356,7 +395,10 @@ def other_workload(args, local_rank):
     torch.cuda.synchronize(dev)
     el = time.perf_counter() - t0
     res.update({"metric": unit, "value": n * args.steps / el, "unit": unit, "ms_per_step": el / args.steps * 1e3})
-    if args.no_cpu_baseline:  # profiler passes: the kernels only
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"product": gout.view(1, 48), "status": gst.view(1, 1)}
+                     if args.workload == "product" else {"out": out})
+    if args.no_cpu_baseline:  # a plain run, profiler passes: the kernels only
         emit(res)
         return
     from oracle import oracle as O  # the checker (cpu_baseline leg)
@@ -528,6 +570,11 @@ def codec_workload(args, local_rank):
                            "basis": "8,064 Fq-mul per Gt::pow (66 x 54 + 250 x 18: the signed 5-bit window chain of "
                                     "cyclotomic-subgroup inputs; the unsigned 4-bit chain before it ran 78 x 54 + "
                                     "252 x 18 = 8,748), x128 MAD32"}
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"out": out} if st is None else {"out": out, "status": st.view(-1, 1)})
+    if args.no_cpu_baseline:  # a plain run: the kernel only
+        emit(res)
+        return
     from oracle import oracle as O  # the checker (cpu_baseline leg)
     m = min(args.cpu_sample or 2048, n)
     g_out = out[:m].cpu().numpy().view(np.uint64)
@@ -699,6 +746,8 @@ def run_pairing(args, eng, rank, world, dist):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     value = total * args.steps / elapsed
+    if args.dump_outputs and rank == 0:  # what a caller holds after the last step: all rows after the all-gather
+        dump_outputs(args.dump_outputs, {"gt": gathered if world > 1 else out})
 
     res = {
         "metric": "BN254 pairings/sec (batched) at 1/2/4/8 MI355X; bit-exact vs CPU ref",
@@ -726,7 +775,7 @@ def run_pairing(args, eng, rank, world, dist):
 
     # cross-rank equality: rebuild a sample of the next rank's rows here and compare
     # this GPU's results with what the all-gather delivered
-    if world > 1:
+    if world > 1 and args.full:
         src = (rank + 1) % world
         m = min(128, local_n)
         mism = 0
@@ -861,6 +910,8 @@ def run_capi_multi(args):
         eng.sync()
     elapsed = time.perf_counter() - t0
     value = total * args.steps / elapsed
+    if args.dump_outputs:  # device 0's gathered rows (the check below compares the other devices' with them)
+        dump_outputs(args.dump_outputs, {"gt": shards[0][2]})
     res = {
         "metric": "BN254 pairings/sec (batched) at 1/2/4/8 MI355X; bit-exact vs CPU ref",
         "value": value, "unit": "pairings/s", "n_gpus": N, "steps": args.steps, "warmup": args.warmup,
@@ -889,16 +940,18 @@ def run_capi_multi(args):
         mctx.dev_status()  # the sticky device outcome (BN_ERR_INTERNAL / BN_ERR_FE_ZERO) of every device
     # every device's gathered buffer equals device 0's
     ref = shards[0][2]
-    mism = 0
-    for _, _, out in shards[1:]:
-        o = out if dry else out.to(engs[0].dev)
-        mism += int((o != ref).any(dim=1).sum().item())
     res["collective"] = {"backend": "stub (dry run)" if dry else "rccl: ncclCommInitAll + grouped ncclAllGather "
                          "(bn_pairing_many_allgather_dev, librccl dlopen'ed)",
                          "world_from_allreduce": N if dry else mctx.num_devices,
-                         "devices_equal_to_device0": mism == 0, "mismatched_rows": mism,
-                         "what": "the communicator's device count; every device's gathered buffer compared with "
-                                 "device 0's row by row"}
+                         "what": "the communicator's device count"}
+    if args.full:
+        mism = 0
+        for _, _, out in shards[1:]:
+            o = out if dry else out.to(engs[0].dev)
+            mism += int((o != ref).any(dim=1).sum().item())
+        res["collective"].update({"devices_equal_to_device0": mism == 0, "mismatched_rows": mism,
+                                  "what": "the communicator's device count; every device's gathered buffer "
+                                          "compared with device 0's row by row"})
     if not args.no_cpu_baseline:
         res["sample_check"], res["cpu_baseline"] = gathered_sample_check(engs[0], ref, total, host_cpus())
     return res
@@ -963,6 +1016,14 @@ def main():
                     help="pairings per launch set (2^16 = one wave per SIMD); all-gathers go per chunk")
     ap.add_argument("--cpu-sample", type=int, default=None,
                     help="oracle sample size (default: 16384 pairings, 2048 for the 8(f) workloads; ~10-30 s of CPU-thread work)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU oracle baseline and sample "
+                         "checks, the cross-rank recompute, the host-buffer figure, config 4's workload on one GPU, "
+                         "the product workload's roofline, two-in-flight and affine-input figures (the --no-* "
+                         "options below drop single legs of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's outputs as DIR/<name>.npy (float64, one "
+                         "value per 32-bit word; a seeded row sample of an output above 56 MiB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-e2e", action="store_true", help="skip the host-buffer (PCIe-inclusive) figure")
     ap.add_argument("--no-config4-ref", action="store_true",
@@ -981,6 +1042,10 @@ def main():
     args = ap.parse_args()
     if args.config is None:
         args.config = 2 if args.gpus == 1 else 4
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:  # a plain run: the timed steps and the result line only
+        args.no_cpu_baseline = args.no_e2e = args.no_config4_ref = True
 
     if args.form == "capi":
         if args.workload != "pairing" or os.environ.get("WORLD_SIZE") not in (None, "1"):

@@ -24,7 +24,7 @@ def run(args, env=None):
 @pytest.mark.parametrize("world", [2, 4, 8])
 def test_bench_spawns_ranks_config4(world):
     r = run(["--gpus", str(world), "--dry-run-cpu", "--steps", "1", "--warmup", "1", "--total", "16384",
-             "--chunk", "2048"])
+             "--chunk", "2048", "--full"])
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == world and line["dry_run"] is True
@@ -40,6 +40,56 @@ def test_bench_spawns_ranks_config4(world):
     assert cb["parity_sample_bit_exact"] is True and cb["value"] > 0 and cb["kind"] == "dry-run stub"
     assert {"cores", "single_core", "cpu_model", "sample", "unit"} <= set(cb)
     assert line["collective"]["world_from_allreduce"] == world
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) times --steps steps and prints the line without the legs
+    that take runs of their own; --dump-outputs writes the last step's rows as float64
+    32-bit words, the same from run to run."""
+    import numpy as np
+    lines, dumps = [], []
+    for k in range(2):
+        d = tmp_path / ("dump%d" % k)
+        r = run(["--gpus", "1", "--dry-run-cpu", "--steps", "3", "--warmup", "0", "--pairs", "4096",
+                 "--dump-outputs", str(d)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(json.loads(r.stdout.strip().splitlines()[-1]))
+        assert sorted(p.name for p in d.iterdir()) == ["gt.npy"]
+        dumps.append(np.load(d / "gt.npy"))
+    line = lines[0]
+    assert line["steps"] == 3 and line["warmup"] == 0 and line["ms_per_step"] > 0
+    assert line["value"] == pytest.approx(4096 * 1e3 / line["ms_per_step"])
+    assert {"metric", "unit", "higher_is_better", "dtype"} <= set(line)
+    assert not {"cpu_baseline", "sample_check", "cross_rank_check", "host_buffer_e2e", "config4_on_1_gpu"} & set(line)
+    a = dumps[0]
+    assert a.dtype == np.float64 and a.shape == (4096, 96) and np.array_equal(a, dumps[1])
+    # the stub's rows: P = the first scalar's words three times over
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "paritytech-bn_amd"))
+    from substrate_bn import synth
+    s, _ = synth.dataset_scalars(0, 4096)
+    assert np.array_equal(a[:, :8], np.ascontiguousarray(s).view(np.uint32).astype(np.float64))
+
+
+def test_dump_outputs_samples_large_outputs(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BYTES", 64 * 1024)
+    t = torch.arange(1000 * 48, dtype=torch.int64).reshape(1000, 48) * ((1 << 40) + 3)
+    st = torch.arange(1000, dtype=torch.int32).reshape(-1, 1)
+    for k in range(2):
+        bench.dump_outputs(str(tmp_path / str(k)), {"out": t, "status": st})
+    d = tmp_path / "0"
+    rows = np.load(d / "out_rows.npy")
+    out = np.load(d / "out.npy")
+    assert rows.dtype == out.dtype == np.float64 and len(rows) == len(out) < 1000 and np.all(np.diff(rows) > 0)
+    want = t.numpy()[rows.astype(np.int64)].view(np.uint32).astype(np.float64)
+    assert np.array_equal(out, want)
+    assert sum(p.stat().st_size for p in d.iterdir()) <= 64 * 1024 + 4 * 256  # the budget + the .npy headers
+    for p in d.iterdir():
+        assert np.array_equal(np.load(p), np.load(tmp_path / "1" / p.name))
 
 
 def test_sample_blocks_cover_every_shard():
@@ -66,7 +116,7 @@ def test_bench_capi_form_keys(ndev):
     spawned, every device's gathered buffer is compared with device 0's, and rank
     0's checker sample and cpu_baseline keys are the torch form's."""
     r = run(["--gpus", str(ndev), "--form", "capi", "--dry-run-cpu", "--steps", "2", "--warmup", "1",
-             "--total", "12288"])
+             "--total", "12288", "--full"])
     assert r.returncode == 0, r.stderr[-2000:]
     assert "launching" not in r.stderr  # no torch.distributed.run child
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -105,7 +155,7 @@ def test_bench_under_the_drivers_launcher_world8():
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
                         "--gpus", "8", "--steps", "1", "--warmup", "1", "--dry-run-cpu", "--total", "16384",
-                        "--chunk", "2048"], capture_output=True, text=True, timeout=300, env=e, cwd=ROOT)
+                        "--chunk", "2048", "--full"], capture_output=True, text=True, timeout=300, env=e, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]  # rank 0 alone prints the line

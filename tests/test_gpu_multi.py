@@ -243,7 +243,7 @@ def test_bench_driver_launch_two_ranks_on_one_gpu():
     env = dict(os.environ, BN254MI_BENCH_SHARED_GPU="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--total", "16384", "--chunk", "4096", "--cpu-sample", "256", "--no-e2e"]
+           "--total", "16384", "--chunk", "4096", "--cpu-sample", "256", "--no-e2e", "--full"]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])

@@ -13,10 +13,10 @@ echo "== tests"
 timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 200 --timeout-method thread > $OUT/gpu_tests.log 2>&1 || { tail -30 $OUT/gpu_tests.log; exit 1; }
 tail -1 $OUT/gpu_tests.log
 echo "== bench"
-timeout -k 10 300 python -u bench.py > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 300 python -u bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 cat $OUT/bench.json
 echo "== config 4 in one process (bn_ctx_create_multi + bn_pairing_many_allgather_dev; RCCL world of the visible GPUs)"
-timeout -k 10 300 python -u bench.py --form capi --gpus ${CAPI_GPUS:-1} --steps 3 --warmup 1 > $OUT/bench_capi.json 2> $OUT/bench_capi.err
+timeout -k 10 300 python -u bench.py --form capi --gpus ${CAPI_GPUS:-1} --steps 3 --warmup 1 --full > $OUT/bench_capi.json 2> $OUT/bench_capi.err
 head -c 400 $OUT/bench_capi.json; echo
 echo "== kernel stats"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run -- python3 bench.py $Q > $OUT/bench_prof.json 2> $OUT/prof.err
@@ -44,7 +44,7 @@ if [ -f paritytech-bn_amd/libbn254mi_dbg.so ]; then
 fi
 echo "== workloads"
 for w in g1mul g2mul product gtpow g2validate g2decompress; do
-  timeout -k 10 300 python -u bench.py --workload $w --steps 10 --warmup 2 > $OUT/bench_$w.json 2> $OUT/bench_$w.err
+  timeout -k 10 300 python -u bench.py --workload $w --steps 10 --warmup 2 --full > $OUT/bench_$w.json 2> $OUT/bench_$w.err
   head -c 300 $OUT/bench_$w.json; echo
 done
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof_product -o run -- python3 bench.py --workload product --steps 10 > /dev/null 2> $OUT/prof_product.err
