@@ -6,8 +6,11 @@ with K = 0 on the exact lanes and k + 3 * 2^29 on the Montgomery lanes, the exac
 fix reaching the Montgomery lanes as 6p - r -- then the fold estimate in float32.  Each
 round's invariants are asserted (the exact lanes stay in [0, p] and fold with q = 0, the
 Montgomery lanes in [0, 6p]); the result is checked against the modular inverse in the
-engine's Montgomery form (R = 2^261).  The GPU path is checked bit for bit through every
-pairing test that runs k_prepare_wide, the latency kernel or k_seg_tail."""
+engine's Montgomery form (R = 2^261).  The kernel itself is checked on the GPU, bit for
+bit, by the inversion sweep of tests/test_gpu_edges.py
+(test_inversion_sweep_through_pairing: every operand of GCD(p) -- small values, values
+next to p, every power of two -- through k_pairing_latency and k_prepare_wide), and on
+random operands by every pairing test that runs those kernels or k_seg_tail."""
 import random
 
 import numpy as np
