@@ -70,13 +70,15 @@ int bn_dev_status(bn_ctx* ctx, void* stream);
 
 /* ---- several devices of the node in one process ----
  * A multi-device context shards the host-buffer calls bn_pairing_many,
- * bn_final_exponentiation_many, bn_miller_loop_many, bn_g1_mul_many and
- * bn_g2_mul_many contiguously (device k takes bn_shard_range(n, D, k)), runs the
+ * bn_final_exponentiation_many, bn_miller_loop_many, bn_g1_mul_many, bn_g2_mul_many
+ * and bn_g1_msm contiguously (device k takes bn_shard_range(n, D, k)), runs the
  * shards concurrently and writes each into the caller's output: the same bytes
  * as one device.  bn_pairing_batch / bn_miller_loop_batch reduce each shard to
  * one Miller value, multiply the partials on the first device in device order
  * (pairing_batch then runs one final exponentiation): the reference's shared
- * loop value exactly (mod.rs:609-640).  Other calls need a single-device
+ * loop value exactly (mod.rs:609-640).  bn_g1_msm reduces each shard to its
+ * Jacobian partial sum, adds the partials on the first device in device order and
+ * normalizes there.  Other calls need a single-device
  * context: bn_ctx_device(ctx, k) returns device k's (owned by ctx). */
 int bn_ctx_create_multi(const int* devices, int ndev, bn_ctx** out);
 int bn_ctx_num_devices(const bn_ctx* ctx);
@@ -140,6 +142,30 @@ int bn_g1_mul_many(bn_ctx* ctx, const bn_g1* p, const bn_fr* k, size_t n, bn_g1*
 int bn_g1_mul_many_dev(bn_ctx* ctx, const bn_g1* d_p, const bn_fr* d_k, size_t n, bn_g1* d_out, void* stream);
 int bn_g2_mul_many(bn_ctx* ctx, const bn_g2* p, const bn_fr* k, size_t n, bn_g2* out);
 int bn_g2_mul_many_dev(bn_ctx* ctx, const bn_g2* d_p, const bn_fr* d_k, size_t n, bn_g2* d_out, void* stream);
+
+/* ---- G1 multi-scalar multiplication (bucket method) ---- */
+
+/* *out = (sum over i < n of p[i] * k[i]).normalize()  -- groups/mod.rs:272-334 for the terms and the
+ * sum, lib.rs:391-398 for normalize.  The reference has no multi-scalar multiplication, so there is
+ * no Jacobian image to reproduce; the normalized image (x, y, one) is the unique one and is what is
+ * returned.  A zero sum, and n == 0, give G1::zero() = (0, one, 0) (mod.rs:230-236).  p[i] may be any
+ * Jacobian image (z != one, z == 0); k[i] are Fr images as for bn_g1_mul_many.
+ * n above 2^26 terms is refused with BN_ERR_INVALID_ARGUMENT (no chunking: entry indices and
+ * positions are 32-bit), and so is an n whose n * windows exceeds 2^31 - 1 at a forced narrow window.
+ * The _dev form enqueues on `stream` without synchronizing; it may allocate (and then waits for
+ * earlier work) on first use at a larger n, as bn_pairing_many_dev does. */
+int bn_g1_msm(bn_ctx* ctx, const bn_g1* p, const bn_fr* k, size_t n, bn_g1* out);
+int bn_g1_msm_dev(bn_ctx* ctx, const bn_g1* d_p, const bn_fr* d_k, size_t n, bn_g1* d_out, void* stream);
+/* window width in bits for the bucket path, 2 .. 16; 0 (default) = chosen from n by the measured table.
+ * Any other value is refused with BN_ERR_INVALID_ARGUMENT.  Results are identical at every width. */
+int bn_set_msm_window(bn_ctx* ctx, int c);
+/* batches below n terms take the small path (bn_g1_mul_many's kernels + an addition tree);
+ * 0 sends every n >= 1 down the bucket path.  Default: the measured crossover or $BN254MI_MSM_MIN.
+ * Results are identical on either path. */
+int bn_set_msm_min(bn_ctx* ctx, size_t n);
+/* pre-size the MSM workspace for up to n terms (else allocated on first use, as bn_reserve);
+ * it is separate from the pairing workspace and not counted by bn_workspace_bytes */
+int bn_msm_reserve(bn_ctx* ctx, size_t n);
 
 /* ---- group law (lib.rs:388-423, 539-574; src/groups/mod.rs:169-216, 294-358) ----
  * Batched forms of the G1 / G2 operators, each lane running the reference's own

@@ -72,6 +72,11 @@ constexpr size_t kLatencyMaxDefault = 4096;  // one-wave crossover: 2048 pairs 1
 // batches up to this size run k_prepare_wide (8 lanes per pair: 2^14 pairs fill
 // the GPU at two waves per SIMD).  BN254MI_PREPARE_WIDE_MAX overrides (0: never).
 constexpr size_t kPrepareWideMaxDefault = 16384;
+// bn_g1_msm batches below this many terms take the small path (bn_g1_mul_many's
+// kernels and an addition tree), larger ones the bucket path (kernels_msm.hip);
+// $BN254MI_MSM_MIN or bn_set_msm_min override.  0: the bucket path was the faster one
+// at every size of the sweep, down to one term.
+constexpr size_t kMsmMinDefault = 0;
 
 size_t ws_bytes(size_t n) {
     return n * ((size_t)kCoeffFq * 9 * 4 + kPathLanes * (2 * 9 * 4 + 1) + (size_t)kFeSlots * kSlotWords * 4) + 64;
@@ -909,6 +914,8 @@ int bn_ctx_create(int device, bn_ctx** out) {
         c->fe_ds_max = v < (size_t)kFeDsMax ? v : (size_t)kFeDsMax;
     }
     if (const char* e = getenv("BN254MI_PREPARE_WIDE_MAX")) c->prepare_wide_max = (size_t)strtoull(e, nullptr, 10);
+    c->msm_min = kMsmMinDefault;
+    if (const char* e = getenv("BN254MI_MSM_MIN")) c->msm_min = (size_t)strtoull(e, nullptr, 10);
     Prog P;
     c->fe_out = (int)build_final_exp(P);
     P.finalize({(uint32_t)c->fe_out});
@@ -965,7 +972,8 @@ static void ctx_teardown(bn_ctx* c) {
     for (hipStream_t s : {c->h2d, c->d2h})
         if (s) (void)hipStreamDestroy(s);
     for (void* p : {(void*)c->coeffs, (void*)c->paff, (void*)c->slots, (void*)c->flags, (void*)c->d_err,
-                    (void*)c->d_prog, c->stage, (void*)c->tail_ws, (void*)c->fe_ds_ws})
+                    (void*)c->d_prog, c->stage, (void*)c->tail_ws, (void*)c->fe_ds_ws, (void*)c->msm_keys,
+                    (void*)c->msm_sorted, (void*)c->msm_buckets, (void*)c->msm_parts, (void*)c->msm_tmp})
         if (p) (void)hipFree(p);
     for (auto& ev : c->ev_marks)
         for (auto e : ev) c->ev_pool.push_back(e);
@@ -1503,6 +1511,193 @@ int bn_g1_mul_many(bn_ctx* c, const bn_g1* p, const bn_fr* k, size_t n, bn_g1* o
 int bn_g2_mul_many(bn_ctx* c, const bn_g2* p, const bn_fr* k, size_t n, bn_g2* out) {
     if (c && !c->subs.empty()) return bn_multi_g2_mul_many(c, p, k, n, out);
     return host_mul(c, p, k, n, out, g2_mul_launch);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- G1 multi-scalar multiplication
+// (kernels_msm.hip).  The bucket path and the small path return the
+// same image: the group law is exact and the result is normalized.
+constexpr size_t kMsmMaxTerms = size_t(1) << 26;  // the entry index keeps bit 31 for the sign; keys and positions are 32-bit
+// The window width used when bn_set_msm_window is 0: the fastest width of the measured
+// sweep (profiles/msm_sweep.jsonl, tools/msm_bench.py) at the nearest
+// measured size, the steps at the geometric means between sizes whose best width
+// differs.  Below 2^13 terms every width from 8 to 12 is within the run-to-run spread.
+static int msm_auto_window(size_t n) {
+    if (n < 6144) return 10;
+    if (n < 92682) return 12;    // 2^16.5
+    if (n < 370728) return 14;   // 2^18.5
+    if (n < 741455) return 15;   // 2^19.5
+    return 16;
+}
+struct MsmPlan {
+    bool small;
+    int c;
+    uint32_t nwin, nkeys, nseg;
+    size_t nent;  // n * W(c): the most entries
+};
+static MsmPlan msm_plan(const bn_ctx* c, size_t n) {
+    MsmPlan m{};
+    m.small = n < c->msm_min;
+    m.c = c->msm_window ? c->msm_window : msm_auto_window(n);
+    m.nwin = (uint32_t)msm_windows(m.c);
+    m.nkeys = msm_num_keys(m.c);
+    m.nseg = (msm_buckets(m.c) + kMsmSegment - 1) / kMsmSegment;
+    m.nent = n * m.nwin;
+    return m;
+}
+template <class T>
+static int msm_grow(bn_ctx* c, T** buf, size_t* cap, size_t need) {
+    if (need <= *cap) return BN_OK;
+    if (*buf) {
+        RET_IF(ws_drain(c));
+        HIPCHK(c, hipFree(*buf));
+    }
+    *buf = nullptr;
+    *cap = 0;
+    HIPCHK(c, hipMalloc((void**)buf, need * sizeof(T)));
+    *cap = need;
+    return BN_OK;
+}
+static int msm_reserve(bn_ctx* c, size_t n, const MsmPlan& m) {
+    if (m.small) return msm_grow(c, &c->msm_tmp, &c->msm_tmp_cap, n);
+    RET_IF(msm_grow(c, &c->msm_keys, &c->msm_keys_cap, 3 * (size_t)m.nkeys + 1));
+    RET_IF(msm_grow(c, &c->msm_sorted, &c->msm_sorted_cap, m.nent));
+    RET_IF(msm_grow(c, &c->msm_buckets, &c->msm_buckets_cap, (size_t)m.nkeys));
+    return msm_grow(c, &c->msm_parts, &c->msm_parts_cap, (size_t)m.nseg * m.nwin);
+}
+// buf[0] = sum of buf[0 .. m) by a halving addition tree in place (odd tail carried),
+// then *d_out = its returned image (finish) or the Jacobian sum as it stands
+static int msm_tree_out(bn_ctx* c, bn_g1* buf, size_t m, size_t width, int finish, bn_g1* d_out, hipStream_t s) {
+    while (m > 1) {
+        const size_t h = (m + 1) / 2;
+        k_g1_op<<<grid_for((m - h) * width), kBlock, 0, s>>>(kGroupAdd, buf, buf + h * width, (m - h) * width, buf, nullptr);
+        m = h;
+    }
+    if (width != 1) return BN_OK;
+    if (finish)
+        k_msm_finish<<<1, 64, 0, s>>>(m ? buf : nullptr, d_out);
+    else if (m)
+        HIPCHK(c, hipMemcpyAsync(d_out, buf, sizeof(bn_g1), hipMemcpyDeviceToDevice, s));
+    else
+        k_msm_finish<<<1, 64, 0, s>>>(nullptr, d_out);  // zero is its own Jacobian image
+    return BN_OK;
+}
+// the device sequence on stream s; the caller holds the lock and the workspace order
+static int msm_dev_impl(bn_ctx* c, const bn_g1* d_p, const bn_fr* d_k, size_t n, bn_g1* d_out, hipStream_t s,
+                        int finish) {
+    if (n == 0) {
+        k_msm_finish<<<1, 64, 0, s>>>(nullptr, d_out);
+        HIPCHK(c, hipGetLastError());
+        return BN_OK;
+    }
+    const MsmPlan m = msm_plan(c, n);
+    if (!m.small && m.nent > (size_t)0x7fffffff)
+        return fail(c, BN_ERR_INVALID_ARGUMENT, "n * windows exceeds the 32-bit entry positions at this window width");
+    RET_IF(msm_reserve(c, n, m));
+    if (m.small) {
+        g1_mul_launch(d_p, d_k, n, c->msm_tmp, s);
+        RET_IF(msm_tree_out(c, c->msm_tmp, n, 1, finish, d_out, s));
+        HIPCHK(c, hipGetLastError());
+        return BN_OK;
+    }
+    uint32_t* counts = c->msm_keys;
+    uint32_t* cursors = counts + m.nkeys;
+    uint32_t* offsets = cursors + m.nkeys;
+    const uint32_t nent = (uint32_t)m.nent;
+    HIPCHK(c, hipMemsetAsync(counts, 0, (size_t)m.nkeys * 4, s));
+    k_msm_count<<<grid_for(n), kBlock, 0, s>>>(d_p, d_k, n, m.c, m.nkeys, counts);
+    k_msm_scan<<<1, kMsmScanBlock, 0, s>>>(counts, m.nkeys, offsets, cursors);
+    k_msm_scatter<<<grid_for(n), kBlock, 0, s>>>(d_p, d_k, n, m.c, m.nkeys, cursors, offsets, c->msm_sorted, nent);
+    k_msm_accumulate<<<grid_for(m.nkeys), kBlock, 0, s>>>(d_p, n, c->msm_sorted, offsets, m.nkeys, nent, c->msm_buckets);
+    k_msm_reduce<<<grid_for((size_t)m.nseg * m.nwin), kBlock, 0, s>>>(c->msm_buckets, m.c, m.nkeys, m.nseg, c->msm_parts);
+    RET_IF(msm_tree_out(c, c->msm_parts, m.nseg, m.nwin, 0, nullptr, s));
+    k_msm_horner<<<1, 64, 0, s>>>(c->msm_parts, m.c, finish, d_out);
+    HIPCHK(c, hipGetLastError());
+    return BN_OK;
+}
+static int msm_check_args(bn_ctx* c, const void* p, const void* k, size_t n, const void* out) {
+    if (n > kMsmMaxTerms) return fail(c, BN_ERR_INVALID_ARGUMENT, "more than 2^26 terms");
+    if (!out || (n && (!p || !k))) return fail(c, BN_ERR_INVALID_ARGUMENT, "null buffer");
+    return BN_OK;
+}
+static int msm_host(bn_ctx* c, const bn_g1* p, const bn_fr* k, size_t n, bn_g1* out, int finish) {
+    CTX_GUARD_HOST(c);
+    RET_IF(msm_check_args(c, p, k, n, out));
+    RET_IF(stage(c, (n + 1) * sizeof(bn_g1) + n * sizeof(bn_fr)));
+    bn_g1* dout = (bn_g1*)c->stage;
+    bn_g1* dp = dout + 1;
+    bn_fr* dk = (bn_fr*)(dp + n);
+    if (n) {
+        HIPCHK(c, hipMemcpyAsync(dp, p, n * sizeof(bn_g1), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(dk, k, n * sizeof(bn_fr), hipMemcpyHostToDevice, c->stream));
+    }
+    RET_IF(msm_dev_impl(c, dp, dk, n, dout, c->stream, finish));
+    HIPCHK(c, hipMemcpyAsync(out, dout, sizeof(bn_g1), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return BN_OK;
+}
+extern "C" {
+
+int bn_internal_g1_msm_partial(bn_ctx* c, const bn_g1* p, const bn_fr* k, size_t n, bn_g1* out) {
+    return msm_host(c, p, k, n, out, 0);
+}
+int bn_internal_g1_sum(bn_ctx* c, const bn_g1* a, size_t m, bn_g1* out) {
+    CTX_GUARD_HOST(c);
+    if (!out || (m && !a)) return fail(c, BN_ERR_INVALID_ARGUMENT, "null buffer");
+    RET_IF(msm_grow(c, &c->msm_tmp, &c->msm_tmp_cap, m + 1));
+    bn_g1* dout = c->msm_tmp + m;
+    if (m) HIPCHK(c, hipMemcpyAsync(c->msm_tmp, a, m * sizeof(bn_g1), hipMemcpyHostToDevice, c->stream));
+    RET_IF(msm_tree_out(c, c->msm_tmp, m, 1, 1, dout, c->stream));
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(out, dout, sizeof(bn_g1), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return BN_OK;
+}
+int bn_g1_msm(bn_ctx* c, const bn_g1* p, const bn_fr* k, size_t n, bn_g1* out) {
+    if (c && !c->subs.empty()) return bn_multi_g1_msm(c, p, k, n, out);
+    return msm_host(c, p, k, n, out, 1);
+}
+int bn_g1_msm_dev(bn_ctx* c, const bn_g1* d_p, const bn_fr* d_k, size_t n, bn_g1* d_out, void* stream) {
+    CTX_GUARD(c);
+    RET_IF(msm_check_args(c, d_p, d_k, n, d_out));
+    hipStream_t s = pick(c, stream);
+    RET_IF(ws_acquire(c, s));
+    WsUse use{c, s};
+    return msm_dev_impl(c, d_p, d_k, n, d_out, s, 1);
+}
+int bn_set_msm_window(bn_ctx* c, int bits) {
+    if (c && bits != 0 && !msm_window_ok(bits))
+        return fail(c, BN_ERR_INVALID_ARGUMENT, "window width outside 2 .. 16 (0: automatic)");
+    if (c && !c->subs.empty()) {
+        for (bn_ctx* d : c->subs) RET_IF(bn_set_msm_window(d, bits));
+        return BN_OK;
+    }
+    CTX_GUARD(c);
+    c->msm_window = bits;
+    return BN_OK;
+}
+int bn_set_msm_min(bn_ctx* c, size_t n) {
+    if (c && !c->subs.empty()) {
+        for (bn_ctx* d : c->subs) RET_IF(bn_set_msm_min(d, n));
+        return BN_OK;
+    }
+    CTX_GUARD(c);
+    c->msm_min = n;
+    return BN_OK;
+}
+int bn_msm_reserve(bn_ctx* c, size_t n) {
+    if (c && !c->subs.empty()) {
+        for (bn_ctx* d : c->subs) RET_IF(bn_msm_reserve(d, n / c->subs.size() + 1));
+        return BN_OK;
+    }
+    CTX_GUARD(c);
+    if (n > kMsmMaxTerms) return fail(c, BN_ERR_INVALID_ARGUMENT, "more than 2^26 terms");
+    if (n == 0) return BN_OK;
+    const MsmPlan m = msm_plan(c, n);
+    if (!m.small && m.nent > (size_t)0x7fffffff)
+        return fail(c, BN_ERR_INVALID_ARGUMENT, "n * windows exceeds the 32-bit entry positions at this window width");
+    return msm_reserve(c, n, m);
 }
 
 int bn_fq12_op_many(bn_ctx* c, int op, const bn_gt* a, const bn_gt* b, size_t n, bn_gt* out) {

@@ -185,6 +185,20 @@ BN_INLINE Jac<F> jac_neg(const Jac<F>& a) {
     return {a.x, F_select(z, a.y, narrow<kPt>(F_neg(a.y))), a.z};
 }
 
+// Group::normalize (lib.rs:391-398, 542-549): to_affine (mod.rs:199-216), then
+// to_jacobian (mod.rs:220-226: z = one); a zero point stays as it is.  The
+// inverse is unique, so (x z^-2, y z^-3, 1) is the reference's image also when z
+// is already one (its shortcut returns the same residues).
+template <template <int> class F>
+BN_INLINE Jac<F> jac_normalize(const Jac<F>& a) {
+    const bool zero = jac_is_zero(a);
+    const auto zinv = F_inv(a.z);  // F_inv(0) = 0; that result is discarded
+    const auto zinv2 = F_sqr(zinv);
+    const Jac<F> r = {narrow<kPt>(F_mul(a.x, zinv2)), narrow<kPt>(F_mul(a.y, F_mul(zinv2, zinv))),
+                      F_widen<kPt>(F_one<F>())};
+    return {F_select(zero, a.x, r.x), F_select(zero, a.y, r.y), F_select(zero, a.z, r.z)};
+}
+
 // The per-lane bit state of one double-and-add chain (mod.rs:272-292): `w` holds
 // the scalar shifted so that the next bit to consume is bit 31 of w[7]; `left` =
 // bits still to consume after the top set bit; `need_add`: the chain's next step

@@ -102,19 +102,6 @@ __global__ void __launch_bounds__(kPairBlock) k_g1_mul2(const bn_g1* __restrict_
     }
 }
 // ---------------------------------------------------------------- group law
-// Group::normalize (lib.rs:391-398, 542-549): to_affine (mod.rs:199-216), then
-// to_jacobian (mod.rs:220-226: z = one); a zero point stays as it is.  The
-// inverse is unique, so (x z^-2, y z^-3, 1) is the reference's image also when z
-// is already one (its shortcut returns the same residues).
-template <template <int> class F>
-__device__ __forceinline__ Jac<F> jac_normalize(const Jac<F>& a) {
-    const bool zero = jac_is_zero(a);
-    const auto zinv = F_inv(a.z);  // F_inv(0) = 0; that result is discarded
-    const auto zinv2 = F_sqr(zinv);
-    const Jac<F> r = {narrow<kPt>(F_mul(a.x, zinv2)), narrow<kPt>(F_mul(a.y, F_mul(zinv2, zinv))),
-                      F_widen<kPt>(F_one<F>())};
-    return {F_select(zero, a.x, r.x), F_select(zero, a.y, r.y), F_select(zero, a.z, r.z)};
-}
 // PartialEq for G<P> (mod.rs:169-195): both zero, or neither and
 // x1 z2^2 == x2 z1^2 and y1 z2^3 == y2 z1^3 (mod p)
 template <template <int> class F>

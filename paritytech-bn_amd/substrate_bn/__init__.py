@@ -19,7 +19,8 @@ and the wire formats and validation around it:
     G1.from_compressed, G2.from_compressed             lib.rs:359-375, 506-526
     Gt.pow(Fr)                                         lib.rs:592-594
 
-plus the batched forms the reference lacks (pairing_many, g1_mul_many) that
+plus the batched forms the reference lacks (pairing_many, g1_mul_many, and the
+multi-scalar multiplication g1_msm = sum of points[i] * scalars[i]) that
 the engine exists for.  Values keep the reference's memory images (canonical
 Montgomery, little-endian u64 limbs), so a Gt compares equal exactly when the
 reference's derived PartialEq would.  Every computation runs on the GPU; there
@@ -398,6 +399,28 @@ def g1_mul_many(p, k):
 
 def g2_mul_many(p, k):
     return context().g2_mul_many(p, k)
+
+
+def _images(xs, width):
+    """(n, width) uint64 rows from a sequence of G1 / Fr values or an array of images."""
+    if isinstance(xs, np.ndarray):
+        return _native._arr(xs, width)
+    xs = list(xs)
+    if not xs:
+        return np.zeros((0, width), np.uint64)
+    return np.stack([np.asarray(getattr(x, "img", x), dtype=np.uint64).reshape(width) for x in xs])
+
+
+def g1_msm(points, scalars):
+    """sum of points[i] * scalars[i] as a normalized G1 (bn_g1_msm).  Takes sequences of
+    G1 / Fr or the (n, 12) / (n, 4) image arrays; no terms give G1.zero() without a
+    device call; different lengths raise ValueError."""
+    p, k = _images(points, 12), _images(scalars, 4)
+    if p.shape[0] != k.shape[0]:
+        raise ValueError("g1_msm: %d points and %d scalars" % (p.shape[0], k.shape[0]))
+    if p.shape[0] == 0:
+        return G1.zero()
+    return G1(context().g1_msm(p, k))
 
 
 def g2_affine_new_many(x, y):

@@ -1,0 +1,160 @@
+#!/usr/bin/env python3
+"""Device time of bn_g1_msm_dev per size (HBM-resident inputs, torch events on the
+launch stream, bn_msm_reserve and a warm-up before timing), alternating in one
+process:
+  small    the small path forced (bn_g1_mul_many's kernels, an addition tree of
+           k_g1_op, normalize): what a caller composes from bn_g1_mul_many_dev,
+           ceil(log2 n) x bn_g1_add_many_dev and bn_g1_normalize_many_dev
+  c=K      the bucket path forced at window width K
+  default  a context with untouched settings (the window table and the threshold)
+Before a size is timed every form must return the same 96 bytes, else the script
+exits non-zero.  One JSON line per size, then one line for all-equal scalars at
+--skew terms (one lane per window walks every term: the documented skew limit).
+`frac` is the integer-VALU roofline fraction as DESIGN.md §4.5 counts it:
+algorithmic Fq products x 128 MAD32 over the time, against 39.3 T MAD32/s.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "paritytech-bn_amd"))
+sys.path.insert(0, ROOT)
+
+PEAK_MAD32 = 39.3e12
+ADD, DBL = 16, 7  # Fq products of jac_add / jac_double (curve.h)
+SEGMENT = 16      # kMsmSegment (kernels.h)
+
+
+def windows(c):
+    return 254 // c + 1
+
+
+def bucket_products(n, c):
+    """Fq products of the bucket path by count: n additions per window into the buckets,
+    two per bucket and a (c-1)-bit double-and-add per segment in the reduction, the
+    segment tree, Horner over the windows."""
+    w, nb = windows(c), 1 << (c - 1)
+    nseg = (nb + SEGMENT - 1) // SEGMENT
+    adds = n * w + 2 * nb * w + nseg * w * c + (nseg - 1) * w + (w - 1)
+    dbls = nseg * w * (c - 1) + (w - 1) * c
+    return ADD * adds + DBL * dbls
+
+
+def small_products(n):
+    """254 doublings and 127 additions per term on average, n - 1 additions in the tree"""
+    return n * (254 * DBL + 127 * ADD) + (n - 1) * ADD
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sizes", default="1,16,128,512," + ",".join(str(1 << e) for e in range(10, 21)))
+    ap.add_argument("--windows", default="8,9,10,11,12,13,14,15,16")
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--skew", type=int, default=1 << 18)
+    ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
+    args = ap.parse_args()
+    import torch
+
+    from substrate_bn import Context, synth
+
+    def emit(rec):
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if args.out:
+            with open(args.out, "a") as fh:
+                fh.write(line + "\n")
+
+    dev = torch.device("cuda", 0)
+    ctx, dctx = Context(0), Context(0)
+    sizes = [int(s) for s in args.sizes.split(",")]
+    cs = [int(c) for c in args.windows.split(",")]
+    nmax = max(sizes + [args.skew])
+    s = synth.fr_images_raw(nmax, 0x6d736d31)
+    k = synth.fr_images_raw(nmax, 0x6d736d32, lo=0)
+    g1 = torch.from_numpy(np.tile(synth.g1_one_image().view(np.int64), (nmax, 1))).to(dev)
+    sd = torch.from_numpy(s.view(np.int64)).to(dev)
+    K = torch.from_numpy(k.view(np.int64)).to(dev)
+    P = torch.empty((nmax, 12), dtype=torch.int64, device=dev)
+    stream = torch.cuda.Stream(dev)
+    sh = stream.cuda_stream
+    torch.cuda.synchronize(dev)
+    ctx.g1_mul_many_dev(g1.data_ptr(), sd.data_ptr(), nmax, P.data_ptr(), sh)
+    torch.cuda.synchronize(dev)
+    out = torch.zeros(12, dtype=torch.int64, device=dev)
+
+    def setup(name):
+        """-> the context to call for form `name`, set up for it"""
+        if name == "default":
+            return dctx
+        if name == "small":
+            ctx.set_msm_window(0)
+            ctx.set_msm_min(nmax + 1)
+        else:
+            ctx.set_msm_min(0)
+            ctx.set_msm_window(int(name[2:]))
+        return ctx
+
+    def run(name, n, kd, timed):
+        c = setup(name)
+        if not timed:
+            c.msm_reserve(n)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        with torch.cuda.stream(stream):
+            e0.record()
+            c.g1_msm_dev(P.data_ptr(), kd.data_ptr(), n, out.data_ptr(), sh)
+            e1.record()
+        torch.cuda.synchronize(dev)
+        return e0.elapsed_time(e1), out.cpu().numpy().view(np.uint64).copy()
+
+    def stats(ts):
+        return {"median_ms": round(statistics.median(ts), 4), "min_ms": round(min(ts), 4), "max_ms": round(max(ts), 4)}
+
+    forms = ["small"] + ["c=%d" % c for c in cs] + ["default"]
+    for n in sizes:
+        want = None
+        for f in forms:  # warm-up (allocates) and the agreement check
+            _, got = run(f, n, K, False)
+            if want is None:
+                want = got
+            elif not np.array_equal(got, want):
+                print("MISMATCH at n=%d: %s differs from the small path" % (n, f), file=sys.stderr)
+                sys.exit(1)
+        times = {f: [] for f in forms}
+        for _ in range(args.reps):
+            for f in forms:
+                times[f].append(run(f, n, K, True)[0])
+        rec = {"n": n, "reps": args.reps, "small": stats(times["small"]), "default": stats(times["default"])}
+        rec["small"]["frac"] = round(small_products(n) * 128 / (rec["small"]["median_ms"] * 1e-3) / PEAK_MAD32, 4)
+        best = None
+        for c in cs:
+            st = stats(times["c=%d" % c])
+            st["frac"] = round(bucket_products(n, c) * 128 / (st["median_ms"] * 1e-3) / PEAK_MAD32, 4)
+            rec["c=%d" % c] = st
+            if best is None or st["median_ms"] < rec["c=%d" % best]["median_ms"]:
+                best = c
+        rec["best_c"] = best
+        rec["small_over_best"] = round(rec["small"]["median_ms"] / rec["c=%d" % best]["median_ms"], 3)
+        rec["small_spread_ms"] = round(rec["small"]["max_ms"] - rec["small"]["min_ms"], 4)
+        emit(rec)
+    if args.skew:
+        n = args.skew
+        ke = torch.from_numpy(np.tile(k[7].view(np.int64), (n, 1))).to(dev)
+        torch.cuda.synchronize(dev)
+        _, want = run("small", n, ke, False)
+        dctx.set_msm_min(0)  # the bucket path at the table's window, whatever the threshold
+        dctx.msm_reserve(n)
+        ms, got = run("default", n, ke, True)
+        if not np.array_equal(got, want):
+            print("MISMATCH on the all-equal batch", file=sys.stderr)
+            sys.exit(1)
+        ms_small, _ = run("small", n, ke, True)
+        emit({"skew_all_equal_n": n, "bucket_ms": round(ms, 3), "small_ms": round(ms_small, 3), "reps": 1})
+
+
+if __name__ == "__main__":
+    main()
