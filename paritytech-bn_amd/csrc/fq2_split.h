@@ -224,6 +224,140 @@ BN_INLINE auto fq_dot2(const Fq<X>& x, const Fq<Y>& y, const Fq<Z>& z, const Fq<
     return r;
 }
 
+// BN_DOT2_ADDEND (on by default): fq_dot2 with addends at weight R.  Columns 9..17 of
+// the chain -- the ones that leave as digits 0..8 -- also take digit d of each addend
+// c_j, times a small constant K_j that rides as the multiply-add's inline constant:
+//   r = REDC(x*y + z*w) + sum K_j * c_j   (r * R == x*y + z*w + R * sum K_j * c_j mod p).
+// Small multiples, sums and differences (a subtrahend enters as K*p - c, fq_neg_lazy)
+// that would follow the product as digit-wise passes, K*p spreads and a carry pass
+// cost one multiply-add per digit and leave normalized: next to the 2^58-sized
+// digit products a term K_j * c_j[d] < 2^36 is invisible in the 64-bit accumulator.
+// The value bound of every addend, times its multiplier, adds to the product's.
+// BN_DOT2_ADDEND=0 builds the callers' digit-wise forms (tools/build_variant.sh).
+#ifndef BN_DOT2_ADDEND
+#define BN_DOT2_ADDEND 1
+#endif
+// NA of the three addends are used (the others: K == 0, any operand)
+template <int NA, int K0, int K1, int K2, int X, int Y, int Z, int W, int C0, int C1, int C2>
+BN_INLINE auto fq_dot2_addn(const Fq<X>& x, const Fq<Y>& y, const Fq<Z>& z, const Fq<W>& w, const Fq<C0>& c0,
+                            const Fq<C1>& c1, const Fq<C2>& c2) {
+    static_assert(NA >= 1 && NA <= 3 && K0 >= 1 && (NA > 1 ? K1 >= 1 : K1 == 0) && (NA > 2 ? K2 >= 1 : K2 == 0),
+                  "fq_dot2_add: multipliers of the addends in use");
+    static_assert(K0 <= 64 && K1 <= 64 && K2 <= 64, "fq_dot2_add: a multiplier must be an inline constant");
+    // a column: 54 digit products and 9 m*p terms < 2^58 each (63 * 2^58), a carry < 2^35
+    // and the addend digits, together below 2^50 < 2^58 - 2^35
+    static_assert(kl(X) * kl(Y) + kl(Z) * kl(W) <= 6, "fq_dot2_add: column sum could overflow 64 bits");
+    static_assert((long long)K0 * kl(C0) + (long long)K1 * kl(C1) + (long long)K2 * kl(C2) <= (1 << 20),
+                  "fq_dot2_add: column sum could overflow 64 bits");
+    constexpr int BP = 1 + (int)(((long long)kv(X) * kv(Y) + (long long)kv(Z) * kv(W)) * 5908 / 1000000 + 1);
+    constexpr int BO = BP + K0 * kv(C0) + K1 * kv(C1) + K2 * kv(C2);
+    static_assert(BO <= kMaxBound, "fq_dot2_add: the value must stay below 2^261");
+    Fq<BO> r;
+#if BN_DOT2_ASM && defined(__HIP_DEVICE_COMPILE__)
+    if constexpr ((BN_DOT2_ASM & 1) != 0) {
+        if constexpr (NA == 1) {
+            asm(BN_ASM_DOT2A1 : BN_ASM_OUT9(r.v)
+                : BN_ASM_IN9(x.v), BN_ASM_IN9(y.v), BN_ASM_IN9(z.v), BN_ASM_IN9(w.v), BN_ASM_IN9(c0.v), BN_ASM_P, "n"(K0)
+                : BN_ASM_CLOBBER);
+        } else if constexpr (NA == 2) {
+            asm(BN_ASM_DOT2A2 : BN_ASM_OUT9(r.v)
+                : BN_ASM_IN9(x.v), BN_ASM_IN9(y.v), BN_ASM_IN9(z.v), BN_ASM_IN9(w.v), BN_ASM_IN9(c0.v), BN_ASM_IN9(c1.v),
+                  BN_ASM_P, "n"(K0), "n"(K1)
+                : BN_ASM_CLOBBER);
+        } else {
+            asm(BN_ASM_DOT2A3 : BN_ASM_OUT9(r.v)
+                : BN_ASM_IN9(x.v), BN_ASM_IN9(y.v), BN_ASM_IN9(z.v), BN_ASM_IN9(w.v), BN_ASM_IN9(c0.v), BN_ASM_IN9(c1.v),
+                  BN_ASM_IN9(c2.v), BN_ASM_P, "n"(K0), "n"(K1), "n"(K2)
+                : BN_ASM_CLOBBER);
+        }
+        return r;
+    }
+#endif
+    uint32_t m[9];
+    uint64_t acc = 0;
+#pragma unroll
+    for (int k = 0; k < 18; ++k) {
+        const int lo = k < 9 ? 0 : k - 8;
+        const int hi = k < 9 ? k : 8;
+#pragma unroll
+        for (int i = lo; i <= hi; ++i) {
+            acc += (uint64_t)x.v[i] * y.v[k - i];
+            acc += (uint64_t)z.v[i] * w.v[k - i];
+        }
+#pragma unroll
+        for (int i = lo; i <= hi; ++i)
+            if (i < k) acc += (uint64_t)m[i] * kP29.v[k - i];
+        if (k < 9) {
+            m[k] = ((uint32_t)acc * BN_PINV29) & M29;
+            acc += (uint64_t)m[k] * kP29.v[0];
+        } else {
+            acc += (uint64_t)c0.v[k - 9] * K0;
+            if constexpr (NA > 1) acc += (uint64_t)c1.v[k - 9] * K1;
+            if constexpr (NA > 2) acc += (uint64_t)c2.v[k - 9] * K2;
+            r.v[k - 9] = k < 17 ? (uint32_t)acc & M29 : (uint32_t)acc;
+        }
+        acc >>= 29;
+    }
+    return r;
+}
+template <int K0, int X, int Y, int Z, int W, int C0>
+BN_INLINE auto fq_dot2_add(const Fq<X>& x, const Fq<Y>& y, const Fq<Z>& z, const Fq<W>& w, const Fq<C0>& c0) {
+    return fq_dot2_addn<1, K0, 0, 0>(x, y, z, w, c0, c0, c0);
+}
+template <int K0, int K1, int X, int Y, int Z, int W, int C0, int C1>
+BN_INLINE auto fq_dot2_add(const Fq<X>& x, const Fq<Y>& y, const Fq<Z>& z, const Fq<W>& w, const Fq<C0>& c0,
+                           const Fq<C1>& c1) {
+    return fq_dot2_addn<2, K0, K1, 0>(x, y, z, w, c0, c1, c1);
+}
+template <int K0, int K1, int K2, int X, int Y, int Z, int W, int C0, int C1, int C2>
+BN_INLINE auto fq_dot2_add(const Fq<X>& x, const Fq<Y>& y, const Fq<Z>& z, const Fq<W>& w, const Fq<C0>& c0,
+                           const Fq<C1>& c1, const Fq<C2>& c2) {
+    return fq_dot2_addn<3, K0, K1, K2>(x, y, z, w, c0, c1, c2);
+}
+
+// K0*c0 + K1*c1 [+ K2*c2] with normalized digits: the addends without a product, as
+// one carry chain (dot2_asm.inc LIN2 / LIN3: per digit the carry shift, one
+// multiply-add per term and the 29-bit extract).  For combinations whose multiples
+// overflow a 32-bit digit (9 * b) or would need a carry pass of their own.
+template <int NA, int K0, int K1, int K2, int C0, int C1, int C2>
+BN_INLINE auto fq_linn(const Fq<C0>& c0, const Fq<C1>& c1, const Fq<C2>& c2) {
+    static_assert((NA == 2 || NA == 3) && K0 >= 1 && K1 >= 1 && (NA > 2 ? K2 >= 1 : K2 == 0), "fq_lin: multipliers");
+    static_assert(K0 <= 64 && K1 <= 64 && K2 <= 64, "fq_lin: a multiplier must be an inline constant");
+    // a digit's sum < 3 * 64 * 7 * 2^29 and the carry < 2^12: far below 2^64
+    constexpr int BO = K0 * kv(C0) + K1 * kv(C1) + K2 * kv(C2);
+    static_assert(BO <= kMaxBound, "fq_lin: the value must stay below 2^261");
+    Fq<BO> r;
+#if BN_DOT2_ASM && defined(__HIP_DEVICE_COMPILE__)
+    if constexpr ((BN_DOT2_ASM & 1) != 0) {
+        if constexpr (NA == 2) {
+            asm(BN_ASM_LIN2 : BN_ASM_OUT9(r.v) : BN_ASM_IN9(c0.v), BN_ASM_IN9(c1.v), "n"(K0), "n"(K1) : BN_ASM_CLOBBER);
+        } else {
+            asm(BN_ASM_LIN3 : BN_ASM_OUT9(r.v)
+                : BN_ASM_IN9(c0.v), BN_ASM_IN9(c1.v), BN_ASM_IN9(c2.v), "n"(K0), "n"(K1), "n"(K2)
+                : BN_ASM_CLOBBER);
+        }
+        return r;
+    }
+#endif
+    uint64_t acc = 0;
+#pragma unroll
+    for (int d = 0; d < 9; ++d) {
+        acc += (uint64_t)c0.v[d] * K0 + (uint64_t)c1.v[d] * K1;
+        if constexpr (NA > 2) acc += (uint64_t)c2.v[d] * K2;
+        r.v[d] = d < 8 ? (uint32_t)acc & M29 : (uint32_t)acc;
+        acc >>= 29;
+    }
+    return r;
+}
+template <int K0, int K1, int C0, int C1>
+BN_INLINE auto fq_lin(const Fq<C0>& c0, const Fq<C1>& c1) {
+    return fq_linn<2, K0, K1, 0>(c0, c1, c1);
+}
+template <int K0, int K1, int K2, int C0, int C1, int C2>
+BN_INLINE auto fq_lin(const Fq<C0>& c0, const Fq<C1>& c1, const Fq<C2>& c2) {
+    return fq_linn<3, K0, K1, K2>(c0, c1, c2);
+}
+
 // fq2.rs:136-148 (the same residues as fq2_mul_sb): lane 0 computes
 // c0 = a0*b0 + a1*(K*p - b1), lane 1 computes c1 = a1*b0 + a0*b1, both as
 // own_a * Y + partner_a * W with per-lane operand choice.
@@ -254,6 +388,54 @@ BN_INLINE auto fq2_mul_split(const Fq2<A>& a, const Fq2<B>& b) {
 #endif
         return wrap2(fq_dot2(a.c, y, pa, w));
     }
+}
+// The cyclotomic square on the addend chains (tower.h fq12_cyclotomic_sqr).
+// BN_CYC_LIN bits: 1 = the product's operand xi*b + a, 2 = the outputs n1 and n5,
+// 4 = n2 through fq_lin instead of digit-wise passes.  Off by default: 116 VALU fewer
+// per square, but k_pairing_full then spills 108 B more per lane and runs 3-5 %
+// slower; kernels_gtpow.hip turns all three on (profiles/r7_ab_cyc_lin.txt).
+#ifndef BN_CYC_LIN
+#define BN_CYC_LIN 0
+#endif
+// fq2_cyc_xt: the partner's coordinate of tmp with the sign of -xi * tmp's cross
+// term -- lane 0: tmp1, lane 1: K*p - tmp0.
+template <int T>
+BN_INLINE auto fq2_cyc_xt(const Fq2<T>& tmp) {
+    return fq_partner(fq_pick(lane_odd(), tmp.c, fq_neg_lazy(tmp.c)));
+}
+// fq2_cyc_u: t - z = (a + b)(xi*b + a) - (1 + xi)*tmp - z,  tmp = a*b,  xi = 9 + u,
+// per lane own(product) - 10*own(tmp) + xt - own(z).  The product is
+// fq2_mul_split's column sum; the three terms enter it as 10 * (K*p - tmp), xt
+// and K*p - z.  Its operand xi*b + a = 9*own(b) + (lane 0: K*p - b1, lane 1: b0)
+// + own(a) is fq2_mul_xi and a carry pass, or with BN_CYC_LIN & 1 one fq_lin chain
+// (9 * b overflows a 32-bit digit).  Normalized digits, value bound the product's + 39.
+template <int A, int B, int T, int XT, int ZB>
+BN_INLINE auto fq2_cyc_u(const Fq2<A>& a, const Fq2<B>& b, const Fq2<T>& tmp, const Fq<XT>& xt, const Fq2<ZB>& zs) {
+    static_assert(kl(T) == 1 && kl(ZB) == 1, "fq2_cyc_u: normalized tmp and z");
+    const bool odd = lane_odd();
+    const auto s = fq2_add(a, b);
+#if BN_CYC_LIN & 1
+    const auto pb = fq_partner(b.c);
+    const auto y2 = fq_lin<9, 1>(b.c, fq_add(fq_pick(odd, pb, fq_neg_lazy(pb)), a.c));
+#else
+    const auto y2 = fq_norm(fq_add(fq2_mul_xi(b).c, a.c));
+    (void)odd;
+#endif
+    static_assert(split_mul_cost(kl(decltype(s.c)::kK), 1) <= 6, "fq2_cyc_u: column budget");
+    const auto ps = fq_partner(s.c);
+    const auto ntmp = fq_neg_lazy(tmp.c);
+    const auto nz = fq_neg_lazy(zs.c);
+#if defined(__HIP_DEVICE_COMPILE__)
+    const auto y = fq_bcast_c0(y2);
+    const auto ny = fq_neg_lazy(y2);
+    Fq<kjoin(decltype(y2)::kK, decltype(ny)::kK)> w;
+    dpp_sel_own_partner(w.v, y2.v, ny.v);
+#else
+    const auto py = fq_partner(y2);
+    const auto y = fq_select(odd, py, y2);
+    const auto w = fq_pick(odd, y2, fq_neg_lazy(py));
+#endif
+    return wrap2(fq_dot2_add<10, 1, 1>(s.c, y, ps, w, ntmp, xt, nz));
 }
 template <int A, int B>
 BN_INLINE auto fq2_mul(const Fq2<A>& a_in, const Fq2<B>& b_in) {

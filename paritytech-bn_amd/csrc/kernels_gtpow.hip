@@ -27,6 +27,12 @@
 #ifndef BN_FOLD_LDS
 #define BN_FOLD_LDS 1
 #endif
+// the cyclotomic square's operand and odd outputs through fq_lin (fq2_split.h
+// BN_CYC_LIN): k_gt_pow -4.4 % here; k_pairing_full spills with it and runs slower,
+// so the other units keep the digit-wise forms (profiles/r7_ab_cyc_lin.txt)
+#ifndef BN_CYC_LIN
+#define BN_CYC_LIN 7
+#endif
 #include <type_traits>
 
 #include "fq.h"

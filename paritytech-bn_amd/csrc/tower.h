@@ -846,6 +846,42 @@ BN_INLINE auto fq12_cyclotomic_sqr(const Fq12<A>& a) {
     const auto& z2 = a.c1.c0;
     const auto& z1 = a.c1.c1;
     const auto& z5 = a.c1.c2;
+#if BN_SPLIT && BN_DOT2_ADDEND
+    // On the addend chains (fq2_split.h): the even outputs n = 3t - 2z = 3(t - z) + z
+    // with t - z straight from the product's chain (fq2_cyc_u) -- no xi * tmp pass,
+    // K*p spreads or carry pass for t, and 3u + z keeps its digits below 4 * 2^29,
+    // so the fold takes it as it is: 258 VALU fewer per square, k_pairing_full
+    // 7.30-7.33 -> 7.17-7.19 ms (profiles/r7_ab_cyc_addend.txt).  The odd outputs stay
+    // digit-wise; with BN_CYC_LIN (fq2_split.h; the Gt::pow unit) 6 * tmp + 2z and
+    // n2 = 6 * xi * tmp45 + 2 * z2 = 54 * own - 6 * xt + 2 * z2 are one carry chain
+    // each (fq_lin), normalized
+    auto tmp01 = fq2_mul(z0, z1);
+    auto u0 = fq2_cyc_u(z0, z1, tmp01, fq2_cyc_xt(tmp01), z0);
+    auto tmp23 = fq2_mul(z2, z3);
+    auto u2 = fq2_cyc_u(z2, z3, tmp23, fq2_cyc_xt(tmp23), z4);
+    auto tmp45 = fq2_mul(z4, z5);
+    auto xt45 = fq2_cyc_xt(tmp45);
+    auto u4 = fq2_cyc_u(z4, z5, tmp45, xt45, z3);
+
+    auto n0 = fq2_add(fq2_add(fq2_dbl(u0), u0), z0);
+    auto n3 = fq2_add(fq2_add(fq2_dbl(u4), u4), z3);
+    auto n4 = fq2_add(fq2_add(fq2_dbl(u2), u2), z4);
+#if BN_CYC_LIN & 2
+    auto n1 = wrap2(fq_lin<6, 2>(tmp01.c, z1.c));
+    auto n5 = wrap2(fq_lin<6, 2>(tmp23.c, z5.c));
+#else
+    auto t1 = fq2_dbl(tmp01);
+    auto t3 = fq2_dbl(tmp23);
+    auto n1 = fq2_add(fq2_dbl(fq2_add(t1, z1)), t1);
+    auto n5 = fq2_add(fq2_dbl(fq2_add(t3, z5)), t3);
+#endif
+#if BN_CYC_LIN & 4
+    auto n2 = wrap2(fq_lin<54, 6, 2>(tmp45.c, fq_neg_lazy(xt45), z2.c));
+#else
+    auto x5 = BN_CYC_T(fq2_dbl(fq2_mul_xi(tmp45)));  // xi * t5
+    auto n2 = fq2_add(fq2_dbl(fq2_add(x5, z2)), x5);
+#endif
+#else
     auto tmp01 = fq2_mul(z0, z1);
     auto t0 = BN_CYC_T(fq2_sub(fq2_sub(fq2_mul(fq2_add(z0, z1), fq2_add(fq2_mul_xi(z1), z0)), tmp01), fq2_mul_xi(tmp01)));
     auto t1 = fq2_dbl(tmp01);
@@ -863,6 +899,7 @@ BN_INLINE auto fq12_cyclotomic_sqr(const Fq12<A>& a) {
     auto n3 = fq2_add(fq2_dbl(fq2_sub(t4, z3)), t4);
     auto n4 = fq2_add(fq2_dbl(fq2_sub(t2, z4)), t2);
     auto n5 = fq2_add(fq2_dbl(fq2_add(t3, z5)), t3);
+#endif
     return mk12(mk6(n0, n4, n3), mk6(n2, n1, n5));
 }
 

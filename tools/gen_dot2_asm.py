@@ -24,6 +24,21 @@ half feeds v_mul_lo_u32 / v_bfe_u32, and an asm operand cannot name half of a
 64-bit operand); m_k lives in output operand k, whose digit is written only
 after m_k's last use (column k + 8 < k + 9).  vcc takes the unused carry-out.
 Operands: %0-%8 r (=&v), then x, y[, z, w] (v), then p_0..p_8 and -p^-1 (s).
+
+Addend-taking kinds ('dot2a1' .. 'dot2a3'): the dot2 chain, whose columns 9..17 --
+the ones that leave as output digits 0..8, i.e. weight R = 2^261 -- also take digit d
+of up to three addend vectors c_j as v_mad_u64_u32 acc, c_j[d], K_j, acc with K_j an
+inline constant ("n" operand): r * R == x*y + z*w + R * sum(K_j * c_j) (mod p), so
+r == REDC(x*y + z*w) + sum(K_j * c_j) as an integer.  A small multiple and a sum of
+terms that would be digit-wise passes and a carry pass after the product cost one
+multiply-add per digit here and leave normalized.  Operands: r, x, y, z, w, c_0[,
+c_1[, c_2]] (v), p_0..p_8, -p^-1 (s), K_0[, K_1[, K_2]] (n).
+
+Linear kinds ('lin2', 'lin3'): no product, only the addends -- the normalized digits
+of sum(K_j * c_j) as one carry chain (per digit: the carry shift, one multiply-add per
+term, the 29-bit extract), for a small-constant combination whose multiples would
+overflow 32-bit digits or need a carry pass of their own.  Operands: r, c_0, c_1[,
+c_2] (v), K_0, K_1[, K_2] (n).
 """
 import os
 
@@ -34,7 +49,12 @@ ACC_LO = "v2"
 def gen(kind):
     """kind: 'dot2' (x*y + z*w), 'dot6' (sum of six products, pairing.h's sparse line
     product), 'mul' (x*y) or 'sqr' (x*x with doubled cross terms: d = 2x)"""
-    nin = {"dot2": 4, "dot6": 12, "mul": 2, "sqr": 2}[kind]
+    if kind.startswith("lin"):
+        return gen_lin(int(kind[3:]))
+    nadd = int(kind[5:]) if kind.startswith("dot2a") else 0  # addend vectors at weight R
+    if nadd:
+        kind = "dot2"
+    nin = {"dot2": 4, "dot6": 12, "mul": 2, "sqr": 2}[kind] + nadd
     X = lambda i: "%%%d" % (9 + i)                    # noqa: E731
     Y = lambda j: "%%%d" % (18 + j)                   # noqa: E731 (sqr: the doubled digits d)
     Z = lambda i: "%%%d" % (27 + i)                   # noqa: E731
@@ -43,6 +63,8 @@ def gen(kind):
     P = lambda j: "%%%d" % (pbase + j)                # noqa: E731
     PINV = "%%%d" % (pbase + 9)
     M = lambda i: "%%%d" % i                          # noqa: E731
+    C = lambda t, d: "%%%d" % (45 + 9 * t + d)        # noqa: E731 (addend t, digit d)
+    KC = lambda t: "%%%d" % (pbase + 10 + t)          # noqa: E731 (its multiplier)
     out = []
     first = True
 
@@ -77,10 +99,29 @@ def gen(kind):
             out.append("v_bfe_u32 %s, %s, 0, 29" % (M(k), M(k)))
             mad(M(k), P(0))
         else:
+            for t in range(nadd):
+                mad(C(t, k - 9), KC(t))
             out.append("v_bfe_u32 %s, %s, 0, 29" % (M(k - 9), ACC_LO))
     out.append("v_lshrrev_b64 %s, 29, %s" % (ACC, ACC))
+    for t in range(nadd):
+        mad(C(t, 8), KC(t))
     out.append("v_mov_b32 %s, %s" % (M(8), ACC_LO))
     return out
+
+
+def gen_lin(n):
+    out = []
+    for d in range(9):
+        if d:
+            out.append("v_lshrrev_b64 %s, 29, %s" % (ACC, ACC))
+        for t in range(n):
+            out.append("v_mad_u64_u32 %s, vcc, %%%d, %%%d, %s" % (ACC, 9 + 9 * t + d, 9 + 9 * n + t,
+                                                             ACC if d or t else "0"))
+        out.append("v_bfe_u32 %%%d, %s, 0, 29" % (d, ACC_LO) if d < 8 else "v_mov_b32 %%8, %s" % ACC_LO)
+    return out
+
+
+KINDS = ("dot2", "mul", "sqr", "dot6", "dot2a1", "dot2a2", "dot2a3", "lin2", "lin3")
 
 
 def main():
@@ -88,9 +129,11 @@ def main():
     dst = os.path.join(here, "..", "paritytech-bn_amd", "csrc", "dot2_asm.inc")
     lines = ["// dot2_asm.inc -- GENERATED by tools/gen_dot2_asm.py (do not edit): the single-chain",
              "// column sums of fq_dot2 / fq_mul / fq_sqr (fq2_split.h, fq.h BN_DOT2_ASM) and of the",
-             "// six-product sum of the sparse line product (pairing.h, BN_DOT6_ASM).",
+             "// six-product sum of the sparse line product (pairing.h, BN_DOT6_ASM); DOT2A<n>: dot2",
+             "// with n addend vectors at weight R, LIN<n>: the normalized sum of n small multiples",
+             "// (fq2_split.h fq_dot2_add, fq_lin; BN_DOT2_ADDEND).",
              "#pragma once"]
-    for kind in ("dot2", "mul", "sqr", "dot6"):
+    for kind in KINDS:
         ins = gen(kind)
         nmad = sum(1 for s in ins if s.startswith("v_mad"))
         lines.append("// %s: %d instructions, %d v_mad_u64_u32" % (kind, len(ins), nmad))
