@@ -271,6 +271,13 @@ int bn_set_phase_timing(bn_ctx* ctx, int enable);
  * $BN254MI_FE_WIDE_MAX; results are identical either way.  On a multi-device
  * context it applies to every device. */
 int bn_set_fe_wide_max(bn_ctx* ctx, size_t n);
+/* Which build of the two-lane step machine bn_fq12_op_many runs: 0 (default) the final
+ * exponentiation unit's (k_fq12_vm), 1 the one inside the throughput kernel's unit
+ * (k_fq12_vm_pairing: the Fq12 operations exactly as k_pairing_full runs them).  The two
+ * are built with different forms of the Fq12 product, square and cyclotomic square;
+ * results are identical.  Meant for checking single operations of the throughput
+ * kernel on chosen operands.  On a multi-device context it applies to every device. */
+int bn_set_fq12_op_unit(bn_ctx* ctx, int unit);
 /* Within the latency path, bn_pairing_many_dev batches of at most n pairs run the
  * whole pairing in ONE launch (k_pairing_latency: a wave computing the 87 lines of
  * each pair feeds, through an LDS ring, 16-lane groups running the Miller loop and

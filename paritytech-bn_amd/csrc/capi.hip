@@ -1412,6 +1412,16 @@ int bn_set_latency_max(bn_ctx* c, size_t n) {
     c->latency_max = n;
     return BN_OK;
 }
+int bn_set_fq12_op_unit(bn_ctx* c, int unit) {
+    if (c && !c->subs.empty()) {
+        for (bn_ctx* d : c->subs) RET_IF(bn_set_fq12_op_unit(d, unit));
+        return BN_OK;
+    }
+    CTX_GUARD(c);
+    if (unit != 0 && unit != 1) return fail(c, BN_ERR_INVALID_ARGUMENT, "unit must be 0 or 1");
+    c->fq12_op_unit = unit;
+    return BN_OK;
+}
 int bn_set_fe_wide_max(bn_ctx* c, size_t n) {
     if (c && !c->subs.empty()) {
         for (bn_ctx* d : c->subs) RET_IF(bn_set_fe_wide_max(d, n));
@@ -1734,7 +1744,10 @@ int bn_fq12_op_many(bn_ctx* c, int op, const bn_gt* a, const bn_gt* b, size_t n,
         }
         P.finalize({res});
         HIPCHK(c, hipMemcpyAsync(dprog, P.s.data(), P.s.size() * 4, hipMemcpyHostToDevice, c->stream));
-        k_fq12_vm<<<grid_pair(kPathLanes * m), kPairBlock, 0, c->stream>>>(dprog, P.steps(), c->slots, m);
+        if (c->fq12_op_unit == 1)
+            k_fq12_vm_pairing<<<grid_pair(kPathLanes * m), kPairBlock, 0, c->stream>>>(dprog, P.steps(), c->slots, m);
+        else
+            k_fq12_vm<<<grid_pair(kPathLanes * m), kPairBlock, 0, c->stream>>>(dprog, P.steps(), c->slots, m);
         k_gt_store<<<grid_for(kPathLanes * m), kBlock, 0, c->stream>>>(c->slots + (size_t)res * kSlotWords * m, m, m, dout);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipMemcpyAsync(out + off, dout, m * sizeof(bn_gt), hipMemcpyDeviceToHost, c->stream));

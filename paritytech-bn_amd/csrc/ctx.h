@@ -37,6 +37,9 @@ struct bn_ctx {
     // wide layout (kernels_wide.hip, 16 lanes per element: latency) instead of
     // the step machine (k_fq12_vm, 2 lanes per element: throughput)
     size_t fe_wide_max = 0;
+    // bn_fq12_op_many's step machine: 0 = k_fq12_vm (kernels_fe.hip), 1 = k_fq12_vm_pairing
+    // (kernels_pairing.hip: the build of the operations that k_pairing_full runs)
+    int fq12_op_unit = 0;
     // A/B switch ($BN254MI_MILLER_FORM) for bn_pairing_many_dev batches above the
     // wide threshold: 1 (default, measured fastest) = to_affine,
     // line steps and Miller loop fused in one kernel (k_pairing_fused, no

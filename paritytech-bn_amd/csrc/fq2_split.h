@@ -392,8 +392,10 @@ BN_INLINE auto fq2_mul_split(const Fq2<A>& a, const Fq2<B>& b) {
 // The cyclotomic square on the addend chains (tower.h fq12_cyclotomic_sqr).
 // BN_CYC_LIN bits: 1 = the product's operand xi*b + a, 2 = the outputs n1 and n5,
 // 4 = n2 through fq_lin instead of digit-wise passes.  Off by default: 116 VALU fewer
-// per square, but k_pairing_full then spills 108 B more per lane and runs 3-5 %
-// slower; kernels_gtpow.hip turns all three on (profiles/r7_ab_cyc_lin.txt).
+// per square, but next to the Karatsuba Fq12 products k_pairing_full then spills 108 B
+// more per lane and runs 3-5 % slower (profiles/r7_ab_cyc_lin.txt).  kernels_gtpow.hip
+// turns all three on, and so does kernels_pairing.hip since its Fq12 products run on
+// six-product column sums (tower.h BN_FQ6_LAZY; profiles/r8_ab_fq6_lazy.txt).
 #ifndef BN_CYC_LIN
 #define BN_CYC_LIN 0
 #endif

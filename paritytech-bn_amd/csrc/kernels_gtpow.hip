@@ -28,8 +28,9 @@
 #define BN_FOLD_LDS 1
 #endif
 // the cyclotomic square's operand and odd outputs through fq_lin (fq2_split.h
-// BN_CYC_LIN): k_gt_pow -4.4 % here; k_pairing_full spills with it and runs slower,
-// so the other units keep the digit-wise forms (profiles/r7_ab_cyc_lin.txt)
+// BN_CYC_LIN): k_gt_pow -4.4 % here (profiles/r7_ab_cyc_lin.txt).  The Fq12 products stay
+// Karatsuba: over six-product column sums (tower.h BN_FQ6_LAZY=3) k_gt_pow ran 0.4-1.0 %
+// slower in every round despite 312 -> 156 B of scratch (profiles/r8_ab_fq6_lazy.txt)
 #ifndef BN_CYC_LIN
 #define BN_CYC_LIN 7
 #endif

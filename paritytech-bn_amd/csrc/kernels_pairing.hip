@@ -7,6 +7,27 @@
 #ifndef BN_FOLD_LDS
 #define BN_FOLD_LDS 1
 #endif
+// The Fq12 product and square over six-product column sums (tower.h BN_FQ6_LAZY; bit 1 the
+// product, bit 2 the square): k_pairing_full 2,069,552 -> 2,002,782 weighted VALU per
+// lane, scratch 548 -> 544 B, 7.13 -> 7.04 ms (-1.2 %).  With them the cyclotomic
+// square's operand and odd outputs through fq_lin (fq2_split.h BN_CYC_LIN) no longer
+// spill -- 512 B per lane, where they took the Karatsuba build to 660 B and made it
+// slower -- and take 113 VALU more off each square: 1,981,210, 6.98-7.02 ms (-1.5 to
+// -2.1 %, every round faster than both; profiles/r8_ab_fq6_lazy.txt).  kernels_fe.hip
+// and kernels_gtpow.hip measured no gain with BN_FQ6_LAZY and keep the Karatsuba form.
+// BN_CYC_LIN's default here is 7 only next to BN_FQ6_LAZY == 3, the combination that was
+// measured; with any other BN_FQ6_LAZY it is 0 unless given, so -DBN_FQ6_LAZY=0 alone
+// builds the Karatsuba form with the digit-wise square, as before.
+#ifndef BN_FQ6_LAZY
+#define BN_FQ6_LAZY 3
+#endif
+#ifndef BN_CYC_LIN
+#if BN_FQ6_LAZY == 3
+#define BN_CYC_LIN 7
+#else
+#define BN_CYC_LIN 0
+#endif
+#endif
 #include "fq.h"
 #define BN_SPLIT BN_PATH_SPLIT
 #include "kernels.h"
@@ -164,6 +185,20 @@ __global__ void BN_PATH_ATTR __launch_bounds__(kPairBlock) k_pairing_fused(const
     Fq12<kF> f = miller_fused(a.qa, a.px, a.py, [&](int d) { balance_step(bal, (uint32_t)d); });
     if (flags[l]) f = widen<kF>(fq12_one());
     st_fq12(f_out, nl, l, f);
+}
+
+// The step machine as this unit builds it (k_pairing_full's: the Fq12 product and square
+// on column sums, the cyclotomic square's linear chains), over values already in the
+// slots, as kernels_fe.hip's k_fq12_vm.  bn_fq12_op_many runs it on a context with
+// bn_set_fq12_op_unit(ctx, 1), which is how single operations of this unit's build are
+// checked on chosen operands (tests/test_gpu_fq6_lazy.py).
+__global__ void BN_PATH_ATTR __launch_bounds__(kPairBlock) k_fq12_vm_pairing(const uint32_t* __restrict__ prog,
+                                                                            int nsteps, uint32_t* slots, size_t n) {
+    fold_table_init();
+    const Balance bal = balance_init();
+    const size_t i = lane_id();
+    if (i >= kL * n) return;
+    (void)fq12_vm_run(prog, nsteps, slots, kL * n, i, bal, 0, true);
 }
 
 // A/B form (miller_form 3): k_pairing_fused, k_fq12_vm and

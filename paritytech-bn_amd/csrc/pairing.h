@@ -42,48 +42,22 @@ BN_INLINE void g2_precompute(const G2Aff<B>& q, Emit&& emit) {
 }
 
 #if BN_SPLIT
-// BN_DOT6_ASM: each output's six-product column sum as one v_mad_u64_u32 chain
-// (dot2_asm.inc) instead of 17 64-bit column accumulators: k_miller_seg's loop
-// spilled 27 dwords and reloaded 44 per line with the accumulators (scratch 320 ->
-// 72 B per lane), config 5 1.84-1.90 -> 1.76-1.80 ms and its PMC traffic 1.62 ->
-// 0.80 GB per product, k_pairing_full unchanged (profiles/r5w_ab_dot6.txt)
-#ifndef BN_DOT6_ASM
-#define BN_DOT6_ASM 1
-#endif
 // The same product f * (x0 + x4 w^3 + x2 w^4) on the two-lane layout, as six
 // column sums reduced once each.  In the w-basis (f_m = coefficient of w^m:
 // c0.c(m/2) for even m, c1.c((m-1)/2) for odd m; w^6 = xi)
 //   out_m = f_m x0 + f_(m-3) x4 + f_(m-4) x2,  indices mod 6, times xi on a wrap,
 // with xi moved onto the f side (xi f_2 .. xi f_5).  Each lane sums its
 // coordinate of three Fq2 products -- six digit products, own(u) * v0 +
-// partner(u) * (lane 0: K*p - v1, lane 1: v1) -- in one column accumulator and
-// reduces once: 36 products + 6 reductions per lane instead of the 13-product
+// partner(u) * (lane 0: K*p - v1, lane 1: v1) -- in one column sum (tower.h fq_dot6)
+// and reduces once: 36 products + 6 reductions per lane instead of the 13-product
 // formula's 26 + 13, and no combining adds, subtractions or folds.  The line
 // side's operand forms are built once per coefficient.  The value is the
 // reference's product (fq12.rs:130-196) -- the same residues.
-struct LineOps {
-    Fq<kLine> y;  // v0 on both lanes
-    Fq<8> w;      // lane 0: K*p - v1, lane 1: v1 (normalized digits, value <= (kLine + 1) p)
-};
+using LineOps = LineOpsT<kLine, kLine + 1>;
 template <int X>
 BN_INLINE LineOps line_ops(const Fq2<X>& v_in) {
-    const Fq<kv(X)> v = fq_norm(v_in.c);
-    const bool odd = lane_odd();
-#if defined(__HIP_DEVICE_COMPILE__)
-    // w as fq2_mul_split forms it: the odd lane's own v1, the even lane the partner's K*p - v1
-    Fq<kjoin(kv(X), kenc(kv(X) + 1, 2))> w;
-    dpp_sel_own_partner(w.v, v.v, fq_neg_lazy(v).v);
-    (void)odd;
-    return {widen<kLine>(fq_bcast_c0(v)), widen<8>(fq_norm(w))};
-#else
-    const Fq<kv(X)> pv = fq_partner(v);
-    return {widen<kLine>(fq_select(odd, pv, v)), widen<8>(fq_norm(fq_pick(odd, v, fq_neg_lazy(pv))))};
-#endif
-}
-// t += u * v for this lane's coordinate (u: f side, normalized)
-BN_INLINE void acc_mad2(Acc& t, const Fq<2>& u, const LineOps& v) {
-    acc_mad(t, u, v.y);
-    acc_mad(t, fq_partner(u), v.w);
+    const auto o = line_ops_of(v_in);
+    return {widen<kLine>(o.y), widen<kLine + 1>(o.w)};
 }
 template <int F, int X>
 BN_INLINE Fq12<2> fq12_mul_by_024_lazy(const Fq12<F>& f_in, const Fq2<X>& x0_in, const Fq2<X>& x4_in,
@@ -96,24 +70,9 @@ BN_INLINE Fq12<2> fq12_mul_by_024_lazy(const Fq12<F>& f_in, const Fq2<X>& x0_in,
     // value per lane <= 3 * (2p * 4p + 2p * 5p) = 54 p^2: the reduction is below 1.4 p
     auto out = [&](const Fq<2>& a, const LineOps& va, const Fq<2>& b, const LineOps& vb, const Fq<2>& c,
                    const LineOps& vc) {
-#if BN_DOT6_ASM && BN_DOT2_ASM && defined(__HIP_DEVICE_COMPILE__)
-        // the same six-product column sum as one v_mad_u64_u32 chain (dot2_asm.inc
-        // BN_ASM_DOT6): no 17-column accumulator held across the products
-        const Fq<2> pa = fq_partner(a), pb = fq_partner(b), pc = fq_partner(c);
-        Fq<2> r;
-        asm(BN_ASM_DOT6 : BN_ASM_OUT9(r.v)
-            : BN_ASM_IN9(a.v), BN_ASM_IN9(va.y.v), BN_ASM_IN9(pa.v), BN_ASM_IN9(va.w.v), BN_ASM_IN9(b.v),
-              BN_ASM_IN9(vb.y.v), BN_ASM_IN9(pb.v), BN_ASM_IN9(vb.w.v), BN_ASM_IN9(c.v), BN_ASM_IN9(vc.y.v),
-              BN_ASM_IN9(pc.v), BN_ASM_IN9(vc.w.v), BN_ASM_P
-            : BN_ASM_CLOBBER);
-        return Fq2<2>{r};
-#else
-        Acc t = {};
-        acc_mad2(t, a, va);
-        acc_mad2(t, b, vb);
-        acc_mad2(t, c, vc);
-        return Fq2<2>{acc_redc<2>(t)};
-#endif
+        // this call's contract: f side below 2 p, y <= kLine p, w <= (kLine + 1) p; the
+        // value per lane stays <= 54 p^2 and the reduction below 1.4 p (fq_dot6 asserts it)
+        return Fq2<2>{fq_dot6(a, va, b, vb, c, vc)};
     };
     // outputs last-first, each xi*f_k made just before its first use: under the default
     // scheduler 0.7 % faster than first-first with the four xi*f_k up front

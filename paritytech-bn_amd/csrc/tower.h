@@ -657,6 +657,138 @@ BN_INLINE auto fq6_mul(const Fq6<A>& a, const Fq6<B>& b) {
     return mk6(fq2_add(fq2_mul_xi(t0), a_a), fq2_add(t1, fq2_mul_xi(c_c)), fq2_sub(fq2_add(t2, b_b), c_c));
     }
 }
+#if BN_SPLIT
+// ---------------------------------------------------------------- six-product column sums
+// An Fq2 operand v in the forms a two-lane product takes it in (fq2_mul_split's y and w),
+// built once and shared by every sum that multiplies by v.
+template <int Y, int W>
+struct LineOpsT {
+    Fq<Y> y;  // v0 on both lanes
+    Fq<W> w;  // lane 0: K*p - v1, lane 1: v1 (normalized digits, value <= (Y + 1) p)
+};
+template <int X>
+BN_INLINE LineOpsT<kv(X), kv(X) + 1> line_ops_of(const Fq2<X>& v_in) {
+    const Fq<kv(X)> v = fq_norm(v_in.c);
+    const bool odd = lane_odd();
+#if defined(__HIP_DEVICE_COMPILE__)
+    // w as fq2_mul_split forms it: the odd lane's own v1, the even lane the partner's K*p - v1
+    Fq<kjoin(kv(X), kenc(kv(X) + 1, 2))> w;
+    dpp_sel_own_partner(w.v, v.v, fq_neg_lazy(v).v);
+    (void)odd;
+    return {fq_bcast_c0(v), fq_norm(w)};
+#else
+    const Fq<kv(X)> pv = fq_partner(v);
+    return {fq_select(odd, pv, v), fq_norm(fq_pick(odd, v, fq_neg_lazy(pv)))};
+#endif
+}
+// BN_DOT6_ASM: the sum as one v_mad_u64_u32 chain (dot2_asm.inc BN_ASM_DOT6) instead of
+// 17 64-bit column accumulators: k_miller_seg's loop spilled 27 dwords and reloaded 44
+// per line with the accumulators (scratch 320 -> 72 B per lane), config 5 1.84-1.90 ->
+// 1.76-1.80 ms and its PMC traffic 1.62 -> 0.80 GB per product, k_pairing_full unchanged
+// (profiles/r5w_ab_dot6.txt)
+#ifndef BN_DOT6_ASM
+#define BN_DOT6_ASM 1
+#endif
+// This lane's coordinate of a * va + b * vb + c * vc over Fq2, reduced once:
+//   REDC(sum over the three of own(u) * v.y + partner(u) * v.w),   pu = fq_partner(u).
+// Contract: every operand has normalized digits, so a column holds at most 54 digit
+// products and 9 m * p terms, each below 2^58, and a carry below 2^35: under 2^64
+// whatever the value bounds.  The value S * p^2, S = sum of U * (Y + W), reduces to
+// at most (1 + S * p / R) * p; the sparse line product has S = 3 * 2 * (4 + 5) = 54 and
+// leaves below 1.4 p.
+template <int A, int B, int C, int YA, int WA, int YB, int WB, int YC, int WC>
+BN_INLINE auto fq_dot6p(const Fq<A>& a, const Fq<A>& pa, const LineOpsT<YA, WA>& va, const Fq<B>& b, const Fq<B>& pb,
+                        const LineOpsT<YB, WB>& vb, const Fq<C>& c, const Fq<C>& pc, const LineOpsT<YC, WC>& vc) {
+    static_assert(kl(A) == 1 && kl(B) == 1 && kl(C) == 1, "fq_dot6: normalized u-side digits");
+    static_assert(kl(YA) == 1 && kl(WA) == 1 && kl(YB) == 1 && kl(WB) == 1 && kl(YC) == 1 && kl(WC) == 1,
+                  "fq_dot6: normalized v-side digits");
+    constexpr long long S = (long long)kv(A) * (kv(YA) + kv(WA)) + (long long)kv(B) * (kv(YB) + kv(WB)) +
+                            (long long)kv(C) * (kv(YC) + kv(WC));
+    constexpr int BO = 1 + (int)(S * 5908 / 1000000 + 1);
+    static_assert(BO <= kMaxBound, "fq_dot6: the value must stay below 2^261");
+    static_assert(S > 54 || BO == 2, "fq_dot6: the sparse line product's contract leaves below 2 p");
+#if BN_DOT6_ASM && BN_DOT2_ASM && defined(__HIP_DEVICE_COMPILE__)
+    Fq<BO> r;
+    asm(BN_ASM_DOT6 : BN_ASM_OUT9(r.v)
+        : BN_ASM_IN9(a.v), BN_ASM_IN9(va.y.v), BN_ASM_IN9(pa.v), BN_ASM_IN9(va.w.v), BN_ASM_IN9(b.v),
+          BN_ASM_IN9(vb.y.v), BN_ASM_IN9(pb.v), BN_ASM_IN9(vb.w.v), BN_ASM_IN9(c.v), BN_ASM_IN9(vc.y.v),
+          BN_ASM_IN9(pc.v), BN_ASM_IN9(vc.w.v), BN_ASM_P
+        : BN_ASM_CLOBBER);
+    return r;
+#else
+    Acc t = {};
+    acc_mad(t, a, va.y);
+    acc_mad(t, pa, va.w);
+    acc_mad(t, b, vb.y);
+    acc_mad(t, pb, vb.w);
+    acc_mad(t, c, vc.y);
+    acc_mad(t, pc, vc.w);
+    return acc_redc<BO>(t);
+#endif
+}
+template <int A, int B, int C, int YA, int WA, int YB, int WB, int YC, int WC>
+BN_INLINE auto fq_dot6(const Fq<A>& a, const LineOpsT<YA, WA>& va, const Fq<B>& b, const LineOpsT<YB, WB>& vb,
+                       const Fq<C>& c, const LineOpsT<YC, WC>& vc) {
+    const Fq<A> pa = fq_partner(a);
+    const Fq<B> pb = fq_partner(b);
+    const Fq<C> pc = fq_partner(c);
+    return fq_dot6p(a, pa, va, b, pb, vb, c, pc, vc);
+}
+
+// BN_FQ6_LAZY (bit 1: fq12_mul, bit 2: fq12_sqr): the Fq6 products of the Karatsuba
+// Fq12 product and square as schoolbook column sums, fq6.rs:197-207 with xi moved
+// onto the a side,
+//   c0 = a0 b0 + (xi a1) b2 + (xi a2) b1
+//   c1 = a0 b1 +     a1  b0 + (xi a2) b2
+//   c2 = a0 b2 +     a1  b1 +     a2  b0,
+// each one fq_dot6 chain: 54 digit products instead of Karatsuba's 36, but no operand
+// sums, recombination passes, xi passes on results or folds: the Fq12 product 7,541 ->
+// 6,862 VALU, the square 5,235 -> 4,819.  Off unless the including unit turns it on;
+// each unit decides by measurement (kernels_pairing.hip runs it).
+#ifndef BN_FQ6_LAZY
+#define BN_FQ6_LAZY 0
+#endif
+// the a side: normalized coordinates, their partners, and xi a1, xi a2 with partners
+template <int U>
+struct Fq6U {
+    static constexpr int kG = 10 * kv(U) + 1;
+    Fq<U> u0, u1, u2, p0, p1, p2;
+    Fq<kG> g1, g2, q1, q2;
+};
+// xi * u for this lane, normalized: 9 * own + (lane 0: K*p - u1, lane 1: u0) as one
+// carry chain (9 * own overflows a 32-bit digit); value <= (10 U + 1) p
+template <int U>
+BN_INLINE Fq<10 * kv(U) + 1> fq_xi_lin(const Fq<U>& own, const Fq<U>& par) {
+    static_assert(kl(U) == 1, "fq_xi_lin: normalized");
+    return fq_lin<9, 1>(own, fq_pick(lane_odd(), par, fq_neg_lazy(par)));
+}
+constexpr int kLazyIn = 4;  // operands enter at value <= 4 p (a sum of two stored values) or folded
+template <int A>
+BN_INLINE auto fq6_lazy_u(const Fq6<A>& a_in) {
+    const auto a = fq6_norm(pre<kLazyIn>(a_in));
+    constexpr int U = decltype(a.c0.c)::kK;
+    Fq6U<U> r;
+    r.u0 = a.c0.c, r.u1 = a.c1.c, r.u2 = a.c2.c;
+    r.p0 = fq_partner(r.u0), r.p1 = fq_partner(r.u1), r.p2 = fq_partner(r.u2);
+    r.g1 = fq_xi_lin(r.u1, r.p1), r.g2 = fq_xi_lin(r.u2, r.p2);
+    r.q1 = fq_partner(r.g1), r.q2 = fq_partner(r.g2);
+    return r;
+}
+template <int U, int Y0, int W0, int Y1, int W1, int Y2, int W2>
+BN_INLINE auto fq6_mul_uv(const Fq6U<U>& a, const LineOpsT<Y0, W0>& v0, const LineOpsT<Y1, W1>& v1,
+                          const LineOpsT<Y2, W2>& v2) {
+    const auto c2 = fq_dot6p(a.u0, a.p0, v2, a.u1, a.p1, v1, a.u2, a.p2, v0);
+    const auto c1 = fq_dot6p(a.u0, a.p0, v1, a.u1, a.p1, v0, a.g2, a.q2, v2);
+    const auto c0 = fq_dot6p(a.u0, a.p0, v0, a.g1, a.q1, v2, a.g2, a.q2, v1);
+    return mk6(wrap2(c0), wrap2(c1), wrap2(c2));
+}
+template <int A, int B>
+BN_INLINE auto fq6_mul_lazy(const Fq6<A>& a, const Fq6<B>& b_in) {
+    const auto b = pre<kLazyIn>(b_in);
+    return fq6_mul_uv(fq6_lazy_u(a), line_ops_of(b.c0), line_ops_of(b.c1), line_ops_of(b.c2));
+}
+#endif  // BN_SPLIT
+
 // fq6.rs:163-177
 template <int A>
 BN_INLINE auto fq6_sqr(const Fq6<A>& a) {
@@ -738,9 +870,16 @@ BN_INLINE auto fq12_neg(const Fq12<B>& a) { return mk12(fq6_neg(a.c0), fq6_neg(a
 template <int A, int B>
 BN_INLINE auto fq12_mul(const Fq12<A>& a, const Fq12<B>& b) {
     if constexpr (kv(A) > 10 || kv(B) > 10) return fq12_mul(pre<10>(a), pre<10>(b)); else {
+#if BN_SPLIT && (BN_FQ6_LAZY & 1)
+    // the chains leave normalized and below 7 p: no fold before the recombination
+    auto aa = fq6_mul_lazy(a.c0, b.c0);
+    auto bb = fq6_mul_lazy(a.c1, b.c1);
+    auto t = fq6_mul_lazy(fq6_add(a.c0, a.c1), fq6_add(b.c0, b.c1));
+#else
     auto aa = fq6_fold(fq6_mul(a.c0, b.c0));
     auto bb = fq6_fold(fq6_mul(a.c1, b.c1));
     auto t = fq6_mul(fq6_add(a.c0, a.c1), fq6_add(b.c0, b.c1));
+#endif
     return mk12(fq6_add(fq6_mul_by_nonresidue(bb), aa), fq6_sub(fq6_sub(t, aa), bb));
     }
 }
@@ -748,8 +887,18 @@ BN_INLINE auto fq12_mul(const Fq12<A>& a, const Fq12<B>& b) {
 template <int A>
 BN_INLINE auto fq12_sqr(const Fq12<A>& a) {
     if constexpr (kv(A) > 2) return fq12_sqr(fq12_fold(a)); else {
+#if BN_SPLIT && (BN_FQ6_LAZY & 2)
+    // ab = a.c1 * a.c0 with a.c1 on the a side: its xi * a.c1.c2 is also the first
+    // coefficient of the other product's operand v * a.c1 + a.c0, which enters as the
+    // b side (a carry pass in line_ops_of, no fold)
+    const auto u1 = fq6_lazy_u(a.c1);
+    auto ab = fq6_mul_uv(u1, line_ops_of(a.c0.c0), line_ops_of(a.c0.c1), line_ops_of(a.c0.c2));
+    auto t = fq6_mul_uv(fq6_lazy_u(fq6_add(a.c0, a.c1)), line_ops_of(fq2_add(wrap2(u1.g2), a.c0.c0)),
+                        line_ops_of(fq2_add(a.c1.c0, a.c0.c1)), line_ops_of(fq2_add(a.c1.c1, a.c0.c2)));
+#else
     auto ab = fq6_fold(fq6_mul(a.c0, a.c1));
     auto t = fq6_mul(fq6_add(fq6_mul_by_nonresidue(a.c1), a.c0), fq6_add(a.c0, a.c1));
+#endif
     return mk12(fq6_sub(fq6_sub(t, ab), fq6_mul_by_nonresidue(ab)), fq6_add(ab, ab));
     }
 }

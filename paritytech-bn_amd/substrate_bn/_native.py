@@ -36,7 +36,7 @@ EXPORTS = [
     "bn_g1_from_compressed_many_dev", "bn_g2_from_compressed_many_dev", "bn_gt_pow_many", "bn_gt_pow_many_dev",
     "bn_ctx_create_multi", "bn_ctx_num_devices", "bn_ctx_device", "bn_shard_range", "bn_pairing_many_allgather_dev",
     "bn_pairing_batch_dev", "bn_miller_loop_batch_dev", "bn_set_fe_wide_max", "bn_g2_precompute_many",
-    "bn_set_latency_max", "bn_dev_status",
+    "bn_set_latency_max", "bn_dev_status", "bn_set_fq12_op_unit",
     "bn_g1_msm", "bn_g1_msm_dev", "bn_set_msm_window", "bn_set_msm_min", "bn_msm_reserve",
 ] + ["bn_%s_%s_many%s" % (g, op, dev) for g in ("g1", "g2") for op in ("add", "sub", "neg", "normalize", "eq")
      for dev in ("", "_dev")]
@@ -119,6 +119,7 @@ def load():
         "bn_miller_loop_batch_dev": ([vp, vp, vp, sz, vp, vp, vp], i),
         "bn_set_fe_wide_max": ([vp, sz], i),
         "bn_set_latency_max": ([vp, sz], i),
+        "bn_set_fq12_op_unit": ([vp, i], i),
         "bn_g2_precompute_many": ([vp, vp, sz, vp], i),
         "bn_dev_status": ([vp, vp], i),
         "bn_g1_msm": ([vp, vp, vp, sz, vp], i),
@@ -379,6 +380,10 @@ class Context:
     def set_fe_wide_max(self, n):
         """Batches of at most n elements use the 16-lane final exponentiation (latency path)."""
         self._check(self._L.bn_set_fe_wide_max(self._h, n))
+
+    def set_fq12_op_unit(self, unit):
+        """fq12_op_many's step machine: 0 = the final-exponentiation unit's, 1 = the throughput kernel's unit's."""
+        self._check(self._L.bn_set_fq12_op_unit(self._h, unit))
 
     def set_latency_max(self, n):
         """Latency-path batches of at most n pairs run the one-launch k_pairing_latency."""
