@@ -428,8 +428,62 @@ struct G2Proj {
     Fq2<kPt> x, y, z;
 };
 
+// BN_LINE_CHAIN (split layout only; a bit mask, 0 unless the including unit turns it on):
+// the line steps with differences of products as one column sum and sums of a product and
+// stored values on the addend columns (fq2_split.h, "line-step chains").  Every coordinate
+// of R and every coefficient keeps its residue mod p, so all outputs stay bit-identical.
+//   1 = doubling_step: e = (3 b') * c with the tripled constant (no 3c pass);
+//       s.x = (x y) * (b - g) -- b - g == (b - f) / 2, one halving fewer; s.y = g^2 - 3 e^2 as
+//       one two-product chain (one reduction, no tripling, subtraction or fold);
+//       -h = b + c - (y + z)^2 as one chain that serves ell_vw and, negated inside the
+//       product's operand forms, s.z = b * h;
+//   2 = mixed_addition_step: d, e through the addend columns from the negated base, built
+//       once per base; ny = e (i - j) - h y and the sum inside l0 as four-product chains;
+//   8 = miller_fused (pairing.h) starts from the first line instead of one^2 * line.
+#ifndef BN_LINE_CHAIN
+#define BN_LINE_CHAIN 0
+#endif
+#if !BN_SPLIT
+#undef BN_LINE_CHAIN
+#define BN_LINE_CHAIN 0
+#endif
+#if BN_LINE_CHAIN & 1
+constexpr Limbs9 limbs_times(const Limbs9& a, unsigned m) {
+    Limbs9 r = {{0, 0, 0, 0, 0, 0, 0, 0, 0}};
+    unsigned long long c = 0;
+    for (int i = 0; i < 9; ++i) {
+        const unsigned long long t = (unsigned long long)a.v[i] * m + c;
+        r.v[i] = i < 8 ? (uint32_t)(t & M29) : (uint32_t)t;
+        c = t >> 29;
+    }
+    return r;
+}
+// 3 * b' as the integer 3 * (the constant's digits): value below 3 p
+BN_INLINE Fq2<3> g2_coeff_3b() {
+    constexpr Limbs9 c0 = limbs_times(Limbs9{BN_G2B_C0}, 3), c1 = limbs_times(Limbs9{BN_G2B_C1}, 3);
+    return {fq_select(lane_odd(), fq_from_limbs<3>(c1), fq_from_limbs<3>(c0))};
+}
+#endif
+
 // mod.rs:754-776 -- the twist() * i product is xi * i (ring identity)
 BN_INLINE Ell doubling_step(G2Proj& s) {
+#if BN_LINE_CHAIN & 1
+    {
+        auto xy = fq2_mul(s.x, s.y);
+        auto b = fq2_sqr(s.y);
+        auto c = fq2_sqr(s.z);
+        auto e = fq2_mul(g2_coeff_3b(), c);
+        auto f = fq2_add(fq2_add(e, e), e);
+        auto g = fq2_half(fq2_add(b, f));
+        auto nh = fq2_nsqr_add(fq2_add(s.y, s.z), b, c);
+        auto i = fq2_sub(e, b);
+        auto j = fq2_sqr(s.x);
+        s.x = narrow<kPt>(fq2_mul(xy, fq2_sub(b, g)));
+        s.y = narrow<kPt>(fq2_sqr_sub_msqr<3>(g, e));
+        s.z = narrow<kPt>(fq2_mul_negb(fq2_norm(b), nh));
+        return {narrow<kLine>(fq2_mul_xi(i)), narrow<kLine>(nh), narrow<kLine>(fq2_add(fq2_add(j, j), j))};
+    }
+#endif
     // x * two_inv is the halving x / 2 mod p: the same residue, no product
     auto a = fq2_half(fq2_mul(s.x, s.y));
     auto b = fq2_sqr(s.y);
@@ -466,6 +520,54 @@ BN_INLINE Ell mixed_addition_step(G2Proj& s, const G2Aff<BB>& base) {
     auto l0 = fq2_mul_xi(fq2_sub(fq2_mul(e, base.x), fq2_mul(d, base.y)));
     return {narrow<kLine>(l0), narrow<kLine>(d), narrow<kLine>(fq2_neg(e))};
 }
+// The base of an addition step with both signs of y, built once per base: bx = x, or -x
+// with BN_LINE_CHAIN & 2 (the form the chains take it in).
+template <int B>
+struct G2Base {
+    Fq2<B> bx, y, ny;
+};
+template <int B>
+BN_INLINE G2Base<B> g2_base(const G2Aff<B>& q) {
+    static_assert(kl(B) == 1, "g2_base: normalized base");
+#if BN_LINE_CHAIN & 2
+    return {widen<B>(fq2_neg(q.x)), q.y, widen<B>(fq2_neg(q.y))};
+#else
+    return {q.x, q.y, widen<B>(fq2_neg(q.y))};
+#endif
+}
+// the base or its negative (wave-uniform `minus`)
+template <int B>
+BN_INLINE G2Base<B> g2_base_signed(const G2Base<B>& b, bool minus) {
+    return {b.bx, fq2_select(minus, b.ny, b.y), fq2_select(minus, b.y, b.ny)};
+}
+#if BN_LINE_CHAIN & 2
+// the same step from d = x + z * (-bx) and -e = z * by - y (its square is e's): j = z g + h - 2 i
+// with h and K*p - i as addends, ny = (-e) (j - i) - h y and the sum inside
+// l0 = xi * ((-e) (-bx) + d (-by)) as four-product chains; ell_vv = -e is a chain's output
+template <int BB>
+BN_INLINE Ell mixed_addition_step(G2Proj& s, const G2Base<BB>& base) {
+    const Fq2<kLine> d = narrow<kLine>(fq2_mul_add<1>(s.z, base.bx, s.x));
+    const Fq2<kLine> ne = narrow<kLine>(fq2_mul_add<1>(s.z, base.y, wrap2(fq_neg_lazy(s.y.c))));
+    auto f = fq2_sqr(d);
+    auto g = fq2_sqr(ne);
+    auto h = fq2_mul(d, f);
+    auto i = fq2_mul(s.x, f);
+    auto j = fq2_mul_add<1, 2>(s.z, g, h, wrap2(fq_neg_lazy(i.c)));
+    auto nx = fq2_mul(d, j);
+    auto ny = fq2_dot_pm(ne, fq2_norm(fq2_sub(j, i)), h, s.y);
+    auto nz = fq2_mul(s.z, h);
+    s.x = narrow<kPt>(nx);
+    s.y = narrow<kPt>(ny);
+    s.z = narrow<kPt>(nz);
+    auto l0 = fq2_mul_xi(fq2_dot_pp(ne, base.bx, d, base.ny));
+    return {narrow<kLine>(l0), d, ne};
+}
+#else
+template <int BB>
+BN_INLINE Ell mixed_addition_step(G2Proj& s, const G2Base<BB>& base) {
+    return mixed_addition_step(s, G2Aff<BB>{base.bx, base.y});
+}
+#endif
 // mod.rs:694-699
 template <int B>
 BN_INLINE G2Aff<kPt> mul_by_q(const G2Aff<B>& q) {

@@ -315,6 +315,151 @@ BN_INLINE auto fq_dot2_add(const Fq<X>& x, const Fq<Y>& y, const Fq<Z>& z, const
     return fq_dot2_addn<3, K0, K1, K2>(x, y, z, w, c0, c1, c2);
 }
 
+// The same for one product (dot2_asm.inc MULA1..3): r = REDC(x*y) + sum K_j * c_j, the
+// fq_mul chain with the addends' digits on columns 9..17.  Column budget: 9 digit
+// products < Lx*Ly * 2^58 and 9 m*p terms < 2^58 (at most 63 * 2^58 with Lx*Ly <= 6), the
+// carry and the addend digits below 2^50.
+template <int NA, int K0, int K1, int K2, int X, int Y, int C0, int C1, int C2>
+BN_INLINE auto fq_mul_addn(const Fq<X>& x, const Fq<Y>& y, const Fq<C0>& c0, const Fq<C1>& c1, const Fq<C2>& c2) {
+    static_assert(NA >= 1 && NA <= 3 && K0 >= 1 && (NA > 1 ? K1 >= 1 : K1 == 0) && (NA > 2 ? K2 >= 1 : K2 == 0),
+                  "fq_mul_add: multipliers of the addends in use");
+    static_assert(K0 <= 64 && K1 <= 64 && K2 <= 64, "fq_mul_add: a multiplier must be an inline constant");
+    static_assert(kl(X) * kl(Y) <= 6, "fq_mul_add: column sum could overflow 64 bits");
+    static_assert((long long)K0 * kl(C0) + (long long)K1 * kl(C1) + (long long)K2 * kl(C2) <= (1 << 20),
+                  "fq_mul_add: column sum could overflow 64 bits");
+    constexpr int BO = mul_bound(kv(X), kv(Y)) + K0 * kv(C0) + K1 * kv(C1) + K2 * kv(C2);
+    static_assert(BO <= kMaxBound, "fq_mul_add: the value must stay below 2^261");
+    Fq<BO> r;
+#if BN_DOT2_ASM && defined(__HIP_DEVICE_COMPILE__)
+    if constexpr ((BN_DOT2_ASM & 2) != 0) {
+        if constexpr (NA == 1) {
+            asm(BN_ASM_MULA1 : BN_ASM_OUT9(r.v) : BN_ASM_IN9(x.v), BN_ASM_IN9(y.v), BN_ASM_IN9(c0.v), BN_ASM_P, "n"(K0)
+                : BN_ASM_CLOBBER);
+        } else if constexpr (NA == 2) {
+            asm(BN_ASM_MULA2 : BN_ASM_OUT9(r.v)
+                : BN_ASM_IN9(x.v), BN_ASM_IN9(y.v), BN_ASM_IN9(c0.v), BN_ASM_IN9(c1.v), BN_ASM_P, "n"(K0), "n"(K1)
+                : BN_ASM_CLOBBER);
+        } else {
+            asm(BN_ASM_MULA3 : BN_ASM_OUT9(r.v)
+                : BN_ASM_IN9(x.v), BN_ASM_IN9(y.v), BN_ASM_IN9(c0.v), BN_ASM_IN9(c1.v), BN_ASM_IN9(c2.v), BN_ASM_P,
+                  "n"(K0), "n"(K1), "n"(K2)
+                : BN_ASM_CLOBBER);
+        }
+        return r;
+    }
+#endif
+    uint32_t m[9];
+    uint64_t acc = 0;
+#pragma unroll
+    for (int k = 0; k < 18; ++k) {
+        const int lo = k < 9 ? 0 : k - 8;
+        const int hi = k < 9 ? k : 8;
+#pragma unroll
+        for (int i = lo; i <= hi; ++i) acc += (uint64_t)x.v[i] * y.v[k - i];
+#pragma unroll
+        for (int i = lo; i <= hi; ++i)
+            if (i < k) acc += (uint64_t)m[i] * kP29.v[k - i];
+        if (k < 9) {
+            m[k] = ((uint32_t)acc * BN_PINV29) & M29;
+            acc += (uint64_t)m[k] * kP29.v[0];
+        } else {
+            acc += (uint64_t)c0.v[k - 9] * K0;
+            if constexpr (NA > 1) acc += (uint64_t)c1.v[k - 9] * K1;
+            if constexpr (NA > 2) acc += (uint64_t)c2.v[k - 9] * K2;
+            r.v[k - 9] = k < 17 ? (uint32_t)acc & M29 : (uint32_t)acc;
+        }
+        acc >>= 29;
+    }
+    return r;
+}
+template <int K0, int X, int Y, int C0>
+BN_INLINE auto fq_mul_add(const Fq<X>& x, const Fq<Y>& y, const Fq<C0>& c0) {
+    return fq_mul_addn<1, K0, 0, 0>(x, y, c0, c0, c0);
+}
+template <int K0, int K1, int X, int Y, int C0, int C1>
+BN_INLINE auto fq_mul_add(const Fq<X>& x, const Fq<Y>& y, const Fq<C0>& c0, const Fq<C1>& c1) {
+    return fq_mul_addn<2, K0, K1, 0>(x, y, c0, c1, c1);
+}
+template <int K0, int K1, int K2, int X, int Y, int C0, int C1, int C2>
+BN_INLINE auto fq_mul_add(const Fq<X>& x, const Fq<Y>& y, const Fq<C0>& c0, const Fq<C1>& c1, const Fq<C2>& c2) {
+    return fq_mul_addn<3, K0, K1, K2>(x, y, c0, c1, c2);
+}
+
+// REDC(x0*y0 + x1*y1 + x2*y2 + x3*y3) [+ K0*c0 [+ K1*c1]]: one Montgomery reduction of a
+// four-product column sum (dot2_asm.inc DOT4, DOT4A1, DOT4A2) -- two Fq2 products' worth of
+// this lane's coordinate.  A column holds at most 9 * sum(Lx_t * Ly_t) digit products and
+// 9 m*p terms below 2^58 each: under 2^64 while the sum is <= 6, as for fq_dot2.
+template <int NA, int K0, int K1, int X0, int Y0, int X1, int Y1, int X2, int Y2, int X3, int Y3, int C0, int C1>
+BN_INLINE auto fq_dot4_addn(const Fq<X0>& x0, const Fq<Y0>& y0, const Fq<X1>& x1, const Fq<Y1>& y1, const Fq<X2>& x2,
+                            const Fq<Y2>& y2, const Fq<X3>& x3, const Fq<Y3>& y3, const Fq<C0>& c0, const Fq<C1>& c1) {
+    static_assert(NA >= 0 && NA <= 2 && (NA > 0 ? K0 >= 1 : K0 == 0) && (NA > 1 ? K1 >= 1 : K1 == 0),
+                  "fq_dot4: multipliers of the addends in use");
+    static_assert(K0 <= 64 && K1 <= 64, "fq_dot4: a multiplier must be an inline constant");
+    static_assert(kl(X0) * kl(Y0) + kl(X1) * kl(Y1) + kl(X2) * kl(Y2) + kl(X3) * kl(Y3) <= 6,
+                  "fq_dot4: column sum could overflow 64 bits");
+    static_assert((long long)K0 * kl(C0) + (long long)K1 * kl(C1) <= (1 << 20),
+                  "fq_dot4: column sum could overflow 64 bits");
+    constexpr long long S = (long long)kv(X0) * kv(Y0) + (long long)kv(X1) * kv(Y1) + (long long)kv(X2) * kv(Y2) +
+                            (long long)kv(X3) * kv(Y3);
+    constexpr int BO = 1 + (int)(S * 5908 / 1000000 + 1) + K0 * kv(C0) + K1 * kv(C1);
+    static_assert(BO <= kMaxBound, "fq_dot4: the value must stay below 2^261");
+    Fq<BO> r;
+#if BN_DOT2_ASM && defined(__HIP_DEVICE_COMPILE__)
+    if constexpr ((BN_DOT2_ASM & 1) != 0) {
+        if constexpr (NA == 0) {
+            asm(BN_ASM_DOT4 : BN_ASM_OUT9(r.v)
+                : BN_ASM_IN9(x0.v), BN_ASM_IN9(y0.v), BN_ASM_IN9(x1.v), BN_ASM_IN9(y1.v), BN_ASM_IN9(x2.v),
+                  BN_ASM_IN9(y2.v), BN_ASM_IN9(x3.v), BN_ASM_IN9(y3.v), BN_ASM_P
+                : BN_ASM_CLOBBER);
+        } else if constexpr (NA == 1) {
+            asm(BN_ASM_DOT4A1 : BN_ASM_OUT9(r.v)
+                : BN_ASM_IN9(x0.v), BN_ASM_IN9(y0.v), BN_ASM_IN9(x1.v), BN_ASM_IN9(y1.v), BN_ASM_IN9(x2.v),
+                  BN_ASM_IN9(y2.v), BN_ASM_IN9(x3.v), BN_ASM_IN9(y3.v), BN_ASM_IN9(c0.v), BN_ASM_P, "n"(K0)
+                : BN_ASM_CLOBBER);
+        } else {
+            asm(BN_ASM_DOT4A2 : BN_ASM_OUT9(r.v)
+                : BN_ASM_IN9(x0.v), BN_ASM_IN9(y0.v), BN_ASM_IN9(x1.v), BN_ASM_IN9(y1.v), BN_ASM_IN9(x2.v),
+                  BN_ASM_IN9(y2.v), BN_ASM_IN9(x3.v), BN_ASM_IN9(y3.v), BN_ASM_IN9(c0.v), BN_ASM_IN9(c1.v), BN_ASM_P,
+                  "n"(K0), "n"(K1)
+                : BN_ASM_CLOBBER);
+        }
+        return r;
+    }
+#endif
+    uint32_t m[9];
+    uint64_t acc = 0;
+#pragma unroll
+    for (int k = 0; k < 18; ++k) {
+        const int lo = k < 9 ? 0 : k - 8;
+        const int hi = k < 9 ? k : 8;
+#pragma unroll
+        for (int i = lo; i <= hi; ++i) {
+            acc += (uint64_t)x0.v[i] * y0.v[k - i];
+            acc += (uint64_t)x1.v[i] * y1.v[k - i];
+            acc += (uint64_t)x2.v[i] * y2.v[k - i];
+            acc += (uint64_t)x3.v[i] * y3.v[k - i];
+        }
+#pragma unroll
+        for (int i = lo; i <= hi; ++i)
+            if (i < k) acc += (uint64_t)m[i] * kP29.v[k - i];
+        if (k < 9) {
+            m[k] = ((uint32_t)acc * BN_PINV29) & M29;
+            acc += (uint64_t)m[k] * kP29.v[0];
+        } else {
+            if constexpr (NA > 0) acc += (uint64_t)c0.v[k - 9] * K0;
+            if constexpr (NA > 1) acc += (uint64_t)c1.v[k - 9] * K1;
+            r.v[k - 9] = k < 17 ? (uint32_t)acc & M29 : (uint32_t)acc;
+        }
+        acc >>= 29;
+    }
+    return r;
+}
+template <int X0, int Y0, int X1, int Y1, int X2, int Y2, int X3, int Y3>
+BN_INLINE auto fq_dot4(const Fq<X0>& x0, const Fq<Y0>& y0, const Fq<X1>& x1, const Fq<Y1>& y1, const Fq<X2>& x2,
+                       const Fq<Y2>& y2, const Fq<X3>& x3, const Fq<Y3>& y3) {
+    return fq_dot4_addn<0, 0, 0>(x0, y0, x1, y1, x2, y2, x3, y3, x0, x0);
+}
+
 // K0*c0 + K1*c1 [+ K2*c2] with normalized digits: the addends without a product, as
 // one carry chain (dot2_asm.inc LIN2 / LIN3: per digit the carry shift, one
 // multiply-add per term and the 29-bit extract).  For combinations whose multiples
@@ -495,6 +640,115 @@ BN_INLINE auto fq2_sqr(const Fq2<A>& a_in) {
     return r;
     }
 }
+// ---------------------------------------------------------------- line-step chains
+// The forms curve.h's doubling_step and mixed_addition_step run on with BN_LINE_CHAIN:
+// differences of products as one column sum with one reduction, and sums of a product and
+// stored values through the addend columns.  Each computes the residue of the formula in
+// its comment; the integer (a multiple of p apart) and its bound are the chain's.
+//
+// g^2 - M * e^2 (the doubling step's g^2 - 3 e^2), both squares in fq2_sqr's one-product
+// form in ONE column sum:
+//   lane 0: (g0 - g1) * (g0 + g1) + (K*p + e1 - e0) * M (e0 + e1)
+//   lane 1:  g1 * (g0 + g0)       + (K*p - e1)      * M (e0 + e0)
+// The sums y and w are carried (digit bound 1) so that the differences x and z enter with
+// fq_sub's digits below 3 * 2^29: column budget 3 + 3.
+template <int M, int G, int E>
+BN_INLINE auto fq2_sqr_sub_msqr(const Fq2<G>& g_in, const Fq2<E>& e_in) {
+    const bool odd = lane_odd();
+    const Fq<kv(G)> g = fq_norm(g_in.c), pg = fq_partner(g);
+    const Fq<kv(E)> e = fq_norm(e_in.c), pe = fq_partner(e);
+    const auto x = fq_pick(odd, g, fq_sub(g, pg));
+    const auto y = fq_norm(fq_add(pg, fq_select(odd, pg, g)));
+    const auto z = fq_pick(odd, fq_neg_lazy(e), fq_sub(pe, e));
+    const auto w = fq_norm(fq_mul_small<M>(fq_add(pe, fq_select(odd, pe, e))));
+    return wrap2(fq_dot2(x, y, z, w));
+}
+// b + c - a^2, normalized: fq2_sqr's product with its first operand negated (lane 0:
+// K*p + a1 - a0, lane 1: K*p - a1) and b, c on the addend columns
+template <int A, int B, int C>
+BN_INLINE auto fq2_nsqr_add(const Fq2<A>& a_in, const Fq2<B>& b, const Fq2<C>& c) {
+    const bool odd = lane_odd();
+    const Fq<kv(A)> own = fq_norm(a_in.c), par = fq_partner(own);
+    const auto x = fq_pick(odd, fq_neg_lazy(own), fq_sub(par, own));
+    const auto y = fq_add(par, fq_select(odd, par, own));
+    return wrap2(fq_mul_add<1, 1>(x, y, fq_norm(b.c), fq_norm(c.c)));
+}
+// The second operand b of a two-lane product a * b in the forms the column sum takes it
+// in (fq2_mul_split's y and w): own(a) * y + partner(a) * w.
+template <int Y, int W>
+struct SplitOps {
+    Fq<Y> y;  // b0 on both lanes
+    Fq<W> w;  // lane 0: K*p - b1, lane 1: b1
+};
+// w from this lane's coordinate `own` and the value `neg` whose partner copy the even lane takes
+template <int O, int N>
+BN_INLINE Fq<kjoin(O, N)> split_w(const Fq<O>& own, const Fq<N>& neg) {
+    Fq<kjoin(O, N)> w;
+#if defined(__HIP_DEVICE_COMPILE__)
+    dpp_sel_own_partner(w.v, own.v, neg.v);
+#else
+    w = fq_pick(lane_odd(), own, fq_partner(neg));
+#endif
+    return w;
+}
+// the forms of +b (NW: w carried to digit bound 1, for a sum with no column budget left)
+template <bool NW = false, int B>
+BN_INLINE auto split_ops(const Fq2<B>& b) {
+    static_assert(kl(B) == 1, "split_ops: normalized operand");
+    const auto w = split_w(b.c, fq_neg_lazy(b.c));
+    if constexpr (NW) {
+        return SplitOps<B, kv(decltype(w)::kK)>{fq_bcast_c0(b.c), fq_norm(w)};
+    } else {
+        return SplitOps<B, decltype(w)::kK>{fq_bcast_c0(b.c), w};
+    }
+}
+// the forms of -b from b: y = K*p - b0, w = lane 0: b1, lane 1: K*p - b1 -- the same
+// operand work as for +b
+template <int B>
+BN_INLINE auto split_ops_neg(const Fq2<B>& b) {
+    static_assert(kl(B) == 1, "split_ops_neg: normalized operand");
+    const auto hb = fq_neg_lazy(b.c);  // this lane's coordinate of -b
+    const auto w = split_w(hb, b.c);
+    return SplitOps<decltype(hb)::kK, decltype(w)::kK>{fq_bcast_c0(hb), w};
+}
+// a * (-nb), the product by a value held as its negation nb
+template <int A, int NB>
+BN_INLINE auto fq2_mul_negb(const Fq2<A>& a, const Fq2<NB>& nb) {
+    static_assert(kl(A) == 1, "fq2_mul_negb: normalized operand");
+    const auto o = split_ops_neg(nb);
+    return wrap2(fq_dot2(a.c, o.y, fq_partner(a.c), o.w));
+}
+// a * b + K0 * c0 [+ K1 * c1] with the c_j on the addend columns (normalized result)
+template <int K0, int A, int B, int C0>
+BN_INLINE auto fq2_mul_add(const Fq2<A>& a, const Fq2<B>& b, const Fq2<C0>& c0) {
+    static_assert(kl(A) == 1, "fq2_mul_add: normalized operand");
+    const auto o = split_ops(b);
+    return wrap2(fq_dot2_add<K0>(a.c, o.y, fq_partner(a.c), o.w, c0.c));
+}
+template <int K0, int K1, int A, int B, int C0, int C1>
+BN_INLINE auto fq2_mul_add(const Fq2<A>& a, const Fq2<B>& b, const Fq2<C0>& c0, const Fq2<C1>& c1) {
+    static_assert(kl(A) == 1, "fq2_mul_add: normalized operand");
+    const auto o = split_ops(b);
+    return wrap2(fq_dot2_add<K0, K1>(a.c, o.y, fq_partner(a.c), o.w, c0.c, c1.c));
+}
+// a * b + c * d and a * b - c * d as one four-product column sum, reduced once.  In the
+// difference b's w is carried: the forms of -d take digit bound 2 on both sides
+// (column budget 1 + 1 + 2 + 2).
+template <int A, int B, int C, int D>
+BN_INLINE auto fq2_dot_pp(const Fq2<A>& a, const Fq2<B>& b, const Fq2<C>& c, const Fq2<D>& d) {
+    static_assert(kl(A) == 1 && kl(C) == 1, "fq2_dot_pp: normalized operands");
+    const auto ob = split_ops(b);
+    const auto od = split_ops(d);
+    return wrap2(fq_dot4(a.c, ob.y, fq_partner(a.c), ob.w, c.c, od.y, fq_partner(c.c), od.w));
+}
+template <int A, int B, int C, int D>
+BN_INLINE auto fq2_dot_pm(const Fq2<A>& a, const Fq2<B>& b, const Fq2<C>& c, const Fq2<D>& d) {
+    static_assert(kl(A) == 1 && kl(C) == 1, "fq2_dot_pm: normalized operands");
+    const auto ob = split_ops<true>(b);
+    const auto od = split_ops_neg(d);
+    return wrap2(fq_dot4(a.c, ob.y, fq_partner(a.c), ob.w, c.c, od.y, fq_partner(c.c), od.w));
+}
+
 // x * xi, xi = 9 + u (fq2.rs:19-34, 55-57): lane 0: 9a0 - a1, lane 1: 9a1 + a0.
 template <int A>
 BN_INLINE auto fq2_mul_xi(const Fq2<A>& a) {

@@ -28,6 +28,18 @@
 #define BN_CYC_LIN 0
 #endif
 #endif
+// The Miller loop's line steps on merged and addend-taking column chains (curve.h
+// BN_LINE_CHAIN; bit 1 the doubling step, 2 the addition step, 8 digit 0 of miller_fused
+// outside the loop): k_pairing_full 1,975,275 -> 1,951,264 weighted VALU per lane with 1 | 2
+// (the digit block 12,806 -> 12,566, the addition 9,021 -> 8,633), scratch 512 -> 528 B, 524 B
+// with all three.  Interleaved with the parent's build, every round of 1 | 2 is faster than
+// every round of the parent (-1.1 to -1.3 %) and every round of 1 | 2 | 8 faster than those
+// (-1.3 to -1.7 % against the parent); bit 1 alone is inside the parent's spread, bit 2 alone
+// -0.3 % (profiles/r9_ab_line_chains.txt).  Bit 4 of the plan (xi * f_k of the sparse line
+// product through fq_xi_lin) is not built: DESIGN.md 4.6.
+#ifndef BN_LINE_CHAIN
+#define BN_LINE_CHAIN 11
+#endif
 #include "fq.h"
 #define BN_SPLIT BN_PATH_SPLIT
 #include "kernels.h"

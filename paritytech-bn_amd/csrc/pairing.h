@@ -23,22 +23,20 @@ BN_INLINE Fq12<S> narrow12(const Fq12<B>& a) {
 template <int B, typename Emit>
 BN_INLINE void g2_precompute(const G2Aff<B>& q, Emit&& emit) {
     G2Proj r = {widen<kPt>(q.x), widen<kPt>(q.y), widen<kPt>(fq2_one())};
-    const G2Aff<B> q_neg = {q.x, fq2_neg(q.y)};
+    const G2Base<B> qb = g2_base(q);
     int k = 0;
 #pragma unroll 1
     for (int i = 0; i < BN_NAF_DIGITS; ++i) {
         emit(k++, doubling_step(r));
         if ((kNafNonzero >> i) & 1u) {  // uniform across the wave
-            const bool minus = (kNafMinus >> i) & 1u;
-            G2Aff<B> base = {q.x, fq2_select(minus, q_neg.y, q.y)};
-            emit(k++, mixed_addition_step(r, base));
+            emit(k++, mixed_addition_step(r, g2_base_signed(qb, (kNafMinus >> i) & 1u)));
         }
     }
     G2Aff<kPt> q1 = mul_by_q(q);
     G2Aff<kPt> q2 = mul_by_q(q1);
     q2.y = fq2_neg(q2.y);
-    emit(k++, mixed_addition_step(r, q1));
-    emit(k++, mixed_addition_step(r, q2));
+    emit(k++, mixed_addition_step(r, g2_base(q1)));
+    emit(k++, mixed_addition_step(r, g2_base(q2)));
 }
 
 #if BN_SPLIT
@@ -176,25 +174,36 @@ struct NoStep {
 template <int B, int PB, typename Step = NoStep>
 BN_INLINE Fq12<kF> miller_fused(const G2Aff<B>& q, const Fq<PB>& px, const Fq<PB>& py, Step&& step = Step{}) {
     G2Proj r = {widen<kPt>(q.x), widen<kPt>(q.y), widen<kPt>(fq2_one())};
-    const G2Aff<B> q_neg = {q.x, fq2_neg(q.y)};
+    const G2Base<B> qb = g2_base(q);
+#if BN_LINE_CHAIN & 8
+    // digit 0 outside the loop: f = one, so one^2 * line is the line itself
+    // (line_from_one), then the digit's addition (NAF digit 0 is +1).  As a branch inside
+    // the loop (below) this was slower; peeled, k_pairing_full is faster in every round
+    // (profiles/r9_ab_line_chains.txt, mask 11 against mask 3)
+    static_assert((kNafNonzero & 1u) != 0 && (kNafMinus & 1u) == 0, "miller_fused: digit 0 is +1");
+    step(0);
+    Fq12<kF> f = line_from_one(doubling_step(r), px, py);
+    f = apply_line(f, mixed_addition_step(r, g2_base_signed(qb, false)), px, py);
+    constexpr int kFirst = 1;
+#else
     Fq12<kF> f = widen<kF>(fq12_one());
+    constexpr int kFirst = 0;
+#endif
 #pragma unroll 1
-    for (int i = 0; i < BN_NAF_DIGITS; ++i) {
+    for (int i = kFirst; i < BN_NAF_DIGITS; ++i) {
         step(i);
         // (sqr_line's first-step shortcut here measured 5 % slower: 4.58 vs 4.35 ms,
         // a register-allocation change; it stays in the segment and coefficient loops)
         f = apply_line(narrow12<kF>(fq12_sqr(f)), doubling_step(r), px, py);
         if ((kNafNonzero >> i) & 1u) {
-            const bool minus = (kNafMinus >> i) & 1u;
-            G2Aff<B> base = {q.x, fq2_select(minus, q_neg.y, q.y)};
-            f = apply_line(f, mixed_addition_step(r, base), px, py);
+            f = apply_line(f, mixed_addition_step(r, g2_base_signed(qb, (kNafMinus >> i) & 1u)), px, py);
         }
     }
     G2Aff<kPt> q1 = mul_by_q(q);
     G2Aff<kPt> q2 = mul_by_q(q1);
     q2.y = fq2_neg(q2.y);
-    f = apply_line(f, mixed_addition_step(r, q1), px, py);
-    f = apply_line(f, mixed_addition_step(r, q2), px, py);
+    f = apply_line(f, mixed_addition_step(r, g2_base(q1)), px, py);
+    f = apply_line(f, mixed_addition_step(r, g2_base(q2)), px, py);
     return f;
 }
 

@@ -34,6 +34,17 @@ terms that would be digit-wise passes and a carry pass after the product cost on
 multiply-add per digit here and leave normalized.  Operands: r, x, y, z, w, c_0[,
 c_1[, c_2]] (v), p_0..p_8, -p^-1 (s), K_0[, K_1[, K_2]] (n).
 
+One-product kinds with addends ('mula1' .. 'mula3'): the mul chain with the same addend
+columns, r == REDC(x*y) + sum(K_j * c_j) (fq2_split.h fq_mul_add: a square whose result
+would be followed by additions or subtractions of stored values).  Operands: r, x, y,
+c_0[, c_1[, c_2]] (v), p_0..p_8, -p^-1 (s), K_0[, K_1[, K_2]] (n).
+
+Four-product kinds ('dot4', 'dot4a1', 'dot4a2'): REDC(x_0*y_0 + .. + x_3*y_3) [+ sum(K_j *
+c_j)], dot6's operand order with four products -- this lane's coordinate of a sum or
+difference of two Fq2 products with one reduction (fq2_split.h fq_dot4; the addition
+step of the Miller loop).  Operands: r, x_0, y_0, .., x_3, y_3[, c_0[, c_1]] (v), p, -p^-1
+(s)[, K_0[, K_1]] (n).
+
 Linear kinds ('lin2', 'lin3'): no product, only the addends -- the normalized digits
 of sum(K_j * c_j) as one carry chain (per digit: the carry shift, one multiply-add per
 term, the 29-bit extract), for a small-constant combination whose multiples would
@@ -47,14 +58,17 @@ ACC_LO = "v2"
 
 
 def gen(kind):
-    """kind: 'dot2' (x*y + z*w), 'dot6' (sum of six products, pairing.h's sparse line
-    product), 'mul' (x*y) or 'sqr' (x*x with doubled cross terms: d = 2x)"""
+    """kind: 'dot2' (x*y + z*w), 'dot4' / 'dot6' (sum of four / six products: the addition
+    step's merged products, pairing.h's sparse line product), 'mul' (x*y) or 'sqr' (x*x with
+    doubled cross terms: d = 2x); 'dot2a<n>', 'dot4a<n>', 'mula<n>': with n addend vectors"""
     if kind.startswith("lin"):
         return gen_lin(int(kind[3:]))
-    nadd = int(kind[5:]) if kind.startswith("dot2a") else 0  # addend vectors at weight R
-    if nadd:
-        kind = "dot2"
-    nin = {"dot2": 4, "dot6": 12, "mul": 2, "sqr": 2}[kind] + nadd
+    nadd = 0  # addend vectors at weight R
+    for base in ("dot2", "dot4", "mul"):
+        if kind.startswith(base + "a"):
+            kind, nadd = base, int(kind[len(base) + 1:])
+    nprod = {"dot2": 4, "dot4": 8, "dot6": 12, "mul": 2, "sqr": 2}[kind]
+    nin = nprod + nadd
     X = lambda i: "%%%d" % (9 + i)                    # noqa: E731
     Y = lambda j: "%%%d" % (18 + j)                   # noqa: E731 (sqr: the doubled digits d)
     Z = lambda i: "%%%d" % (27 + i)                   # noqa: E731
@@ -63,7 +77,7 @@ def gen(kind):
     P = lambda j: "%%%d" % (pbase + j)                # noqa: E731
     PINV = "%%%d" % (pbase + 9)
     M = lambda i: "%%%d" % i                          # noqa: E731
-    C = lambda t, d: "%%%d" % (45 + 9 * t + d)        # noqa: E731 (addend t, digit d)
+    C = lambda t, d: "%%%d" % (9 + 9 * nprod + 9 * t + d)  # noqa: E731 (addend t, digit d)
     KC = lambda t: "%%%d" % (pbase + 10 + t)          # noqa: E731 (its multiplier)
     out = []
     first = True
@@ -84,8 +98,8 @@ def gen(kind):
                     mad(X(i), Y(j))
                 elif i == j:
                     mad(X(i), X(i))
-            elif kind == "dot6":
-                for t in range(6):  # operands: x_t %(9 + 18t + i), y_t %(18 + 18t + j)
+            elif kind in ("dot4", "dot6"):
+                for t in range(nprod // 2):  # operands: x_t %(9 + 18t + i), y_t %(18 + 18t + j)
                     mad("%%%d" % (9 + 18 * t + i), "%%%d" % (18 + 18 * t + j))
             else:
                 mad(X(i), Y(j))
@@ -121,7 +135,8 @@ def gen_lin(n):
     return out
 
 
-KINDS = ("dot2", "mul", "sqr", "dot6", "dot2a1", "dot2a2", "dot2a3", "lin2", "lin3")
+KINDS = ("dot2", "mul", "sqr", "dot6", "dot2a1", "dot2a2", "dot2a3", "lin2", "lin3",
+         "mula1", "mula2", "mula3", "dot4", "dot4a1", "dot4a2")
 
 
 def main():
@@ -131,7 +146,8 @@ def main():
              "// column sums of fq_dot2 / fq_mul / fq_sqr (fq2_split.h, fq.h BN_DOT2_ASM) and of the",
              "// six-product sum of the sparse line product (pairing.h, BN_DOT6_ASM); DOT2A<n>: dot2",
              "// with n addend vectors at weight R, LIN<n>: the normalized sum of n small multiples",
-             "// (fq2_split.h fq_dot2_add, fq_lin; BN_DOT2_ADDEND).",
+             "// (fq2_split.h fq_dot2_add, fq_lin; BN_DOT2_ADDEND); MULA<n>: mul with n addend vectors,",
+             "// DOT4[A<n>]: the four-product sum (fq2_split.h fq_mul_add, fq_dot4; curve.h BN_LINE_CHAIN).",
              "#pragma once"]
     for kind in KINDS:
         ins = gen(kind)

@@ -9,7 +9,10 @@ additions, the final-exponentiation step program).  Blocks without an entry
 count once (setup, to_affine, the step-machine dispatch).  Output: per category
 the weighted instruction count per lane and its share of all VALU.
 
-    python tools/isa_weighted.py file.s KERNEL_SYMBOL SIG=WEIGHT[:NAME] ...
+    python tools/isa_weighted.py [--split-branches] file.s KERNEL_SYMBOL SIG=WEIGHT[:NAME] ...
+
+--split-branches ends a block at every branch, not only at labels: needed when a weighted
+block (the NAF addition) follows another (the Miller digit) without a label of its own.
 """
 import collections
 import sys
@@ -30,13 +33,15 @@ GROUPS = {
 
 
 def main():
-    path, sym = sys.argv[1], sys.argv[2]
+    argv = [a for a in sys.argv[1:] if a != "--split-branches"]
+    split = len(argv) != len(sys.argv) - 1
+    path, sym = argv[0], argv[1]
     table = {}
-    for a in sys.argv[3:]:
+    for a in argv[2:]:
         sig, rest = a.split("=")
         w, _, name = rest.partition(":")
         table[int(sig)] = (float(w), name or sig)
-    bl = blocks(path, sym)
+    bl = blocks(path, sym, split)
     tot = collections.Counter()
     seen = collections.Counter()
     per_op = {}
