@@ -297,7 +297,21 @@ void par_copy(void* dst, const void* src, size_t bytes) {
 // eight lanes per pair (k_prepare_wide, about a third of the step latency) while
 // the batch leaves the GPU underfilled, two lanes per pair (k_prepare) otherwise
 // (scale: 1 for the Miller-loop consumers, 0 for the coefficient export)
-static int prepare(bn_ctx* c, const bn_g1* d_p, const bn_g2* d_q, size_t m, int mode, hipStream_t s, int scale = 1) {
+// scaled_inputs: the caller ends in a final exponentiation and outputs nothing but Gt
+// (pairing_batch), so the producers may run on scaled coordinates (pairing.h
+// scaled_inputs: no to_affine inversion); lines and paff are then not the reference's
+static int prepare(bn_ctx* c, const bn_g1* d_p, const bn_g2* d_q, size_t m, int mode, hipStream_t s, int scale = 1,
+                   bool scaled_inputs = false) {
+    if (scaled_inputs && mode == 0 && scale == 1) {
+        if (m <= c->prepare_wide_max)
+            k_prepare_wide_scaled<<<grid_pair(kPrepareWideLanes * m), kPairBlock, 0, s>>>(d_p, d_q, m, c->coeffs,
+                                                                                         c->paff, c->flags);
+        else
+            k_prepare_scaled<<<grid_pair(kPathLanes * m), kPairBlock, 0, s>>>(d_p, d_q, m, c->coeffs, c->paff,
+                                                                              c->flags);
+        HIPCHK(c, hipGetLastError());
+        return BN_OK;
+    }
     if (m <= c->prepare_wide_max)
         k_prepare_wide<<<grid_pair(kPrepareWideLanes * m), kPairBlock, 0, s>>>(d_p, d_q, m, c->coeffs, c->paff,
                                                                               c->flags, c->d_err, mode, scale);
@@ -617,9 +631,10 @@ static SegPlan batch_plan_solve(size_t n) {
 // counts as one; mode 1: a zero point sets the BN_ERR_TO_AFFINE bit), each
 // segment reduced over the pairs into element g * nchunks + k (stride
 // S * nchunks) of `parts`
-int chunk_product(bn_ctx* c, const bn_g1* d_p, const bn_g2* d_q, size_t m, int mode, const SegPlan& plan,
+// do_fe: the product goes through the final exponentiation and only Gt leaves the call
+int chunk_product(bn_ctx* c, const bn_g1* d_p, const bn_g2* d_q, size_t m, int mode, int do_fe, const SegPlan& plan,
                   uint32_t* parts, size_t nchunks, size_t k, hipStream_t s) {
-    RET_IF(prepare(c, d_p, d_q, m, mode, s));
+    RET_IF(prepare(c, d_p, d_q, m, mode, s, 1, mode == 0 && do_fe));
     const SegPlan lay = plan_layout(plan, m, kPairBlock / kPathLanes);  // this chunk's lane pairs
     // k_miller_seg writes lay.total elements from region kRegionSeg to the end of the slots
     if ((size_t)lay.total > (size_t)(kFeSlots - kRegionSeg) * c->cap)
@@ -757,7 +772,7 @@ int miller_product_dev(bn_ctx* c, const bn_g1* d_p, const bn_g2* d_q, size_t n, 
     uint32_t* parts = parts_region(c, nchunks);
     for (size_t k = 0; k < nchunks; ++k) {
         const size_t off = k * kChunk, m = (n - off) < kChunk ? (n - off) : kChunk;
-        RET_IF(chunk_product(c, d_p + off, d_q + off, m, mode, plan, parts, nchunks, k, s));
+        RET_IF(chunk_product(c, d_p + off, d_q + off, m, mode, mode == 0, plan, parts, nchunks, k, s));
     }
     return finish_product(c, plan, nchunks, mode == 0, d_out, s);
 }
@@ -1296,7 +1311,7 @@ static int batch_host(bn_ctx* c, const bn_g1* p, const bn_g2* q, size_t n, int m
         bn_g2* dq = (bn_g2*)(dp + m);
         HIPCHK(c, hipMemcpyAsync(dp, p + off, m * sizeof(bn_g1), hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(dq, q + off, m * sizeof(bn_g2), hipMemcpyHostToDevice, c->stream));
-        RET_IF(chunk_product(c, dp, dq, m, mode, plan, parts, nchunks, k, c->stream));
+        RET_IF(chunk_product(c, dp, dq, m, mode, do_fe ? 1 : 0, plan, parts, nchunks, k, c->stream));
         if (k + 1 < nchunks) HIPCHK(c, hipStreamSynchronize(c->stream));  // the stage is reused
     }
     bn_gt* d = (bn_gt*)c->stage;  // the stage holds at least one Gt past the inputs

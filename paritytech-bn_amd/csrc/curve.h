@@ -465,14 +465,28 @@ BN_INLINE Fq2<3> g2_coeff_3b() {
 }
 #endif
 
-// mod.rs:754-776 -- the twist() * i product is xi * i (ring identity)
-BN_INLINE Ell doubling_step(G2Proj& s) {
+// The curve constant as doubling_step takes it: 3 b' (value below 3 p, normalized digits)
+// with BN_LINE_CHAIN & 1, b' otherwise.
+BN_INLINE auto doubling_coeff() {
+#if BN_LINE_CHAIN & 1
+    return g2_coeff_3b();
+#else
+    return g2_coeff_b();
+#endif
+}
+// mod.rs:754-776 -- the twist() * i product is xi * i (ring identity).  `coeff` is the
+// curve constant in doubling_coeff()'s form: the constant itself wherever the
+// coefficients are observable, or its per-pairing multiple lambda^6 b' on scaled inputs
+// (pairing.h scaled_inputs), at the same digit and value bound.
+template <int CB>
+BN_INLINE Ell doubling_step(G2Proj& s, const Fq2<CB>& coeff) {
 #if BN_LINE_CHAIN & 1
     {
+        static_assert(kl(CB) == 1 && kv(CB) <= 3, "doubling_step: 3 b' normalized, bound 3");
         auto xy = fq2_mul(s.x, s.y);
         auto b = fq2_sqr(s.y);
         auto c = fq2_sqr(s.z);
-        auto e = fq2_mul(g2_coeff_3b(), c);
+        auto e = fq2_mul(coeff, c);
         auto f = fq2_add(fq2_add(e, e), e);
         auto g = fq2_half(fq2_add(b, f));
         auto nh = fq2_nsqr_add(fq2_add(s.y, s.z), b, c);
@@ -489,7 +503,7 @@ BN_INLINE Ell doubling_step(G2Proj& s) {
     auto b = fq2_sqr(s.y);
     auto c = fq2_sqr(s.z);
     auto d = fq2_add(fq2_add(c, c), c);
-    auto e = fq2_mul(g2_coeff_b(), d);
+    auto e = fq2_mul(coeff, d);
     auto f = fq2_add(fq2_add(e, e), e);
     auto g = fq2_half(fq2_add(b, f));
     auto h = fq2_sub(fq2_sqr(fq2_add(s.y, s.z)), fq2_add(b, c));
@@ -501,6 +515,7 @@ BN_INLINE Ell doubling_step(G2Proj& s) {
     s.z = narrow<kPt>(fq2_mul(b, h));
     return {narrow<kLine>(fq2_mul_xi(i)), narrow<kLine>(fq2_neg(h)), narrow<kLine>(fq2_add(fq2_add(j, j), j))};
 }
+BN_INLINE Ell doubling_step(G2Proj& s) { return doubling_step(s, doubling_coeff()); }
 // mod.rs:731-752
 template <int BB>
 BN_INLINE Ell mixed_addition_step(G2Proj& s, const G2Aff<BB>& base) {

@@ -571,6 +571,18 @@ __global__ void __launch_bounds__(kPairBlock) k_prepare_wide(const bn_g1* __rest
                                                          size_t n, uint32_t* __restrict__ coeffs,
                                                          uint32_t* __restrict__ paff, uint8_t* __restrict__ flags,
                                                          int* __restrict__ err, int mode, int scale);
+// The two producers on scaled inputs (pairing.h scaled_inputs: no to_affine inversion,
+// the pair's own curve constant in the doubling steps), prescaled lines, zero points
+// flagged (mode 0).  The lines and paff they store are NOT the reference's: only for
+// consumers that end in a final exponentiation and output nothing but Gt.
+__global__ void __launch_bounds__(kPairBlock) k_prepare_scaled(const bn_g1* __restrict__ p, const bn_g2* __restrict__ q,
+                                                           size_t n, uint32_t* __restrict__ coeffs,
+                                                           uint32_t* __restrict__ paff, uint8_t* __restrict__ flags);
+__global__ void __launch_bounds__(kPairBlock) k_prepare_wide_scaled(const bn_g1* __restrict__ p,
+                                                                const bn_g2* __restrict__ q, size_t n,
+                                                                uint32_t* __restrict__ coeffs,
+                                                                uint32_t* __restrict__ paff,
+                                                                uint8_t* __restrict__ flags);
 __global__ void __launch_bounds__(kBlock) k_coeffs_store(const uint32_t* __restrict__ coeffs, size_t n,
                                                          bn_fq2* __restrict__ out);
 __global__ void __launch_bounds__(kPairBlock) k_pairing_fused(const bn_g1* __restrict__ p, const bn_g2* __restrict__ q,

@@ -40,6 +40,12 @@
 #ifndef BN_LINE_CHAIN
 #define BN_LINE_CHAIN 11
 #endif
+// k_pairing_full and the line producers of the calls that end in a final exponentiation
+// run the Miller loop on scaled coordinates (pairing.h scaled_inputs) instead of affine
+// ones: no to_affine inversion, the same Gt.  0 builds them on pair_to_affine as before.
+#ifndef BN_SCALED_INPUTS
+#define BN_SCALED_INPUTS 1
+#endif
 #include "fq.h"
 #define BN_SPLIT BN_PATH_SPLIT
 #include "kernels.h"
@@ -49,22 +55,18 @@
 namespace bn {
 
 // to_affine + the 87 line coefficients (AffineG2::precompute) -> HBM.
-// Launched with kPairBlock threads per block (kernels.h: issue balance).
-__global__ void BN_PATH_ATTR __launch_bounds__(kPairBlock) k_prepare(const bn_g1* __restrict__ p,
-                                                                    const bn_g2* __restrict__ q, size_t n,
-                                                                    uint32_t* __restrict__ coeffs,
-                                                                    uint32_t* __restrict__ paff,
-                                                                    uint8_t* __restrict__ flags,
-                                                                    int* __restrict__ err, int mode, int scale) {
-    fold_table_init();
-    const Balance bal = balance_init();
-    const size_t l = lane_id(), i = l / kL, nl = kL * n;
-    if (i >= n) return;
-    const PairAffine a = pair_to_affine(p, q, i, l, flags, err, mode);
+// Scaled: the pair in scaled coordinates with its own curve constant (lines_wide.h
+// pair_scaled) -- only for consumers that end in a final exponentiation (mode 0).
+template <bool Scaled>
+__device__ __forceinline__ void prepare_pair(const bn_g1* __restrict__ p, const bn_g2* __restrict__ q, size_t n,
+                                             uint32_t* __restrict__ coeffs, uint32_t* __restrict__ paff,
+                                             uint8_t* __restrict__ flags, int* __restrict__ err, int mode, int scale,
+                                             const Balance& bal, size_t l, size_t i, size_t nl) {
+    const auto a = pair_inputs<Scaled>(p, q, i, l, flags, err, mode);
     st_fq(paff, nl, l, 0, a.px);
     st_fq(paff, nl, l, 1, a.py);
     const bool sc = BN_LINES_PRESCALED && scale;
-    g2_precompute(a.qa, [&](int k, const Ell& e) {
+    g2_precompute(a.qa, pair_coeff(a), [&](int k, const Ell& e) {
         balance_step(bal, (uint32_t)k);
         st_fq2(coeffs, nl, l, k * 6 + 0, e.ell_0);
         if (sc) {  // wave-uniform
@@ -76,24 +78,43 @@ __global__ void BN_PATH_ATTR __launch_bounds__(kPairBlock) k_prepare(const bn_g1
         }
     });
 }
-
-#if BN_SPLIT
 // Launched with kPairBlock threads per block (kernels.h: issue balance).
-__global__ void BN_PATH_ATTR __launch_bounds__(kPairBlock) k_prepare_wide(const bn_g1* __restrict__ p,
-                                                                         const bn_g2* __restrict__ q, size_t n,
-                                                                         uint32_t* __restrict__ coeffs,
-                                                                         uint32_t* __restrict__ paff,
-                                                                         uint8_t* __restrict__ flags,
-                                                                         int* __restrict__ err, int mode,
-                                                                         int scale) {
+__global__ void BN_PATH_ATTR __launch_bounds__(kPairBlock) k_prepare(const bn_g1* __restrict__ p,
+                                                                    const bn_g2* __restrict__ q, size_t n,
+                                                                    uint32_t* __restrict__ coeffs,
+                                                                    uint32_t* __restrict__ paff,
+                                                                    uint8_t* __restrict__ flags,
+                                                                    int* __restrict__ err, int mode, int scale) {
     fold_table_init();
     const Balance bal = balance_init();
-    const size_t l = lane_id(), i = l / kPW, nl = kL * n;
+    const size_t l = lane_id(), i = l / kL, nl = kL * n;
     if (i >= n) return;
+    prepare_pair<false>(p, q, n, coeffs, paff, flags, err, mode, scale, bal, l, i, nl);
+}
+// the same on scaled inputs, for pairing_batch (mode 0, prescaled lines: capi.hip prepare())
+__global__ void BN_PATH_ATTR __launch_bounds__(kPairBlock) k_prepare_scaled(const bn_g1* __restrict__ p,
+                                                                           const bn_g2* __restrict__ q, size_t n,
+                                                                           uint32_t* __restrict__ coeffs,
+                                                                           uint32_t* __restrict__ paff,
+                                                                           uint8_t* __restrict__ flags) {
+    fold_table_init();
+    const Balance bal = balance_init();
+    const size_t l = lane_id(), i = l / kL, nl = kL * n;
+    if (i >= n) return;
+    prepare_pair<BN_SCALED_INPUTS != 0>(p, q, n, coeffs, paff, flags, nullptr, 0, 1, bal, l, i, nl);
+}
+
+#if BN_SPLIT
+// the same on eight lanes per pair (lines_wide.h)
+template <bool Scaled>
+__device__ __forceinline__ void prepare_pair_wide(const bn_g1* __restrict__ p, const bn_g2* __restrict__ q, size_t n,
+                                                  uint32_t* __restrict__ coeffs, uint32_t* __restrict__ paff,
+                                                  uint8_t* __restrict__ flags, int* __restrict__ err, int mode,
+                                                  int scale, const Balance& bal, size_t l, size_t i, size_t nl) {
     const size_t lt = i * kL + (l & 1);  // this lane's index in k_prepare's per-pair arrays
     const int k = pw_slot();
     const bool st = k == 0;
-    const PairAffine a = pair_to_affine<true>(p, q, i, lt, flags, err, st ? mode : 0);
+    const auto a = pair_inputs<Scaled, true>(p, q, i, lt, flags, err, st ? mode : 0);
     if (st) {
         st_fq(paff, nl, lt, 0, a.px);
         st_fq(paff, nl, lt, 1, a.py);
@@ -123,10 +144,14 @@ __global__ void BN_PATH_ATTR __launch_bounds__(kPairBlock) k_prepare_wide(const 
     const Fq2<2> px_r = pw_real(a.px);
     const auto px3_r = pw_real(fq_add(fq_add(a.px, a.px), a.px));
     const auto bxpy_q = fq2_scale(qa.x, a.py);  // base x * Py of Q (and -Q)
+    // the doubling steps' constant: b', or the pair's own on scaled inputs
+    const auto bc = [&] {
+        if constexpr (Scaled) return a.coeff; else return g2_coeff_b();
+    }();
 #pragma unroll 1
     for (int d = 0; d < BN_NAF_DIGITS; ++d) {
         balance_step(bal, (uint32_t)d);
-        emit(c++, pw_doubling_step_p(r, k, py_r, px3_r));
+        emit(c++, pw_doubling_step_p<Scaled && kCoeffTripled>(r, k, py_r, px3_r, bc));
         if ((kNafNonzero >> d) & 1u) {
             const bool minus = (kNafMinus >> d) & 1u;
             const G2Aff<kPt> base = {qa.x, fq2_select(minus, widen<kPt>(qy_neg), qa.y)};
@@ -139,6 +164,7 @@ __global__ void BN_PATH_ATTR __launch_bounds__(kPairBlock) k_prepare_wide(const 
     emit(c++, pw_mixed_addition_step_p(r, q1, fq2_scale(q1.x, a.py), k, py_r, px_r));
     emit(c++, pw_mixed_addition_step_p(r, q2, fq2_scale(q2.x, a.py), k, py_r, px_r));
 #else
+    static_assert(!Scaled, "scaled inputs: only with BN_LINES_PRESCALED");
     (void)scale;
     auto emit = [&](int cc, const Ell& e) {
         if (st) {
@@ -163,6 +189,33 @@ __global__ void BN_PATH_ATTR __launch_bounds__(kPairBlock) k_prepare_wide(const 
     emit(c++, pw_mixed_addition_step(r, q1, k));
     emit(c++, pw_mixed_addition_step(r, q2, k));
 #endif
+}
+// Launched with kPairBlock threads per block (kernels.h: issue balance).
+__global__ void BN_PATH_ATTR __launch_bounds__(kPairBlock) k_prepare_wide(const bn_g1* __restrict__ p,
+                                                                         const bn_g2* __restrict__ q, size_t n,
+                                                                         uint32_t* __restrict__ coeffs,
+                                                                         uint32_t* __restrict__ paff,
+                                                                         uint8_t* __restrict__ flags,
+                                                                         int* __restrict__ err, int mode,
+                                                                         int scale) {
+    fold_table_init();
+    const Balance bal = balance_init();
+    const size_t l = lane_id(), i = l / kPW, nl = kL * n;
+    if (i >= n) return;
+    prepare_pair_wide<false>(p, q, n, coeffs, paff, flags, err, mode, scale, bal, l, i, nl);
+}
+// the same on scaled inputs, for pairing_batch (mode 0, prescaled lines: capi.hip prepare())
+__global__ void BN_PATH_ATTR __launch_bounds__(kPairBlock) k_prepare_wide_scaled(const bn_g1* __restrict__ p,
+                                                                                const bn_g2* __restrict__ q, size_t n,
+                                                                                uint32_t* __restrict__ coeffs,
+                                                                                uint32_t* __restrict__ paff,
+                                                                                uint8_t* __restrict__ flags) {
+    fold_table_init();
+    const Balance bal = balance_init();
+    const size_t l = lane_id(), i = l / kPW, nl = kL * n;
+    if (i >= n) return;
+    prepare_pair_wide<BN_SCALED_INPUTS != 0 && BN_LINES_PRESCALED>(p, q, n, coeffs, paff, flags, nullptr, 0, 1, bal, l, i,
+                                                                   nl);
 }
 #endif
 
@@ -229,8 +282,13 @@ __global__ void BN_PATH_ATTR __launch_bounds__(kPairBlock) k_pairing_full(const 
     const Balance bal = balance_init();
     const size_t l = lane_id(), i = l / kL, nl = kL * n;
     if (i >= n) return;
+#if BN_SCALED_INPUTS
+    const PairScaled a = pair_scaled(p, q, i, l, nullptr);
+    Fq12<kF> f = miller_fused(a.qa, a.px, a.py, a.coeff, [&](int d) { balance_step(bal, (uint32_t)d); });
+#else
     const PairAffine a = pair_to_affine(p, q, i, l, nullptr, err, 0);
     Fq12<kF> f = miller_fused(a.qa, a.px, a.py, [&](int d) { balance_step(bal, (uint32_t)d); });
+#endif
     if (a.skip) f = widen<kF>(fq12_one());
     // f == 0: the reference's final_exponentiation returns None and pairing()
     // panics (fq12.rs:63-72) -> zero Gt and the error bit, as k_fe_out

@@ -86,6 +86,59 @@ __device__ __forceinline__ PairAffine pair_to_affine(const bn_g1* __restrict__ p
     return a;
 }
 
+// The pair in scaled coordinates (pairing.h scaled_inputs) where pair_to_affine gives
+// affine ones: no inversion, for callers whose only output is Gt after a final
+// exponentiation (mode 0 only: a zero point sets `skip` and flags[lane], the pairing is
+// one and the values are never used).  `coeff` goes to the doubling steps in place of the
+// curve constant.
+struct PairScaled {
+    Fq<2> px, py;
+    G2Aff<kPt> qa;
+    G2Coeff coeff;
+    bool skip;
+};
+__device__ __forceinline__ PairScaled pair_scaled(const bn_g1* __restrict__ p, const bn_g2* __restrict__ q, size_t i,
+                                                  size_t l, uint8_t* __restrict__ flags) {
+    uint32_t w[8];
+    ld_words(&p[i].z, w);
+    const bool p_zero = words_zero(w);
+    const Fq<2> pz = fq_load_ref(w);
+#if BN_SPLIT
+    uint32_t wz[8];
+    ld_words(lane_odd() ? &q[i].z.c1 : &q[i].z.c0, wz);  // this lane's coordinate of z
+    const uint32_t own_zero = words_zero(wz) ? 1u : 0u;
+    const bool q_zero = (own_zero & swap_pair(own_zero)) != 0;
+    const Fq2<2> qz = {fq_load_ref(wz)};
+    const auto qz_sq = fq_sqr(qz.c);
+    const auto nq = fq_add(qz_sq, fq_partner(qz_sq));  // N(qz), the same on both lanes
+#else
+    uint32_t w0[8], w1[8];
+    ld_words(&q[i].z.c0, w0);
+    ld_words(&q[i].z.c1, w1);
+    const bool q_zero = words_zero(w0) && words_zero(w1);
+    const Fq2<2> qz = {fq_load_ref(w0), fq_load_ref(w1)};
+    const auto nq = fq_add(fq_sqr(qz.c0), fq_sqr(qz.c1));
+#endif
+    if (flags) flags[l] = (p_zero || q_zero) ? 1 : 0;
+    const ScaledPair s = scaled_inputs(ld_ref(p[i].x), ld_ref(p[i].y), pz, ld_ref2(q[i].x), ld_ref2(q[i].y), qz, nq);
+    return {s.px, s.py, s.qa, s.coeff, p_zero || q_zero};
+}
+// The pair as a line producer takes it, chosen at compile time: scaled for the calls
+// that end in a final exponentiation with Gt as their only output (mode 0), affine with
+// the exact curve constant wherever coefficients or Miller values are observable.
+template <bool Scaled, bool Quad = false>
+__device__ __forceinline__ auto pair_inputs(const bn_g1* __restrict__ p, const bn_g2* __restrict__ q, size_t i, size_t l,
+                                            uint8_t* __restrict__ flags, int* __restrict__ err, int mode) {
+    if constexpr (Scaled) {
+        return pair_scaled(p, q, i, l, flags);
+    } else {
+        return pair_to_affine<Quad>(p, q, i, l, flags, err, mode);
+    }
+}
+// the doubling steps' constant for the pair, as curve.h doubling_step takes it
+__device__ __forceinline__ auto pair_coeff(const PairAffine&) { return doubling_coeff(); }
+__device__ __forceinline__ G2Coeff pair_coeff(const PairScaled& a) { return a.coeff; }
+
 #if BN_SPLIT
 // ---------------------------------------------------------------- k_prepare_wide
 // The same to_affine + 87 line coefficients for small batches, on EIGHT lanes
@@ -209,16 +262,20 @@ __device__ __forceinline__ Fq2<B> pw_real(const Fq<B>& x) {
 // = 2 y z (the same field value), so y z joins layer 1 and x^2 moves to layer 2.
 // L1: x y, y^2, z^2, y z;  L2: e = b' * 3c, j = x^2, y z * Py, z' = y^2 * h;
 // L3: x' = a (b - f), g^2, e^2, j * 3Px
-template <int PY, int PX>
-__device__ __forceinline__ PwEll pw_doubling_step_p(G2Proj& s, int k, const Fq2<PY>& py_r, const Fq2<PX>& px3_r) {
+// `bc`: the curve constant b' (e = b' * 3c), or with Tripled its triple (e = 3b' * c) --
+// the form scaled inputs carry it in (pairing.h kCoeffTripled)
+template <bool Tripled, int PY, int PX, int CB>
+__device__ __forceinline__ PwEll pw_doubling_step_p(G2Proj& s, int k, const Fq2<PY>& py_r, const Fq2<PX>& px3_r,
+                                                    const Fq2<CB>& bc) {
     const auto l1 = pw_mul(k, s.x, s.y, s.y, s.y, s.z, s.z, s.y, s.z);  // x*y, y^2, z^2, y*z
     const auto a = fq2_half(pw_from(l1, 0));
     const auto b = pw_from(l1, 1);
     const auto c = pw_from(l1, 2);
     const auto yz = pw_from(l1, 3);
     const auto h = fq2_add(yz, yz);
-    const auto d = fq2_add(fq2_add(c, c), c);
-    const auto bc = g2_coeff_b();
+    const auto d = [&] {
+        if constexpr (Tripled) return c; else return fq2_add(fq2_add(c, c), c);
+    }();
     const auto l2 = pw_mul(k, bc, d, s.x, s.x, yz, py_r, b, h);  // e, j = x^2, yz * Py, z' = b * h
     const auto e = pw_from(l2, 0);
     const auto j = pw_from(l2, 1);
@@ -237,6 +294,10 @@ __device__ __forceinline__ PwEll pw_doubling_step_p(G2Proj& s, int k, const Fq2<
     r.vw_py = narrow<kLine>(fq2_neg(fq2_add(yzpy, yzpy)));  // -h Py
     r.vv_px = narrow<kLine>(l3);                             // slot 3: 3 j Px
     return r;
+}
+template <int PY, int PX>
+__device__ __forceinline__ PwEll pw_doubling_step_p(G2Proj& s, int k, const Fq2<PY>& py_r, const Fq2<PX>& px3_r) {
+    return pw_doubling_step_p<false>(s, k, py_r, px3_r, g2_coeff_b());
 }
 // mixed_addition_step (curve.h) in four layers with the P products:
 // L1: z bx, z by, x Py, z (bx Py)  (d Py = x Py - z bx Py);  L2: d^2, e^2, e bx, d by;

@@ -20,14 +20,16 @@ BN_INLINE Fq12<S> narrow12(const Fq12<B>& a) {
 
 // ---------------------------------------------------------------- G2 precomputation
 // AffineG2::precompute, mod.rs:701-727.  `emit(k, ell)` receives line k (0..86).
-template <int B, typename Emit>
-BN_INLINE void g2_precompute(const G2Aff<B>& q, Emit&& emit) {
+// `coeff`: the doubling step's curve constant (curve.h doubling_coeff(), or its
+// per-pairing multiple from scaled_inputs below)
+template <int B, int CB, typename Emit>
+BN_INLINE void g2_precompute(const G2Aff<B>& q, const Fq2<CB>& coeff, Emit&& emit) {
     G2Proj r = {widen<kPt>(q.x), widen<kPt>(q.y), widen<kPt>(fq2_one())};
     const G2Base<B> qb = g2_base(q);
     int k = 0;
 #pragma unroll 1
     for (int i = 0; i < BN_NAF_DIGITS; ++i) {
-        emit(k++, doubling_step(r));
+        emit(k++, doubling_step(r, coeff));
         if ((kNafNonzero >> i) & 1u) {  // uniform across the wave
             emit(k++, mixed_addition_step(r, g2_base_signed(qb, (kNafMinus >> i) & 1u)));
         }
@@ -37,6 +39,10 @@ BN_INLINE void g2_precompute(const G2Aff<B>& q, Emit&& emit) {
     q2.y = fq2_neg(q2.y);
     emit(k++, mixed_addition_step(r, g2_base(q1)));
     emit(k++, mixed_addition_step(r, g2_base(q2)));
+}
+template <int B, typename Emit>
+BN_INLINE void g2_precompute(const G2Aff<B>& q, Emit&& emit) {
+    g2_precompute(q, doubling_coeff(), static_cast<Emit&&>(emit));
 }
 
 #if BN_SPLIT
@@ -171,8 +177,11 @@ BN_INLINE Fq12<kF> miller_loop_scaled(Line&& line) {
 struct NoStep {
     BN_INLINE void operator()(int) const {}
 };
-template <int B, int PB, typename Step = NoStep>
-BN_INLINE Fq12<kF> miller_fused(const G2Aff<B>& q, const Fq<PB>& px, const Fq<PB>& py, Step&& step = Step{}) {
+// `coeff`: the doubling step's curve constant (curve.h doubling_coeff(), or its
+// per-pairing multiple from scaled_inputs below)
+template <int B, int PB, int CB, typename Step = NoStep>
+BN_INLINE Fq12<kF> miller_fused(const G2Aff<B>& q, const Fq<PB>& px, const Fq<PB>& py, const Fq2<CB>& coeff,
+                                Step&& step = Step{}) {
     G2Proj r = {widen<kPt>(q.x), widen<kPt>(q.y), widen<kPt>(fq2_one())};
     const G2Base<B> qb = g2_base(q);
 #if BN_LINE_CHAIN & 8
@@ -182,7 +191,7 @@ BN_INLINE Fq12<kF> miller_fused(const G2Aff<B>& q, const Fq<PB>& px, const Fq<PB
     // (profiles/r9_ab_line_chains.txt, mask 11 against mask 3)
     static_assert((kNafNonzero & 1u) != 0 && (kNafMinus & 1u) == 0, "miller_fused: digit 0 is +1");
     step(0);
-    Fq12<kF> f = line_from_one(doubling_step(r), px, py);
+    Fq12<kF> f = line_from_one(doubling_step(r, coeff), px, py);
     f = apply_line(f, mixed_addition_step(r, g2_base_signed(qb, false)), px, py);
     constexpr int kFirst = 1;
 #else
@@ -194,7 +203,7 @@ BN_INLINE Fq12<kF> miller_fused(const G2Aff<B>& q, const Fq<PB>& px, const Fq<PB
         step(i);
         // (sqr_line's first-step shortcut here measured 5 % slower: 4.58 vs 4.35 ms,
         // a register-allocation change; it stays in the segment and coefficient loops)
-        f = apply_line(narrow12<kF>(fq12_sqr(f)), doubling_step(r), px, py);
+        f = apply_line(narrow12<kF>(fq12_sqr(f)), doubling_step(r, coeff), px, py);
         if ((kNafNonzero >> i) & 1u) {
             f = apply_line(f, mixed_addition_step(r, g2_base_signed(qb, (kNafMinus >> i) & 1u)), px, py);
         }
@@ -206,6 +215,63 @@ BN_INLINE Fq12<kF> miller_fused(const G2Aff<B>& q, const Fq<PB>& px, const Fq<PB
     f = apply_line(f, mixed_addition_step(r, g2_base(q2)), px, py);
     return f;
 }
+template <int B, int PB, typename Step = NoStep>
+BN_INLINE Fq12<kF> miller_fused(const G2Aff<B>& q, const Fq<PB>& px, const Fq<PB>& py, Step&& step = Step{}) {
+    return miller_fused(q, px, py, doubling_coeff(), static_cast<Step&&>(step));
+}
+
+// ---------------------------------------------------------------- scaled inputs
+// Where only Gt leaves a pairing, the Miller loop can run on scaled coordinates instead
+// of affine ones, which takes to_affine's inversion away.  The line steps are
+// weighted-homogeneous: with x at weight 2, y at weight 3 and the twist constant b' at
+// weight 6, replacing (x_P, y_P, x_Q, y_Q, b') by (l^2 x_P, l^3 y_P, l^2 x_Q, l^3 y_Q,
+// l^6 b') for l in Fq* multiplies every coordinate of R and all three terms of every
+// line (ell_0, ell_vw * y_P, ell_vv * x_P) by a power of l -- in doubling_step, in
+// mixed_addition_step and through mul_by_q, whose constants carry no weight and whose
+// conjugation fixes l.  The Miller value changes by a power of l, an element of Fq*,
+// which the final exponentiation sends to one ((p - 1) divides (p^6 - 1)): the same Gt.
+// With l = N(Z_Q) Z_P, N = Z_Q.c0^2 + Z_Q.c1^2, nothing is inverted:
+//   l^2 X_P / Z_P^2 = N^2 X_P,  l^3 Y_P / Z_P^3 = N^3 Y_P,
+//   l / Z_Q = Z_P conj(Z_Q) = m:  l^2 X_Q / Z_Q^2 = m^2 X_Q,  l^3 Y_Q / Z_Q^3 = m^3 Y_Q.
+// A point at z == one takes the same formulas (they multiply by one).  A zero z makes
+// every output zero; the caller skips that pair and never uses the values.
+// `coeff` is l^6 times doubling_coeff(), at its bound: what doubling_step takes.
+constexpr bool kCoeffTripled = (BN_LINE_CHAIN & 1) != 0;  // coeff is l^6 * 3 b'
+constexpr int kCoeff = kCoeffTripled ? 3 : 2;
+using G2Coeff = Fq2<kCoeff>;
+struct ScaledPair {
+    Fq<2> px, py;
+    G2Aff<kPt> qa;
+    G2Coeff coeff;
+};
+// nq = N(qz) (the same value on both lanes of the split layout)
+template <int NB>
+BN_INLINE ScaledPair scaled_inputs(const Fq<2>& px, const Fq<2>& py, const Fq<2>& pz, const Fq2<2>& qx,
+                                   const Fq2<2>& qy, const Fq2<2>& qz, const Fq<NB>& nq) {
+    const auto n2 = fq_sqr(nq);
+    const auto l1 = fq_mul(nq, pz);
+    const auto l2 = fq_sqr(l1);
+    const auto l6 = fq_mul(l2, fq_sqr(l2));
+    ScaledPair a;
+    a.px = fq_mul(px, n2);
+    a.py = fq_mul(py, fq_mul(n2, nq));
+#if BN_SPLIT
+    const auto zp = fq_mul(qz.c, pz);
+    const auto m = wrap2(fq_select(lane_odd(), fq_neg(zp), zp));  // Z_P conj(Z_Q)
+#else
+    const auto m = mk2(fq_mul(qz.c0, pz), fq_neg(fq_mul(qz.c1, pz)));
+#endif
+    const auto m2 = fq2_sqr(m);
+    a.qa = {narrow<kPt>(fq2_mul(qx, m2)), narrow<kPt>(fq2_mul(qy, fq2_mul(m2, m)))};
+    a.coeff = widen<kCoeff>(fq2_scale(doubling_coeff(), l6));
+    return a;
+}
+#if !BN_SPLIT
+BN_INLINE ScaledPair scaled_inputs(const Fq<2>& px, const Fq<2>& py, const Fq<2>& pz, const Fq2<2>& qx,
+                                   const Fq2<2>& qy, const Fq2<2>& qz) {
+    return scaled_inputs(px, py, pz, qx, qy, qz, fq_add(fq_sqr(qz.c0), fq_sqr(qz.c1)));
+}
+#endif
 
 // One segment of the Miller loop: digits [lo, hi) starting from f = one, with
 // line coefficients from index `idx` on; the last segment (hi == 64) also

@@ -145,7 +145,7 @@ if prod:
              or len(prod.get("k_horner_tree2", {}).get("FETCH_SIZE", []))
              or len(prod.get("k_horner_tree", {}).get("FETCH_SIZE", [])) or 1)
     per_kernel = {}
-    product_kernels = ("k_prepare_wide", "k_prepare", "k_miller_seg", "k_fq12_reduce_wide", "k_horner_tree",
+    product_kernels = ("k_prepare_wide", "k_prepare", "k_prepare_wide_scaled", "k_prepare_scaled", "k_miller_seg", "k_fq12_reduce_wide", "k_horner_tree",
                        "k_horner_tree2", "k_seg_fe1", "k_seg_tail", "k_horner_wide", "k_pairing_latency", "k_err_status")  # not the bench's input generation
     for k, v in prod.items():
         if k not in product_kernels:
