@@ -71,12 +71,12 @@ int bn_dev_status(bn_ctx* ctx, void* stream);
 /* ---- several devices of the node in one process ----
  * A multi-device context shards the host-buffer calls bn_pairing_many,
  * bn_final_exponentiation_many, bn_miller_loop_many, bn_g1_mul_many, bn_g2_mul_many
- * and bn_g1_msm contiguously (device k takes bn_shard_range(n, D, k)), runs the
+ * bn_g1_msm and bn_g2_msm contiguously (device k takes bn_shard_range(n, D, k)), runs the
  * shards concurrently and writes each into the caller's output: the same bytes
  * as one device.  bn_pairing_batch / bn_miller_loop_batch reduce each shard to
  * one Miller value, multiply the partials on the first device in device order
  * (pairing_batch then runs one final exponentiation): the reference's shared
- * loop value exactly (mod.rs:609-640).  bn_g1_msm reduces each shard to its
+ * loop value exactly (mod.rs:609-640).  bn_g1_msm / bn_g2_msm reduce each shard to its
  * Jacobian partial sum, adds the partials on the first device in device order and
  * normalizes there.  Other calls need a single-device
  * context: bn_ctx_device(ctx, k) returns device k's (owned by ctx). */
@@ -156,16 +156,32 @@ int bn_g2_mul_many_dev(bn_ctx* ctx, const bn_g2* d_p, const bn_fr* d_k, size_t n
  * earlier work) on first use at a larger n, as bn_pairing_many_dev does. */
 int bn_g1_msm(bn_ctx* ctx, const bn_g1* p, const bn_fr* k, size_t n, bn_g1* out);
 int bn_g1_msm_dev(bn_ctx* ctx, const bn_g1* d_p, const bn_fr* d_k, size_t n, bn_g1* d_out, void* stream);
-/* window width in bits for the bucket path, 2 .. 16; 0 (default) = chosen from n by the measured table.
- * Any other value is refused with BN_ERR_INVALID_ARGUMENT.  Results are identical at every width. */
+/* window width in bits for the bucket path of both groups, 2 .. 16; 0 (default) = chosen from n by
+ * the group's own measured table.  Any other value is refused with BN_ERR_INVALID_ARGUMENT.  Results
+ * are identical at every width. */
 int bn_set_msm_window(bn_ctx* ctx, int c);
-/* batches below n terms take the small path (bn_g1_mul_many's kernels + an addition tree);
- * 0 sends every n >= 1 down the bucket path.  Default: the measured crossover or $BN254MI_MSM_MIN.
- * Results are identical on either path. */
+/* batches of either group below n terms take the small path (bn_g1_mul_many's / bn_g2_mul_many's
+ * kernels + an addition tree); 0 sends every n >= 1 down the bucket path.  Default: each group's own
+ * measured crossover, or $BN254MI_MSM_MIN for both.  Results are identical on either path. */
 int bn_set_msm_min(bn_ctx* ctx, size_t n);
-/* pre-size the MSM workspace for up to n terms (else allocated on first use, as bn_reserve);
+/* pre-size the G1 MSM workspace for up to n terms (else allocated on first use, as bn_reserve);
  * it is separate from the pairing workspace and not counted by bn_workspace_bytes */
 int bn_msm_reserve(bn_ctx* ctx, size_t n);
+
+/* ---- G2 multi-scalar multiplication (bucket method on the two-lane layout) ---- */
+
+/* The same contract over G2: *out = (sum over i < n of p[i] * k[i]).normalize(), the image (x, y, one)
+ * with one the Fq2 one; a zero sum, and n == 0, give G2::zero() = (0, one, 0).  p[i] may be any
+ * Jacobian image (z != one, and z == 0 with arbitrary x, y).  The same limits on n, refused before
+ * any buffer is read; NULL pointers are refused; the _dev form is refused on a multi-device context.
+ * A multi-device context shards bn_g2_msm as bn_g1_msm (bn_shard_range, Jacobian partials added on
+ * the first device in device order, normalized there): the single-device bytes. */
+int bn_g2_msm(bn_ctx* ctx, const bn_g2* p, const bn_fr* k, size_t n, bn_g2* out);
+int bn_g2_msm_dev(bn_ctx* ctx, const bn_g2* d_p, const bn_fr* d_k, size_t n, bn_g2* d_out, void* stream);
+/* pre-size the G2 MSM workspace for up to n terms.  The integer buffers (keys, sorted entries) are
+ * shared with G1; the bucket sums, partial sums and small-path products are G2's own (a bn_g2 is
+ * 192 bytes: 96 MiB of bucket sums at c = 16).  Not counted by bn_workspace_bytes. */
+int bn_g2_msm_reserve(bn_ctx* ctx, size_t n);
 
 /* ---- group law (lib.rs:388-423, 539-574; src/groups/mod.rs:169-216, 294-358) ----
  * Batched forms of the G1 / G2 operators, each lane running the reference's own

@@ -77,6 +77,8 @@ constexpr size_t kPrepareWideMaxDefault = 16384;
 // $BN254MI_MSM_MIN or bn_set_msm_min override.  0: the bucket path was the faster one
 // at every size of the sweep, down to one term.
 constexpr size_t kMsmMinDefault = 0;
+// the same for bn_g2_msm, read off G2's own sweep
+constexpr size_t kMsmG2MinDefault = 0;
 
 size_t ws_bytes(size_t n) {
     return n * ((size_t)kCoeffFq * 9 * 4 + kPathLanes * (2 * 9 * 4 + 1) + (size_t)kFeSlots * kSlotWords * 4) + 64;
@@ -929,8 +931,9 @@ int bn_ctx_create(int device, bn_ctx** out) {
         c->fe_ds_max = v < (size_t)kFeDsMax ? v : (size_t)kFeDsMax;
     }
     if (const char* e = getenv("BN254MI_PREPARE_WIDE_MAX")) c->prepare_wide_max = (size_t)strtoull(e, nullptr, 10);
-    c->msm_min = kMsmMinDefault;
-    if (const char* e = getenv("BN254MI_MSM_MIN")) c->msm_min = (size_t)strtoull(e, nullptr, 10);
+    c->msm_g1.min = kMsmMinDefault;
+    c->msm_g2.min = kMsmG2MinDefault;
+    if (const char* e = getenv("BN254MI_MSM_MIN")) c->msm_g1.min = c->msm_g2.min = (size_t)strtoull(e, nullptr, 10);
     Prog P;
     c->fe_out = (int)build_final_exp(P);
     P.finalize({(uint32_t)c->fe_out});
@@ -988,7 +991,8 @@ static void ctx_teardown(bn_ctx* c) {
         if (s) (void)hipStreamDestroy(s);
     for (void* p : {(void*)c->coeffs, (void*)c->paff, (void*)c->slots, (void*)c->flags, (void*)c->d_err,
                     (void*)c->d_prog, c->stage, (void*)c->tail_ws, (void*)c->fe_ds_ws, (void*)c->msm_keys,
-                    (void*)c->msm_sorted, (void*)c->msm_buckets, (void*)c->msm_parts, (void*)c->msm_tmp})
+                    (void*)c->msm_sorted, (void*)c->msm_g1.buckets, (void*)c->msm_g1.parts, (void*)c->msm_g1.tmp,
+                    (void*)c->msm_g2.buckets, (void*)c->msm_g2.parts, (void*)c->msm_g2.tmp})
         if (p) (void)hipFree(p);
     for (auto& ev : c->ev_marks)
         for (auto e : ev) c->ev_pool.push_back(e);
@@ -1540,31 +1544,79 @@ int bn_g2_mul_many(bn_ctx* c, const bn_g2* p, const bn_fr* k, size_t n, bn_g2* o
 
 }  // extern "C"
 
-// ---------------------------------------------------------------- G1 multi-scalar multiplication
-// (kernels_msm.hip).  The bucket path and the small path return the
-// same image: the group law is exact and the result is normalized.
+// ---------------------------------------------------------------- multi-scalar multiplication
+// (kernels_msm.hip, kernels_msm_g2.hip).  The bucket path and the
+// small path return the same image: the group law is exact and the result is
+// normalized.  The host sequence is one template over the point type; MsmGroup<P>
+// names the group's kernels, settings and buffers.
 constexpr size_t kMsmMaxTerms = size_t(1) << 26;  // the entry index keeps bit 31 for the sign; keys and positions are 32-bit
-// The window width used when bn_set_msm_window is 0: the fastest width of the measured
-// sweep (profiles/msm_sweep.jsonl, tools/msm_bench.py) at the nearest
-// measured size, the steps at the geometric means between sizes whose best width
-// differs.  Below 2^13 terms every width from 8 to 12 is within the run-to-run spread.
-static int msm_auto_window(size_t n) {
-    if (n < 6144) return 10;
-    if (n < 92682) return 12;    // 2^16.5
-    if (n < 370728) return 14;   // 2^18.5
-    if (n < 741455) return 15;   // 2^19.5
-    return 16;
-}
+template <class P>
+struct MsmGroup;
+template <>
+struct MsmGroup<bn_g1> {
+    static constexpr size_t kLanes = 1;  // lanes per element of the group-law kernels
+    static constexpr auto k_count = k_msm_count;
+    static constexpr auto k_scatter = k_msm_scatter;
+    static constexpr auto k_accumulate = k_msm_accumulate;
+    static constexpr auto k_reduce = k_msm_reduce;
+    static constexpr auto k_horner = k_msm_horner;
+    static constexpr auto k_finish = k_msm_finish;
+    static constexpr auto k_op = k_g1_op;
+    static MsmGroupWs<bn_g1>& ws(bn_ctx* c) { return c->msm_g1; }
+    static void mul(const bn_g1* d_p, const bn_fr* d_k, size_t n, bn_g1* d_out, hipStream_t s) {
+        g1_mul_launch(d_p, d_k, n, d_out, s);
+    }
+    // The window width used when bn_set_msm_window is 0: the fastest width of the measured
+    // sweep (profiles/msm_sweep.jsonl, tools/msm_bench.py) at the nearest
+    // measured size, the steps at the geometric means between sizes whose best width
+    // differs.  Below 2^13 terms every width from 8 to 12 is within the run-to-run spread.
+    static int auto_window(size_t n) {
+        if (n < 6144) return 10;
+        if (n < 92682) return 12;    // 2^16.5
+        if (n < 370728) return 14;   // 2^18.5
+        if (n < 741455) return 15;   // 2^19.5
+        return 16;
+    }
+};
+template <>
+struct MsmGroup<bn_g2> {
+    static constexpr size_t kLanes = kPathLanes;
+    static constexpr auto k_count = k_msm_count_g2;
+    static constexpr auto k_scatter = k_msm_scatter_g2;
+    static constexpr auto k_accumulate = k_msm_accumulate_g2;
+    static constexpr auto k_reduce = k_msm_reduce_g2;
+    static constexpr auto k_horner = k_msm_horner_g2;
+    static constexpr auto k_finish = k_msm_finish_g2;
+    static constexpr auto k_op = k_g2_op;
+    static MsmGroupWs<bn_g2>& ws(bn_ctx* c) { return c->msm_g2; }
+    static void mul(const bn_g2* d_p, const bn_fr* d_k, size_t n, bn_g2* d_out, hipStream_t s) {
+        g2_mul_launch(d_p, d_k, n, d_out, s);
+    }
+    // G2's own table, read off its own sweep in the same way (profiles/msm_g2_sweep.jsonl,
+    // tools/msm_bench.py --group g2): 11 is the fastest width in the
+    // thousands of terms, 12 at 2^15 and 14 already at 2^16.  Below 2^15 terms the widths
+    // from 8 to 13 differ by less than the run-to-run spread (0.5 ms on a 2.3 ms floor).
+    static int auto_window(size_t n) {
+        if (n < 1449) return 10;     // 2^10.5
+        if (n < 23171) return 11;    // 2^14.5
+        if (n < 46341) return 12;    // 2^15.5
+        if (n < 370728) return 14;   // 2^18.5
+        if (n < 741455) return 15;   // 2^19.5
+        return 16;
+    }
+};
 struct MsmPlan {
     bool small;
     int c;
     uint32_t nwin, nkeys, nseg;
     size_t nent;  // n * W(c): the most entries
 };
-static MsmPlan msm_plan(const bn_ctx* c, size_t n) {
+template <class P>
+static MsmPlan msm_plan(bn_ctx* c, size_t n) {
+    const MsmGroupWs<P>& g = MsmGroup<P>::ws(c);
     MsmPlan m{};
-    m.small = n < c->msm_min;
-    m.c = c->msm_window ? c->msm_window : msm_auto_window(n);
+    m.small = n < g.min;
+    m.c = g.window ? g.window : MsmGroup<P>::auto_window(n);
     m.nwin = (uint32_t)msm_windows(m.c);
     m.nkeys = msm_num_keys(m.c);
     m.nseg = (msm_buckets(m.c) + kMsmSegment - 1) / kMsmSegment;
@@ -1584,45 +1636,52 @@ static int msm_grow(bn_ctx* c, T** buf, size_t* cap, size_t need) {
     *cap = need;
     return BN_OK;
 }
+template <class P>
 static int msm_reserve(bn_ctx* c, size_t n, const MsmPlan& m) {
-    if (m.small) return msm_grow(c, &c->msm_tmp, &c->msm_tmp_cap, n);
+    MsmGroupWs<P>& g = MsmGroup<P>::ws(c);
+    if (m.small) return msm_grow(c, &g.tmp, &g.tmp_cap, n);
     RET_IF(msm_grow(c, &c->msm_keys, &c->msm_keys_cap, 3 * (size_t)m.nkeys + 1));
     RET_IF(msm_grow(c, &c->msm_sorted, &c->msm_sorted_cap, m.nent));
-    RET_IF(msm_grow(c, &c->msm_buckets, &c->msm_buckets_cap, (size_t)m.nkeys));
-    return msm_grow(c, &c->msm_parts, &c->msm_parts_cap, (size_t)m.nseg * m.nwin);
+    RET_IF(msm_grow(c, &g.buckets, &g.buckets_cap, (size_t)m.nkeys));
+    return msm_grow(c, &g.parts, &g.parts_cap, (size_t)m.nseg * m.nwin);
 }
 // buf[0] = sum of buf[0 .. m) by a halving addition tree in place (odd tail carried),
 // then *d_out = its returned image (finish) or the Jacobian sum as it stands
-static int msm_tree_out(bn_ctx* c, bn_g1* buf, size_t m, size_t width, int finish, bn_g1* d_out, hipStream_t s) {
+template <class P>
+static int msm_tree_out(bn_ctx* c, P* buf, size_t m, size_t width, int finish, P* d_out, hipStream_t s) {
+    using G = MsmGroup<P>;
     while (m > 1) {
         const size_t h = (m + 1) / 2;
-        k_g1_op<<<grid_for((m - h) * width), kBlock, 0, s>>>(kGroupAdd, buf, buf + h * width, (m - h) * width, buf, nullptr);
+        G::k_op<<<grid_for((m - h) * width), kBlock, 0, s>>>(kGroupAdd, buf, buf + h * width, (m - h) * width, buf, nullptr);
         m = h;
     }
     if (width != 1) return BN_OK;
     if (finish)
-        k_msm_finish<<<1, 64, 0, s>>>(m ? buf : nullptr, d_out);
+        G::k_finish<<<1, 64, 0, s>>>(m ? buf : nullptr, d_out);
     else if (m)
-        HIPCHK(c, hipMemcpyAsync(d_out, buf, sizeof(bn_g1), hipMemcpyDeviceToDevice, s));
+        HIPCHK(c, hipMemcpyAsync(d_out, buf, sizeof(P), hipMemcpyDeviceToDevice, s));
     else
-        k_msm_finish<<<1, 64, 0, s>>>(nullptr, d_out);  // zero is its own Jacobian image
+        G::k_finish<<<1, 64, 0, s>>>(nullptr, d_out);  // zero is its own Jacobian image
     return BN_OK;
 }
-// the device sequence on stream s; the caller holds the lock and the workspace order
-static int msm_dev_impl(bn_ctx* c, const bn_g1* d_p, const bn_fr* d_k, size_t n, bn_g1* d_out, hipStream_t s,
-                        int finish) {
+// the device sequence on stream s; the caller holds the lock and the workspace order.
+// The group-law kernels take G::kLanes lanes per element (kBlock is even: whole pairs).
+template <class P>
+static int msm_dev_impl(bn_ctx* c, const P* d_p, const bn_fr* d_k, size_t n, P* d_out, hipStream_t s, int finish) {
+    using G = MsmGroup<P>;
     if (n == 0) {
-        k_msm_finish<<<1, 64, 0, s>>>(nullptr, d_out);
+        G::k_finish<<<1, 64, 0, s>>>(nullptr, d_out);
         HIPCHK(c, hipGetLastError());
         return BN_OK;
     }
-    const MsmPlan m = msm_plan(c, n);
+    const MsmPlan m = msm_plan<P>(c, n);
     if (!m.small && m.nent > (size_t)0x7fffffff)
         return fail(c, BN_ERR_INVALID_ARGUMENT, "n * windows exceeds the 32-bit entry positions at this window width");
-    RET_IF(msm_reserve(c, n, m));
+    RET_IF(msm_reserve<P>(c, n, m));
+    MsmGroupWs<P>& g = G::ws(c);
     if (m.small) {
-        g1_mul_launch(d_p, d_k, n, c->msm_tmp, s);
-        RET_IF(msm_tree_out(c, c->msm_tmp, n, 1, finish, d_out, s));
+        G::mul(d_p, d_k, n, g.tmp, s);
+        RET_IF(msm_tree_out(c, g.tmp, n, 1, finish, d_out, s));
         HIPCHK(c, hipGetLastError());
         return BN_OK;
     }
@@ -1630,14 +1689,15 @@ static int msm_dev_impl(bn_ctx* c, const bn_g1* d_p, const bn_fr* d_k, size_t n,
     uint32_t* cursors = counts + m.nkeys;
     uint32_t* offsets = cursors + m.nkeys;
     const uint32_t nent = (uint32_t)m.nent;
+    const size_t nparts = (size_t)m.nseg * m.nwin;
     HIPCHK(c, hipMemsetAsync(counts, 0, (size_t)m.nkeys * 4, s));
-    k_msm_count<<<grid_for(n), kBlock, 0, s>>>(d_p, d_k, n, m.c, m.nkeys, counts);
+    G::k_count<<<grid_for(n), kBlock, 0, s>>>(d_p, d_k, n, m.c, m.nkeys, counts);
     k_msm_scan<<<1, kMsmScanBlock, 0, s>>>(counts, m.nkeys, offsets, cursors);
-    k_msm_scatter<<<grid_for(n), kBlock, 0, s>>>(d_p, d_k, n, m.c, m.nkeys, cursors, offsets, c->msm_sorted, nent);
-    k_msm_accumulate<<<grid_for(m.nkeys), kBlock, 0, s>>>(d_p, n, c->msm_sorted, offsets, m.nkeys, nent, c->msm_buckets);
-    k_msm_reduce<<<grid_for((size_t)m.nseg * m.nwin), kBlock, 0, s>>>(c->msm_buckets, m.c, m.nkeys, m.nseg, c->msm_parts);
-    RET_IF(msm_tree_out(c, c->msm_parts, m.nseg, m.nwin, 0, nullptr, s));
-    k_msm_horner<<<1, 64, 0, s>>>(c->msm_parts, m.c, finish, d_out);
+    G::k_scatter<<<grid_for(n), kBlock, 0, s>>>(d_p, d_k, n, m.c, m.nkeys, cursors, offsets, c->msm_sorted, nent);
+    G::k_accumulate<<<grid_for(G::kLanes * m.nkeys), kBlock, 0, s>>>(d_p, n, c->msm_sorted, offsets, m.nkeys, nent, g.buckets);
+    G::k_reduce<<<grid_for(G::kLanes * nparts), kBlock, 0, s>>>(g.buckets, m.c, m.nkeys, m.nseg, g.parts);
+    RET_IF(msm_tree_out<P>(c, g.parts, m.nseg, m.nwin, 0, nullptr, s));
+    G::k_horner<<<1, 64, 0, s>>>(g.parts, m.c, finish, d_out);
     HIPCHK(c, hipGetLastError());
     return BN_OK;
 }
@@ -1646,50 +1706,86 @@ static int msm_check_args(bn_ctx* c, const void* p, const void* k, size_t n, con
     if (!out || (n && (!p || !k))) return fail(c, BN_ERR_INVALID_ARGUMENT, "null buffer");
     return BN_OK;
 }
-static int msm_host(bn_ctx* c, const bn_g1* p, const bn_fr* k, size_t n, bn_g1* out, int finish) {
+template <class P>
+static int msm_host(bn_ctx* c, const P* p, const bn_fr* k, size_t n, P* out, int finish) {
     CTX_GUARD_HOST(c);
     RET_IF(msm_check_args(c, p, k, n, out));
-    RET_IF(stage(c, (n + 1) * sizeof(bn_g1) + n * sizeof(bn_fr)));
-    bn_g1* dout = (bn_g1*)c->stage;
-    bn_g1* dp = dout + 1;
+    RET_IF(stage(c, (n + 1) * sizeof(P) + n * sizeof(bn_fr)));
+    P* dout = (P*)c->stage;
+    P* dp = dout + 1;
     bn_fr* dk = (bn_fr*)(dp + n);
     if (n) {
-        HIPCHK(c, hipMemcpyAsync(dp, p, n * sizeof(bn_g1), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(dp, p, n * sizeof(P), hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(dk, k, n * sizeof(bn_fr), hipMemcpyHostToDevice, c->stream));
     }
     RET_IF(msm_dev_impl(c, dp, dk, n, dout, c->stream, finish));
-    HIPCHK(c, hipMemcpyAsync(out, dout, sizeof(bn_g1), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out, dout, sizeof(P), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return BN_OK;
 }
-extern "C" {
-
-int bn_internal_g1_msm_partial(bn_ctx* c, const bn_g1* p, const bn_fr* k, size_t n, bn_g1* out) {
-    return msm_host(c, p, k, n, out, 0);
-}
-int bn_internal_g1_sum(bn_ctx* c, const bn_g1* a, size_t m, bn_g1* out) {
+// *out = the returned image of the sum of the m host points a[0 .. m) (the partials of
+// a multi-device context, in device order)
+template <class P>
+static int msm_sum_host(bn_ctx* c, const P* a, size_t m, P* out) {
     CTX_GUARD_HOST(c);
     if (!out || (m && !a)) return fail(c, BN_ERR_INVALID_ARGUMENT, "null buffer");
-    RET_IF(msm_grow(c, &c->msm_tmp, &c->msm_tmp_cap, m + 1));
-    bn_g1* dout = c->msm_tmp + m;
-    if (m) HIPCHK(c, hipMemcpyAsync(c->msm_tmp, a, m * sizeof(bn_g1), hipMemcpyHostToDevice, c->stream));
-    RET_IF(msm_tree_out(c, c->msm_tmp, m, 1, 1, dout, c->stream));
+    MsmGroupWs<P>& g = MsmGroup<P>::ws(c);
+    RET_IF(msm_grow(c, &g.tmp, &g.tmp_cap, m + 1));
+    P* dout = g.tmp + m;
+    if (m) HIPCHK(c, hipMemcpyAsync(g.tmp, a, m * sizeof(P), hipMemcpyHostToDevice, c->stream));
+    RET_IF(msm_tree_out(c, g.tmp, m, 1, 1, dout, c->stream));
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(out, dout, sizeof(bn_g1), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out, dout, sizeof(P), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return BN_OK;
 }
-int bn_g1_msm(bn_ctx* c, const bn_g1* p, const bn_fr* k, size_t n, bn_g1* out) {
-    if (c && !c->subs.empty()) return bn_multi_g1_msm(c, p, k, n, out);
-    return msm_host(c, p, k, n, out, 1);
-}
-int bn_g1_msm_dev(bn_ctx* c, const bn_g1* d_p, const bn_fr* d_k, size_t n, bn_g1* d_out, void* stream) {
+template <class P>
+static int msm_dev(bn_ctx* c, const P* d_p, const bn_fr* d_k, size_t n, P* d_out, void* stream) {
     CTX_GUARD(c);
     RET_IF(msm_check_args(c, d_p, d_k, n, d_out));
     hipStream_t s = pick(c, stream);
     RET_IF(ws_acquire(c, s));
     WsUse use{c, s};
     return msm_dev_impl(c, d_p, d_k, n, d_out, s, 1);
+}
+// bn_msm_reserve / bn_g2_msm_reserve on a single-device context
+template <class P>
+static int msm_reserve_terms(bn_ctx* c, size_t n) {
+    CTX_GUARD(c);
+    if (n > kMsmMaxTerms) return fail(c, BN_ERR_INVALID_ARGUMENT, "more than 2^26 terms");
+    if (n == 0) return BN_OK;
+    const MsmPlan m = msm_plan<P>(c, n);
+    if (!m.small && m.nent > (size_t)0x7fffffff)
+        return fail(c, BN_ERR_INVALID_ARGUMENT, "n * windows exceeds the 32-bit entry positions at this window width");
+    return msm_reserve<P>(c, n, m);
+}
+extern "C" {
+
+int bn_internal_g1_msm_partial(bn_ctx* c, const bn_g1* p, const bn_fr* k, size_t n, bn_g1* out) {
+    return msm_host(c, p, k, n, out, 0);
+}
+int bn_internal_g1_sum(bn_ctx* c, const bn_g1* a, size_t m, bn_g1* out) { return msm_sum_host(c, a, m, out); }
+int bn_internal_g2_msm_partial(bn_ctx* c, const bn_g2* p, const bn_fr* k, size_t n, bn_g2* out) {
+    return msm_host(c, p, k, n, out, 0);
+}
+int bn_internal_g2_sum(bn_ctx* c, const bn_g2* a, size_t m, bn_g2* out) { return msm_sum_host(c, a, m, out); }
+int bn_g1_msm(bn_ctx* c, const bn_g1* p, const bn_fr* k, size_t n, bn_g1* out) {
+    if (c && !c->subs.empty()) return bn_multi_g1_msm(c, p, k, n, out);
+    return msm_host(c, p, k, n, out, 1);
+}
+int bn_g1_msm_dev(bn_ctx* c, const bn_g1* d_p, const bn_fr* d_k, size_t n, bn_g1* d_out, void* stream) {
+    return msm_dev(c, d_p, d_k, n, d_out, stream);
+}
+int bn_g2_msm(bn_ctx* c, const bn_g2* p, const bn_fr* k, size_t n, bn_g2* out) {
+    if (c && !c->subs.empty()) {
+        // the cap is on the whole sum, not on a shard
+        if (n > kMsmMaxTerms) return fail(c, BN_ERR_INVALID_ARGUMENT, "more than 2^26 terms");
+        return bn_multi_g2_msm(c, p, k, n, out);
+    }
+    return msm_host(c, p, k, n, out, 1);
+}
+int bn_g2_msm_dev(bn_ctx* c, const bn_g2* d_p, const bn_fr* d_k, size_t n, bn_g2* d_out, void* stream) {
+    return msm_dev(c, d_p, d_k, n, d_out, stream);
 }
 int bn_set_msm_window(bn_ctx* c, int bits) {
     if (c && bits != 0 && !msm_window_ok(bits))
@@ -1699,7 +1795,8 @@ int bn_set_msm_window(bn_ctx* c, int bits) {
         return BN_OK;
     }
     CTX_GUARD(c);
-    c->msm_window = bits;
+    c->msm_g1.window = bits;
+    c->msm_g2.window = bits;
     return BN_OK;
 }
 int bn_set_msm_min(bn_ctx* c, size_t n) {
@@ -1708,7 +1805,8 @@ int bn_set_msm_min(bn_ctx* c, size_t n) {
         return BN_OK;
     }
     CTX_GUARD(c);
-    c->msm_min = n;
+    c->msm_g1.min = n;
+    c->msm_g2.min = n;
     return BN_OK;
 }
 int bn_msm_reserve(bn_ctx* c, size_t n) {
@@ -1716,13 +1814,15 @@ int bn_msm_reserve(bn_ctx* c, size_t n) {
         for (bn_ctx* d : c->subs) RET_IF(bn_msm_reserve(d, n / c->subs.size() + 1));
         return BN_OK;
     }
-    CTX_GUARD(c);
-    if (n > kMsmMaxTerms) return fail(c, BN_ERR_INVALID_ARGUMENT, "more than 2^26 terms");
-    if (n == 0) return BN_OK;
-    const MsmPlan m = msm_plan(c, n);
-    if (!m.small && m.nent > (size_t)0x7fffffff)
-        return fail(c, BN_ERR_INVALID_ARGUMENT, "n * windows exceeds the 32-bit entry positions at this window width");
-    return msm_reserve(c, n, m);
+    return msm_reserve_terms<bn_g1>(c, n);
+}
+int bn_g2_msm_reserve(bn_ctx* c, size_t n) {
+    if (c && !c->subs.empty()) {
+        if (n > kMsmMaxTerms) return fail(c, BN_ERR_INVALID_ARGUMENT, "more than 2^26 terms");
+        for (bn_ctx* d : c->subs) RET_IF(bn_g2_msm_reserve(d, n / c->subs.size() + 1));
+        return BN_OK;
+    }
+    return msm_reserve_terms<bn_g2>(c, n);
 }
 
 int bn_fq12_op_many(bn_ctx* c, int op, const bn_gt* a, const bn_gt* b, size_t n, bn_gt* out) {

@@ -256,6 +256,23 @@ int bn_multi_g1_msm(bn_ctx* c, const bn_g1* p, const bn_fr* k_, size_t n, bn_g1*
     if (rc) return mfail(c, rc, bn_last_error(c->subs[0]));
     return BN_OK;
 }
+int bn_multi_g2_msm(bn_ctx* c, const bn_g2* p, const bn_fr* k_, size_t n, bn_g2* out) {
+    if (!out || (n && (!p || !k_))) return mfail(c, BN_ERR_INVALID_ARGUMENT, "null buffer");
+    const size_t d = c->subs.size();
+    std::vector<bn_g2> part(d);
+    std::vector<char> have(d, 0);
+    int rc = for_shards(c, n, [&](size_t k, size_t lo, size_t hi) {
+        have[k] = 1;
+        return bn_internal_g2_msm_partial(c->subs[k], p + lo, k_ + lo, hi - lo, &part[k]);
+    });
+    if (rc) return rc;
+    size_t m = 0;
+    for (size_t k = 0; k < d; ++k)
+        if (have[k]) part[m++] = part[k];  // device order
+    rc = bn_internal_g2_sum(c->subs[0], part.data(), m, out);
+    if (rc) return mfail(c, rc, bn_last_error(c->subs[0]));
+    return BN_OK;
+}
 
 // per-device Miller products of the shards, multiplied on device 0 in device order
 static int multi_miller_product(bn_ctx* c, const bn_g1* p, const bn_g2* q, size_t n, int mode, bn_gt* result,

@@ -10,6 +10,19 @@
 
 #include "../../include/bn254mi.h"
 
+// One group's settings and point buffers of the multi-scalar multiplication (P = bn_g1
+// or bn_g2): buckets the bucket sums, parts the segment and window partial sums, tmp
+// the small path's n products.
+template <class P>
+struct MsmGroupWs {
+    int window = 0;  // bits; 0: chosen from n (capi.hip msm_auto_window)
+    size_t min = 0;  // batches below this many terms take the small path
+    P* buckets = nullptr;
+    P* parts = nullptr;
+    P* tmp = nullptr;
+    size_t buckets_cap = 0, parts_cap = 0, tmp_cap = 0;
+};
+
 struct bn_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -83,20 +96,18 @@ struct bn_ctx {
     // same buffers.  No caller stream is remembered past its call.
     hipEvent_t ws_event = nullptr;
     bool ws_pending = false;
-    // G1 multi-scalar multiplication (bn_g1_msm, kernels_msm.hip).  Its workspace is
-    // its own (not part of bn_workspace_bytes), grown by bn_msm_reserve or on first
-    // use, ordered like the shared one (ws_event) and freed with the context:
-    // msm_keys = counts | cursors | offsets of the (window, bucket) keys, msm_sorted
-    // the entries sorted by key, msm_buckets the bucket sums, msm_parts the
-    // segment and window partial sums, msm_tmp the small path's n products.
-    int msm_window = 0;   // bits; 0: chosen from n (capi.hip msm_auto_window)
-    size_t msm_min = 0;   // batches below this many terms take the small path
+    // Multi-scalar multiplication (bn_g1_msm, bn_g2_msm; kernels_msm.hip,
+    // kernels_msm_g2.hip).  Its workspace is its own (not part of bn_workspace_bytes),
+    // grown by bn_msm_reserve / bn_g2_msm_reserve or on first use, ordered like the
+    // shared one (ws_event) and freed with the context.  Both groups share the integer
+    // buffers: msm_keys = counts | cursors | offsets of the (window, bucket) keys,
+    // msm_sorted the entries sorted by key.  Each group has its own settings and point
+    // buffers (MsmGroupWs).
     uint32_t* msm_keys = nullptr;
     uint32_t* msm_sorted = nullptr;
-    bn_g1* msm_buckets = nullptr;
-    bn_g1* msm_parts = nullptr;
-    bn_g1* msm_tmp = nullptr;
-    size_t msm_keys_cap = 0, msm_sorted_cap = 0, msm_buckets_cap = 0, msm_parts_cap = 0, msm_tmp_cap = 0;
+    size_t msm_keys_cap = 0, msm_sorted_cap = 0;
+    MsmGroupWs<bn_g1> msm_g1;
+    MsmGroupWs<bn_g2> msm_g2;
     // multi-device context (bn_ctx_create_multi): one single-device sub-context
     // per listed device; `device` is -1 and the fields above are unused
     std::vector<bn_ctx*> subs;
@@ -117,6 +128,7 @@ BN_HIDDEN int bn_multi_miller_loop_many(bn_ctx* c, const bn_g1* p, const bn_g2* 
 BN_HIDDEN int bn_multi_g1_mul_many(bn_ctx* c, const bn_g1* p, const bn_fr* k, size_t n, bn_g1* out);
 BN_HIDDEN int bn_multi_g2_mul_many(bn_ctx* c, const bn_g2* p, const bn_fr* k, size_t n, bn_g2* out);
 BN_HIDDEN int bn_multi_g1_msm(bn_ctx* c, const bn_g1* p, const bn_fr* k, size_t n, bn_g1* out);
+BN_HIDDEN int bn_multi_g2_msm(bn_ctx* c, const bn_g2* p, const bn_fr* k, size_t n, bn_g2* out);
 BN_HIDDEN int bn_multi_destroy(bn_ctx* c);
 // capi.hip internals used by capi_multi.hip
 BN_HIDDEN int bn_internal_miller_product(bn_ctx* c, const bn_g1* p, const bn_g2* q, size_t n, int mode, bn_gt* result);
@@ -125,4 +137,7 @@ BN_HIDDEN void bn_internal_gt_one(bn_gt* out);
 BN_HIDDEN int bn_internal_g1_msm_partial(bn_ctx* c, const bn_g1* p, const bn_fr* k, size_t n, bn_g1* out);
 // *out = the returned image (normalized; zero as G1::zero()) of the sum of a[0 .. m)
 BN_HIDDEN int bn_internal_g1_sum(bn_ctx* c, const bn_g1* a, size_t m, bn_g1* out);
+// the same over G2
+BN_HIDDEN int bn_internal_g2_msm_partial(bn_ctx* c, const bn_g2* p, const bn_fr* k, size_t n, bn_g2* out);
+BN_HIDDEN int bn_internal_g2_sum(bn_ctx* c, const bn_g2* a, size_t m, bn_g2* out);
 }

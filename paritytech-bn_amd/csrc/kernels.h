@@ -34,10 +34,8 @@ constexpr int kSlotWords = 108;              // one Fq12: 12 Fq x 9 digits
 // windows of cyclotomic-subgroup waves (x^0..x^15 otherwise), in the context's
 // Fq12 slots
 constexpr int kGtPowEntries = 17;
-// G1 multi-scalar multiplication (kernels_msm.hip): buckets per lane of the bucket
-// reduction (a lane's dependent chain is 2 * kMsmSegment + 2 * (c - 1) + 1 group
-// operations), and the one block of the histogram scan
-constexpr uint32_t kMsmSegment = 16;
+// multi-scalar multiplication (kernels_msm.hip, kernels_msm_g2.hip): the one block of
+// the histogram scan (kMsmSegment: msm.h)
 constexpr int kMsmScanBlock = 1024;
 
 // ---------------------------------------------------------------- lane-strided storage
@@ -682,6 +680,15 @@ __global__ void __launch_bounds__(kBlock) k_msm_accumulate(const bn_g1* __restri
 __global__ void __launch_bounds__(kBlock) k_msm_reduce(const bn_g1* __restrict__ buckets, int c, uint32_t nkeys, uint32_t nseg, bn_g1* __restrict__ parts);
 __global__ void __launch_bounds__(64) k_msm_horner(const bn_g1* __restrict__ win, int c, int finish, bn_g1* __restrict__ out);
 __global__ void __launch_bounds__(64) k_msm_finish(const bn_g1* in, bn_g1* out);
+__global__ void __launch_bounds__(kBlock) k_msm_count_g2(const bn_g2* __restrict__ p, const bn_fr* __restrict__ k, size_t n, int c, uint32_t nkeys, uint32_t* __restrict__ counts);
+__global__ void __launch_bounds__(kBlock) k_msm_scatter_g2(const bn_g2* __restrict__ p, const bn_fr* __restrict__ k, size_t n, int c, uint32_t nkeys, uint32_t* __restrict__ cursors,
+                                                           const uint32_t* __restrict__ offsets, uint32_t* __restrict__ sorted, uint32_t nent);
+// kernels_msm_g2.hip: kPathLanes lanes per (window, bucket) key, per (segment, window), per result
+__global__ void __launch_bounds__(kBlock) k_msm_accumulate_g2(const bn_g2* __restrict__ p, size_t n, const uint32_t* __restrict__ sorted, const uint32_t* __restrict__ offsets,
+                                                              uint32_t nkeys, uint32_t nent, bn_g2* __restrict__ buckets);
+__global__ void __launch_bounds__(kBlock) k_msm_reduce_g2(const bn_g2* __restrict__ buckets, int c, uint32_t nkeys, uint32_t nseg, bn_g2* __restrict__ parts);
+__global__ void __launch_bounds__(64) k_msm_horner_g2(const bn_g2* __restrict__ win, int c, int finish, bn_g2* __restrict__ out);
+__global__ void __launch_bounds__(64) k_msm_finish_g2(const bn_g2* in, bn_g2* out);
 __global__ void __launch_bounds__(kPairBlock) k_gt_pow(const bn_gt* __restrict__ a, const bn_fr* __restrict__ k, size_t n,
                                                    bn_gt* __restrict__ out, uint32_t* __restrict__ ws);
 // kernels_codec.hip (codec.h): encodings, square roots, validation, decompression

@@ -1,6 +1,8 @@
 // kernels_msm.hip -- G1 multi-scalar multiplication by the bucket method:
-// S = sum_i k[i] * P[i], normalized.  The phases pass data only across kernel
-// boundaries on one stream (no block waits for another):
+// S = sum_i k[i] * P[i], normalized (and the recoding, histogram and scatter of the
+// G2 one, whose group-law kernels are kernels_msm_g2.hip; the group-law bodies of both
+// are msm_group.h's).  The phases pass data only across kernel boundaries on one
+// stream (no block waits for another):
 //   k_msm_count       signed-digit recoding (msm.h), histogram of the (window, bucket) keys
 //   k_msm_scan        exclusive scan of the histogram -> bucket offsets and scatter cursors
 //   k_msm_scatter     recoding again, each entry (term index, sign) to its bucket's run
@@ -14,6 +16,7 @@
 #define BN_FOLD_LDS 1
 #endif
 #include "kernels.h"
+#include "msm_group.h"
 
 namespace bn {
 
@@ -25,29 +28,23 @@ __device__ __forceinline__ void st_g1(bn_g1& o, const G1J& r) {
     st_ref(o.y, r.y);
     st_ref(o.z, r.z);
 }
-__device__ __forceinline__ G1J g1_select(bool c, const G1J& a, const G1J& b) {
-    return {F_select(c, a.x, b.x), F_select(c, a.y, b.y), F_select(c, a.z, b.z)};
-}
-// the returned image: normalize(), and G1::zero() = (0, one, 0) for any zero point
-__device__ __forceinline__ G1J msm_finish(const G1J& a) {
-    const G1J r = jac_normalize(a);
-    return g1_select(jac_is_zero(a), jac_zero<Fq>(), r);
-}
 
 // ---------------------------------------------------------------- recoding, histogram, scatter
 // One lane per term.  kScatter = false counts the keys; true claims a position in
 // each key's run (an atomic cursor: the order inside a bucket is not fixed, the
 // bucket's sum and so the normalized result do not depend on it).  Zero digits and
-// zero points produce no entry.
-template <bool kScatter>
-__device__ __forceinline__ void msm_digits(const bn_g1* __restrict__ p, const bn_fr* __restrict__ k, size_t n, int c,
+// zero points produce no entry.  All it reads of a point is whether z is zero.
+__device__ __forceinline__ bool msm_point_is_zero(const bn_g1& a) { return F_is_zero(ld_ref(a.z)); }
+__device__ __forceinline__ bool msm_point_is_zero(const bn_g2& a) { return F_is_zero(ld_ref2(a.z)); }
+template <bool kScatter, class P>
+__device__ __forceinline__ void msm_digits(const P* __restrict__ p, const bn_fr* __restrict__ k, size_t n, int c,
                                            uint32_t nkeys, uint32_t* __restrict__ counts,
                                            const uint32_t* __restrict__ offsets, uint32_t* __restrict__ sorted,
                                            uint32_t nent) {
     fold_table_init();
     const size_t i = lane_id();
     if (i >= n) return;
-    if (F_is_zero(ld_ref(p[i].z))) return;
+    if (msm_point_is_zero(p[i])) return;
     uint32_t s[8];
     fr_to_canonical(k[i], s);
     uint32_t carry = 0;
@@ -73,6 +70,18 @@ __global__ void __launch_bounds__(kBlock) k_msm_scatter(const bn_g1* __restrict_
                                                         size_t n, int c, uint32_t nkeys, uint32_t* __restrict__ cursors,
                                                         const uint32_t* __restrict__ offsets,
                                                         uint32_t* __restrict__ sorted, uint32_t nent) {
+    msm_digits<true>(p, k, n, c, nkeys, cursors, offsets, sorted, nent);
+}
+__global__ void __launch_bounds__(kBlock) k_msm_count_g2(const bn_g2* __restrict__ p, const bn_fr* __restrict__ k,
+                                                         size_t n, int c, uint32_t nkeys,
+                                                         uint32_t* __restrict__ counts) {
+    msm_digits<false>(p, k, n, c, nkeys, counts, nullptr, nullptr, 0);
+}
+__global__ void __launch_bounds__(kBlock) k_msm_scatter_g2(const bn_g2* __restrict__ p, const bn_fr* __restrict__ k,
+                                                           size_t n, int c, uint32_t nkeys,
+                                                           uint32_t* __restrict__ cursors,
+                                                           const uint32_t* __restrict__ offsets,
+                                                           uint32_t* __restrict__ sorted, uint32_t nent) {
     msm_digits<true>(p, k, n, c, nkeys, cursors, offsets, sorted, nent);
 }
 
@@ -106,10 +115,8 @@ __global__ void __launch_bounds__(kMsmScanBlock) k_msm_scan(const uint32_t* __re
 }
 
 // ---------------------------------------------------------------- bucket accumulation
-// One lane per (window, bucket): walks its run of sorted entries, gathers the point,
-// applies the digit's sign and adds.  jac_add is the general one: its zero
-// short-cuts and doubling branch make duplicates and P + (-P) in a bucket come out
-// right.  An empty bucket is zero.
+// One lane per (window, bucket): the sum of its run of sorted entries
+// (msm_group.h msm_bucket_sum).  An empty bucket is zero.
 __global__ void __launch_bounds__(kBlock) k_msm_accumulate(const bn_g1* __restrict__ p, size_t n,
                                                            const uint32_t* __restrict__ sorted,
                                                            const uint32_t* __restrict__ offsets, uint32_t nkeys,
@@ -121,27 +128,14 @@ __global__ void __launch_bounds__(kBlock) k_msm_accumulate(const bn_g1* __restri
     hi = hi < nent ? hi : nent;
     uint32_t lo = offsets[key];
     lo = lo < hi ? lo : hi;
-    G1J acc = jac_zero<Fq>();
-    for (uint32_t e = lo; e < hi; ++e) {
-        const uint32_t ent = sorted[e];
-        const uint32_t idx = msm_entry_index(ent);
-        if (idx >= n) continue;
-        G1J pt = ld_g1(p[idx]);
-        const G1J ng = jac_neg(pt);
-        pt = g1_select(msm_entry_neg(ent), ng, pt);
-        acc = jac_add(acc, pt);
-    }
+    const G1J acc = msm_bucket_sum<Fq>([&](uint32_t idx) { return ld_g1(p[idx]); }, n, sorted, lo, hi);
     st_g1(buckets[key], acc);
 }
 
 // ---------------------------------------------------------------- bucket reduction
-// One lane per (segment, window).  Segment s of a window holds the buckets
-// j0 .. j0 + len - 1 (j0 = s * kMsmSegment); bucket b weighs (b >> rs) + 1, rs the
-// window's replica shift (msm.h: 0 except in the top window).  Running sums from the
-// top give S = sum B_b and, adding S into T at every b that is a multiple of 2^rs,
-// T = sum (weight(b) - ceil(j0 / 2^rs)) * B_b; the lane returns T + ceil(j0 / 2^rs) * S,
-// the product by a (c - 1)-bit double-and-add.  parts[s * nwin + w], so that the
-// addition tree over the segments is k_g1_op on contiguous halves.
+// One lane per (segment, window): the segment's weighted sum (msm_group.h
+// msm_segment_sum).  parts[s * nwin + w], so that the addition tree over the
+// segments is k_g1_op on contiguous halves.
 __global__ void __launch_bounds__(kBlock) k_msm_reduce(const bn_g1* __restrict__ buckets, int c, uint32_t nkeys,
                                                        uint32_t nseg, bn_g1* __restrict__ parts) {
     fold_table_init();
@@ -149,53 +143,28 @@ __global__ void __launch_bounds__(kBlock) k_msm_reduce(const bn_g1* __restrict__
     const uint32_t nwin = (uint32_t)msm_windows(c);
     if (t >= (size_t)nseg * nwin) return;
     const uint32_t s = (uint32_t)(t / nwin), w = (uint32_t)(t % nwin);
-    const uint32_t nb = msm_buckets(c);
-    const int rs = msm_replica_shift(c, (int)w);
-    const uint32_t rmask = (1u << rs) - 1u;
-    const uint32_t j0 = s * kMsmSegment;
-    const uint32_t len = j0 >= nb ? 0u : (nb - j0 < kMsmSegment ? nb - j0 : kMsmSegment);
-    G1J sum = jac_zero<Fq>(), wsum = jac_zero<Fq>();
-    for (uint32_t j = len; j-- > 0;) {
-        const uint32_t key = w * nb + j0 + j;
-        if (key >= nkeys) continue;
-        sum = jac_add(sum, ld_g1(buckets[key]));
-        const G1J a = jac_add(wsum, sum);
-        wsum = g1_select(((j0 + j) & rmask) == 0, a, wsum);
-    }
-    const uint32_t base = (j0 + rmask) >> rs;  // ceil(j0 / 2^rs) < 2^(c-1)
-    G1J m = jac_zero<Fq>();                    // base * sum
-    for (int b = c - 2; b >= 0; --b) {
-        m = jac_double(m);
-        const G1J a = jac_add(m, sum);
-        m = g1_select(((base >> b) & 1u) != 0, a, m);
-    }
-    st_g1(parts[t], jac_add(wsum, m));
+    st_g1(parts[t], msm_segment_sum<Fq>([&](uint32_t key) { return ld_g1(buckets[key]); }, c, nkeys, s, w));
 }
 
 // ---------------------------------------------------------------- window combination
-// One lane: Horner over the window sums win[0 .. nwin) (c doublings and one addition
-// per window).  finish != 0: the normalized image (msm_finish); 0: the Jacobian
-// partial sum as it stands (a multi-device context adds the partials first).
+// One lane: Horner over the window sums win[0 .. nwin) (msm_group.h msm_horner_sum).
+// finish != 0: the normalized image (msm_finish_point); 0: the Jacobian partial sum
+// as it stands (a multi-device context adds the partials first).
 __global__ void __launch_bounds__(64) k_msm_horner(const bn_g1* __restrict__ win, int c, int finish,
                                                    bn_g1* __restrict__ out) {
     fold_table_init();
     if (lane_id() != 0) return;
-    const int nwin = msm_windows(c);
-    G1J acc = ld_g1(win[nwin - 1]);
-    for (int w = nwin - 2; w >= 0; --w) {
-        for (int b = 0; b < c; ++b) acc = jac_double(acc);
-        acc = jac_add(acc, ld_g1(win[w]));
-    }
-    if (finish) acc = msm_finish(acc);
+    G1J acc = msm_horner_sum<Fq>([&](int w) { return ld_g1(win[w]); }, c);
+    if (finish) acc = msm_finish_point(acc);
     st_g1(*out, acc);
 }
-// *out = the returned image of *in (msm_finish); in == nullptr: of zero (n == 0)
+// *out = the returned image of *in (msm_finish_point); in == nullptr: of zero (n == 0)
 __global__ void __launch_bounds__(64) k_msm_finish(const bn_g1* in, bn_g1* out) {
     fold_table_init();
     if (lane_id() != 0) return;
     G1J a = jac_zero<Fq>();
     if (in) a = ld_g1(*in);
-    st_g1(*out, msm_finish(a));
+    st_g1(*out, msm_finish_point(a));
 }
 
 }  // namespace bn

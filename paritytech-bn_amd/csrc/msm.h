@@ -1,5 +1,5 @@
-// msm.h -- scalar recoding and bucket keys of the G1 multi-scalar multiplication
-// (kernels_msm.hip).  Plain integer code over the canonical scalar's eight
+// msm.h -- scalar recoding and bucket keys of the G1 and G2 multi-scalar multiplication
+// (kernels_msm.hip, kernels_msm_g2.hip).  Plain integer code over the canonical scalar's eight
 // 32-bit words, host and device, so tests/native/msm_emul.cpp compiles it with
 // g++ alone.
 //
@@ -30,6 +30,9 @@ constexpr int kMsmMaxWindow = 16;
 constexpr int kMsmScalarBits = 254;  // r < 2^254
 // the most windows any supported width has (c = 2)
 constexpr int kMsmMaxWindows = kMsmScalarBits / kMsmMinWindow + 1;
+// buckets per lane of the bucket reduction: a lane's dependent chain is
+// 2 * kMsmSegment + 2 * (c - 1) + 1 group operations
+constexpr uint32_t kMsmSegment = 16;
 
 BN_INLINE bool msm_window_ok(int c) { return c >= kMsmMinWindow && c <= kMsmMaxWindow; }
 // W(c)

@@ -20,7 +20,7 @@ and the wire formats and validation around it:
     Gt.pow(Fr)                                         lib.rs:592-594
 
 plus the batched forms the reference lacks (pairing_many, g1_mul_many, and the
-multi-scalar multiplication g1_msm = sum of points[i] * scalars[i]) that
+multi-scalar multiplications g1_msm / g2_msm = sum of points[i] * scalars[i]) that
 the engine exists for.  Values keep the reference's memory images (canonical
 Montgomery, little-endian u64 limbs), so a Gt compares equal exactly when the
 reference's derived PartialEq would.  Every computation runs on the GPU; there
@@ -402,7 +402,7 @@ def g2_mul_many(p, k):
 
 
 def _images(xs, width):
-    """(n, width) uint64 rows from a sequence of G1 / Fr values or an array of images."""
+    """(n, width) uint64 rows from a sequence of G1 / G2 / Fr values or an array of images."""
     if isinstance(xs, np.ndarray):
         return _native._arr(xs, width)
     xs = list(xs)
@@ -421,6 +421,18 @@ def g1_msm(points, scalars):
     if p.shape[0] == 0:
         return G1.zero()
     return G1(context().g1_msm(p, k))
+
+
+def g2_msm(points, scalars):
+    """sum of points[i] * scalars[i] as a normalized G2 (bn_g2_msm).  Takes sequences of
+    G2 / Fr or the (n, 24) / (n, 4) image arrays; no terms give G2.zero() without a
+    device call; different lengths raise ValueError."""
+    p, k = _images(points, 24), _images(scalars, 4)
+    if p.shape[0] != k.shape[0]:
+        raise ValueError("g2_msm: %d points and %d scalars" % (p.shape[0], k.shape[0]))
+    if p.shape[0] == 0:
+        return G2.zero()
+    return G2(context().g2_msm(p, k))
 
 
 def g2_affine_new_many(x, y):

@@ -38,6 +38,7 @@ EXPORTS = [
     "bn_pairing_batch_dev", "bn_miller_loop_batch_dev", "bn_set_fe_wide_max", "bn_g2_precompute_many",
     "bn_set_latency_max", "bn_dev_status", "bn_set_fq12_op_unit",
     "bn_g1_msm", "bn_g1_msm_dev", "bn_set_msm_window", "bn_set_msm_min", "bn_msm_reserve",
+    "bn_g2_msm", "bn_g2_msm_dev", "bn_g2_msm_reserve",
 ] + ["bn_%s_%s_many%s" % (g, op, dev) for g in ("g1", "g2") for op in ("add", "sub", "neg", "normalize", "eq")
      for dev in ("", "_dev")]
 GROUP_OPS = ("add", "sub", "neg", "normalize", "eq")
@@ -127,6 +128,9 @@ def load():
         "bn_set_msm_window": ([vp, i], i),
         "bn_set_msm_min": ([vp, sz], i),
         "bn_msm_reserve": ([vp, sz], i),
+        "bn_g2_msm": ([vp, vp, vp, sz, vp], i),
+        "bn_g2_msm_dev": ([vp, vp, vp, sz, vp, vp], i),
+        "bn_g2_msm_reserve": ([vp, sz], i),
     }
     for g in ("g1", "g2"):
         for op in GROUP_OPS:
@@ -335,6 +339,15 @@ class Context:
         self._check(self._L.bn_g1_msm(self._h, _ptr(p), _ptr(k), n, _ptr(out)))
         return out
 
+    def g2_msm(self, p, k):
+        """bn_g2_msm: the normalized image (24 words) of sum p[i] * k[i]; G2::zero() when
+        the sum is zero or there are no terms."""
+        p, k = _arr(p, 24), _arr(k, 4)
+        n = _same_rows(p, k)
+        out = np.zeros(24, np.uint64)
+        self._check(self._L.bn_g2_msm(self._h, _ptr(p), _ptr(k), n, _ptr(out)))
+        return out
+
     def fq12_op_many(self, op, a, b=None):
         a = _arr(a, 48)
         bb = _arr(b, 48) if b is not None else None
@@ -360,8 +373,12 @@ class Context:
     def g1_msm_dev(self, d_p, d_k, n, d_out, stream=None):
         self._check(self._L.bn_g1_msm_dev(self._h, d_p, d_k, n, d_out, stream))
 
+    def g2_msm_dev(self, d_p, d_k, n, d_out, stream=None):
+        self._check(self._L.bn_g2_msm_dev(self._h, d_p, d_k, n, d_out, stream))
+
     def set_msm_window(self, c):
-        """Window width in bits of the MSM bucket path (2 .. 16); 0: chosen from n."""
+        """Window width in bits of the MSM bucket path of both groups (2 .. 16); 0: chosen
+        from n by the group's own table."""
         self._check(self._L.bn_set_msm_window(self._h, c))
 
     def set_msm_min(self, n):
@@ -370,6 +387,9 @@ class Context:
 
     def msm_reserve(self, n):
         self._check(self._L.bn_msm_reserve(self._h, n))
+
+    def g2_msm_reserve(self, n):
+        self._check(self._L.bn_g2_msm_reserve(self._h, n))
 
     def pairing_batch_dev(self, d_p, d_q, n, d_out, d_status=None, stream=None):
         self._check(self._L.bn_pairing_batch_dev(self._h, d_p, d_q, n, d_out, d_status, stream))

@@ -1,16 +1,17 @@
 #!/usr/bin/env python3
-"""Device time of bn_g1_msm_dev per size (HBM-resident inputs, torch events on the
-launch stream, bn_msm_reserve and a warm-up before timing), alternating in one
-process:
+"""Device time of bn_g1_msm_dev (or, with --group g2, bn_g2_msm_dev) per size
+(HBM-resident inputs, torch events on the launch stream, the group's reserve call and a
+warm-up before timing), alternating in one process:
   small    the small path forced (bn_g1_mul_many's kernels, an addition tree of
            k_g1_op, normalize): what a caller composes from bn_g1_mul_many_dev,
            ceil(log2 n) x bn_g1_add_many_dev and bn_g1_normalize_many_dev
+           (g2: the same from the bn_g2_* calls)
   c=K      the bucket path forced at window width K
   default  a context with untouched settings (the window table and the threshold)
-Before a size is timed every form must return the same 96 bytes, else the script
-exits non-zero.  One JSON line per size, then one line for all-equal scalars at
---skew terms (one lane per window walks every term: the documented skew limit).
-`frac` is the integer-VALU roofline fraction as DESIGN.md §4.5 counts it:
+Before a size is timed every form must return the same 96 (g2: 192) bytes, else the
+script exits non-zero.  One JSON line per size, then one line for all-equal scalars at
+--skew terms (one lane, or lane pair, per window walks every term: the documented skew
+limit).  `frac` is the integer-VALU roofline fraction as DESIGN.md §4.5 counts it:
 algorithmic Fq products x 128 MAD32 over the time, against 39.3 T MAD32/s.
 """
 import argparse
@@ -26,18 +27,22 @@ sys.path.insert(0, os.path.join(ROOT, "paritytech-bn_amd"))
 sys.path.insert(0, ROOT)
 
 PEAK_MAD32 = 39.3e12
-ADD, DBL = 16, 7  # Fq products of jac_add / jac_double (curve.h)
-SEGMENT = 16      # kMsmSegment (kernels.h)
+# Fq products of jac_add / jac_double (curve.h): 11 products + 5 squares, 2 products + 5 squares.
+# g2: an Fq2 product is two Fq products on each lane of the pair (fq2_split.h) = 4, an Fq2
+# square one on each lane (fq2.rs:105-117) = 2
+OPS = {"g1": (16, 7), "g2": (11 * 4 + 5 * 2, 2 * 4 + 5 * 2)}
+SEGMENT = 16      # kMsmSegment (msm.h)
 
 
 def windows(c):
     return 254 // c + 1
 
 
-def bucket_products(n, c):
+def bucket_products(n, c, group="g1"):
     """Fq products of the bucket path by count: n additions per window into the buckets,
     two per bucket and a (c-1)-bit double-and-add per segment in the reduction, the
     segment tree, Horner over the windows."""
+    ADD, DBL = OPS[group]
     w, nb = windows(c), 1 << (c - 1)
     nseg = (nb + SEGMENT - 1) // SEGMENT
     adds = n * w + 2 * nb * w + nseg * w * c + (nseg - 1) * w + (w - 1)
@@ -45,13 +50,15 @@ def bucket_products(n, c):
     return ADD * adds + DBL * dbls
 
 
-def small_products(n):
+def small_products(n, group="g1"):
     """254 doublings and 127 additions per term on average, n - 1 additions in the tree"""
+    ADD, DBL = OPS[group]
     return n * (254 * DBL + 127 * ADD) + (n - 1) * ADD
 
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--group", choices=("g1", "g2"), default="g1")
     ap.add_argument("--sizes", default="1,16,128,512," + ",".join(str(1 << e) for e in range(10, 21)))
     ap.add_argument("--windows", default="8,9,10,11,12,13,14,15,16")
     ap.add_argument("--reps", type=int, default=20)
@@ -62,7 +69,12 @@ def main():
 
     from substrate_bn import Context, synth
 
+    grp = args.group
+    words = {"g1": 12, "g2": 24}[grp]
+
     def emit(rec):
+        if grp != "g1":
+            rec = dict({"group": grp}, **rec)
         line = json.dumps(rec)
         print(line, flush=True)
         if args.out:
@@ -76,16 +88,18 @@ def main():
     nmax = max(sizes + [args.skew])
     s = synth.fr_images_raw(nmax, 0x6d736d31)
     k = synth.fr_images_raw(nmax, 0x6d736d32, lo=0)
-    g1 = torch.from_numpy(np.tile(synth.g1_one_image().view(np.int64), (nmax, 1))).to(dev)
+    one = synth.g1_one_image() if grp == "g1" else synth.g2_one_image()
+    gen = torch.from_numpy(np.tile(one.view(np.int64), (nmax, 1))).to(dev)
     sd = torch.from_numpy(s.view(np.int64)).to(dev)
     K = torch.from_numpy(k.view(np.int64)).to(dev)
-    P = torch.empty((nmax, 12), dtype=torch.int64, device=dev)
+    P = torch.empty((nmax, words), dtype=torch.int64, device=dev)
     stream = torch.cuda.Stream(dev)
     sh = stream.cuda_stream
     torch.cuda.synchronize(dev)
-    ctx.g1_mul_many_dev(g1.data_ptr(), sd.data_ptr(), nmax, P.data_ptr(), sh)
+    mul_many = ctx.g1_mul_many_dev if grp == "g1" else ctx.g2_mul_many_dev
+    mul_many(gen.data_ptr(), sd.data_ptr(), nmax, P.data_ptr(), sh)
     torch.cuda.synchronize(dev)
-    out = torch.zeros(12, dtype=torch.int64, device=dev)
+    out = torch.zeros(words, dtype=torch.int64, device=dev)
 
     def setup(name):
         """-> the context to call for form `name`, set up for it"""
@@ -99,14 +113,21 @@ def main():
             ctx.set_msm_window(int(name[2:]))
         return ctx
 
+    def reserve(c, n):
+        if grp == "g1":
+            c.msm_reserve(n)
+        else:
+            c.g2_msm_reserve(n)
+
     def run(name, n, kd, timed):
         c = setup(name)
         if not timed:
-            c.msm_reserve(n)
+            reserve(c, n)
+        msm_dev = c.g1_msm_dev if grp == "g1" else c.g2_msm_dev
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         with torch.cuda.stream(stream):
             e0.record()
-            c.g1_msm_dev(P.data_ptr(), kd.data_ptr(), n, out.data_ptr(), sh)
+            msm_dev(P.data_ptr(), kd.data_ptr(), n, out.data_ptr(), sh)
             e1.record()
         torch.cuda.synchronize(dev)
         return e0.elapsed_time(e1), out.cpu().numpy().view(np.uint64).copy()
@@ -129,11 +150,11 @@ def main():
             for f in forms:
                 times[f].append(run(f, n, K, True)[0])
         rec = {"n": n, "reps": args.reps, "small": stats(times["small"]), "default": stats(times["default"])}
-        rec["small"]["frac"] = round(small_products(n) * 128 / (rec["small"]["median_ms"] * 1e-3) / PEAK_MAD32, 4)
+        rec["small"]["frac"] = round(small_products(n, grp) * 128 / (rec["small"]["median_ms"] * 1e-3) / PEAK_MAD32, 4)
         best = None
         for c in cs:
             st = stats(times["c=%d" % c])
-            st["frac"] = round(bucket_products(n, c) * 128 / (st["median_ms"] * 1e-3) / PEAK_MAD32, 4)
+            st["frac"] = round(bucket_products(n, c, grp) * 128 / (st["median_ms"] * 1e-3) / PEAK_MAD32, 4)
             rec["c=%d" % c] = st
             if best is None or st["median_ms"] < rec["c=%d" % best]["median_ms"]:
                 best = c
@@ -147,7 +168,7 @@ def main():
         torch.cuda.synchronize(dev)
         _, want = run("small", n, ke, False)
         dctx.set_msm_min(0)  # the bucket path at the table's window, whatever the threshold
-        dctx.msm_reserve(n)
+        reserve(dctx, n)
         ms, got = run("default", n, ke, True)
         if not np.array_equal(got, want):
             print("MISMATCH on the all-equal batch", file=sys.stderr)
