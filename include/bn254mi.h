@@ -78,7 +78,9 @@ int bn_dev_status(bn_ctx* ctx, void* stream);
  * (pairing_batch then runs one final exponentiation): the reference's shared
  * loop value exactly (mod.rs:609-640).  bn_g1_msm / bn_g2_msm reduce each shard to its
  * Jacobian partial sum, adds the partials on the first device in device order and
- * normalizes there.  Other calls need a single-device
+ * normalizes there.  bn_pairing_batch_many is sharded by whole products, balanced by
+ * terms: device k takes the products from the first whose offset is >= k * n / D up to
+ * device k + 1's first, and writes its own rows of out.  Other calls need a single-device
  * context: bn_ctx_device(ctx, k) returns device k's (owned by ctx). */
 int bn_ctx_create_multi(const int* devices, int ndev, bn_ctx** out);
 int bn_ctx_num_devices(const bn_ctx* ctx);
@@ -103,6 +105,44 @@ int bn_pairing_many_dev(bn_ctx* ctx, const bn_g1* d_p, const bn_g2* d_q, size_t 
 /* *out = pairing_batch(&[(p[i], q[i])])                       (lib.rs:615-623, mod.rs:904-926)
  * Pairs with a zero point are skipped; n == 0 or all skipped -> Gt::one(). */
 int bn_pairing_batch(bn_ctx* ctx, const bn_g1* p, const bn_g2* q, size_t n, bn_gt* out);
+
+/* out[j] = pairing_batch(&[(p[i], q[i]) for offsets[j] <= i < offsets[j+1]])  for j < m
+ * (lib.rs:615-623, mod.rs:904-926 per product): many independent products in one call, the
+ * shape of a batch of Groth16 / PLONK verifications or of ecPairing calls.
+ * offsets is HOST memory in both forms: m + 1 entries, non-decreasing, offsets[0] == 0, and
+ * n = offsets[m] pairs in p and q.  Anything else is refused with BN_ERR_INVALID_ARGUMENT
+ * before any buffer is read; so is a NULL out, and a NULL p or q when n > 0.  m == 0 returns
+ * BN_OK and touches nothing.
+ * Each product follows pairing_batch: a pair with a zero point is skipped, an empty or
+ * all-skipped product gives Gt::one(), and every out[j] is bit-identical to bn_pairing_batch
+ * on the same slice.  A zero Miller product (no input is known to give one) makes that out[j]
+ * the zero image and the call return BN_ERR_FE_ZERO, with every other row written.
+ * Products of at most 64 terms run one per lane pair of one kernel (k_miller_products, the
+ * shared-squaring loop per product) in launch sets of at most bn_set_products_chunk terms,
+ * followed by one final exponentiation per product; a longer product, and every product of
+ * a call with fewer than bn_set_products_min of the short ones, runs alone as
+ * bn_pairing_batch_dev does.  Results are identical on every path.
+ * The _dev form enqueues on `stream` without synchronizing and reports the data-dependent
+ * outcome through bn_dev_status, as bn_pairing_many_dev does; it reads offsets before it
+ * returns, may wait for the previous call's upload of its offsets (not for its kernels),
+ * and may allocate (and then waits for earlier work) on first use at a larger size.  It is
+ * refused on a multi-device context.
+ * Workspace: a launch set needs room for the larger of its terms and its products.
+ * bn_reserve(n) guarantees that a call whose launch sets each hold at most n terms and at
+ * most n products allocates no workspace (n up to 2^18, the most a launch set takes of
+ * either); the 32-bit offsets buffer (m + 1 words per launch set) is separate, grows on
+ * first use and is not counted by bn_workspace_bytes. */
+int bn_pairing_batch_many(bn_ctx* ctx, const bn_g1* p, const bn_g2* q, const size_t* offsets, size_t m, bn_gt* out);
+int bn_pairing_batch_many_dev(bn_ctx* ctx, const bn_g1* d_p, const bn_g2* d_q, const size_t* offsets, size_t m,
+                              bn_gt* d_out, void* stream);
+/* bn_pairing_batch_many calls with fewer than m products of at most 64 terms run every
+ * product alone; 0 sends every such product down the packed path.  Default: the measured
+ * crossover or $BN254MI_PRODUCTS_MIN.  On a multi-device context it applies
+ * to every device (and to each device's shard). */
+int bn_set_products_min(bn_ctx* ctx, size_t m);
+/* terms per launch set of the packed path (a single product may exceed it); 0 = the default,
+ * 2^18, and more than that is refused with BN_ERR_INVALID_ARGUMENT */
+int bn_set_products_chunk(bn_ctx* ctx, size_t terms);
 
 /* *out = miller_loop_batch(&[(q[i], p[i])]) -- note the (G2, G1) order (lib.rs:625-633,
  * mod.rs:609-640).  No final exponentiation.  BN_ERR_TO_AFFINE if any point is zero. */

@@ -79,6 +79,11 @@ constexpr size_t kPrepareWideMaxDefault = 16384;
 constexpr size_t kMsmMinDefault = 0;
 // the same for bn_g2_msm, read off G2's own sweep
 constexpr size_t kMsmG2MinDefault = 0;
+// bn_pairing_batch_many calls with fewer products (of at most kProductLaneMax terms) than
+// this run each on the single-product path, the others the packed kernel: the measured
+// crossover at 4 terms per product, rounded to a power of two;
+// $BN254MI_PRODUCTS_MIN or bn_set_products_min override
+constexpr size_t kProductsMinDefault = 8;
 
 size_t ws_bytes(size_t n) {
     return n * ((size_t)kCoeffFq * 9 * 4 + kPathLanes * (2 * 9 * 4 + 1) + (size_t)kFeSlots * kSlotWords * 4) + 64;
@@ -934,6 +939,13 @@ int bn_ctx_create(int device, bn_ctx** out) {
     c->msm_g1.min = kMsmMinDefault;
     c->msm_g2.min = kMsmG2MinDefault;
     if (const char* e = getenv("BN254MI_MSM_MIN")) c->msm_g1.min = c->msm_g2.min = (size_t)strtoull(e, nullptr, 10);
+    c->products_min = kProductsMinDefault;
+    if (const char* e = getenv("BN254MI_PRODUCTS_MIN")) c->products_min = (size_t)strtoull(e, nullptr, 10);
+    c->products_chunk = kChunk;
+    if (const char* e = getenv("BN254MI_PRODUCTS_BLOCK")) {
+        const int v = atoi(e);
+        if (v == 128 || v == 256 || v == kPairBlock) c->products_block = (unsigned)v;
+    }
     Prog P;
     c->fe_out = (int)build_final_exp(P);
     P.finalize({(uint32_t)c->fe_out});
@@ -953,6 +965,7 @@ int bn_ctx_create(int device, bn_ctx** out) {
         hipStreamCreateWithFlags(&c->h2d, hipStreamNonBlocking) != hipSuccess ||
         hipStreamCreateWithFlags(&c->d2h, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&c->ws_event, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&c->prod_off_event, hipEventDisableTiming) != hipSuccess ||
         hipMalloc(&c->d_err, sizeof(int)) != hipSuccess || hipMemset(c->d_err, 0, sizeof(int)) != hipSuccess ||
         hipMalloc(&c->tail_ws, kTailWsWords * 4) != hipSuccess || hipMemset(c->tail_ws, 0, kTailWsWords * 4) != hipSuccess ||
         hipMalloc(&c->fe_ds_ws, (size_t)kFeDsMax * kFeDsWords * 4) != hipSuccess ||
@@ -984,6 +997,9 @@ static void ctx_teardown(bn_ctx* c) {
     for (hipStream_t s : {c->h2d, c->d2h})
         if (s) (void)hipStreamSynchronize(s);
     if (c->ws_event) (void)hipEventDestroy(c->ws_event);
+    if (c->prod_off_event) (void)hipEventDestroy(c->prod_off_event);
+    if (c->prod_off_h) (void)hipHostFree(c->prod_off_h);
+    if (c->prod_off_d) (void)hipFree(c->prod_off_d);
     for (hipEvent_t e : {c->ev_in[0], c->ev_in[1], c->ev_comp[0], c->ev_comp[1], c->ev_out[0], c->ev_out[1]})
         if (e) (void)hipEventDestroy(e);
     if (c->pin) (void)hipHostFree(c->pin);
@@ -1422,6 +1438,215 @@ int bn_miller_loop_batch_dev(bn_ctx* c, const bn_g2* d_q, const bn_g1* d_p, size
     CTX_GUARD(c);
     return batch_dev(c, d_p, d_q, n, d_out, d_status, 1, pick(c, stream));
 }
+// ---- many products in one call (bn_pairing_batch_many)
+// One unit of a call's work, products [j0, j1).  packed: one launch set of the packed
+// path -- k_prepare(_wide)_scaled over its terms, k_miller_products (a lane pair per
+// product), the final exponentiation over its products; every product has at most
+// kProductLaneMax terms, together at most products_chunk (a single product may exceed
+// that), and there are at most kChunk products.  Otherwise j1 == j0 + 1: one product on
+// the single-product path (miller_product_dev in mode 0, as bn_pairing_batch_dev).
+struct ProductsItem {
+    size_t j0, j1;
+    bool packed;
+};
+static std::vector<ProductsItem> products_plan(const bn_ctx* c, const size_t* off, size_t m) {
+    size_t nshort = 0;
+    for (size_t j = 0; j < m; ++j) nshort += off[j + 1] - off[j] <= (size_t)kProductLaneMax ? 1 : 0;
+    // fewer short products than products_min: each alone (a lone two-lane chain takes
+    // milliseconds where the single-product path's 16-lane groups take 0.8 ms)
+    const bool pack = nshort > 0 && nshort >= c->products_min;
+    std::vector<ProductsItem> items;
+    for (size_t j = 0; j < m;) {
+        if (!pack || off[j + 1] - off[j] > (size_t)kProductLaneMax) {
+            items.push_back({j, j + 1, false});
+            ++j;
+            continue;
+        }
+        size_t e = j + 1;
+        while (e < m && e - j < kChunk && off[e + 1] - off[e] <= (size_t)kProductLaneMax &&
+               off[e + 1] - off[j] <= c->products_chunk)
+            ++e;
+        items.push_back({j, e, true});
+        j = e;
+    }
+    return items;
+}
+// offsets: m + 1 host entries, non-decreasing from 0; then the buffers (n = offsets[m])
+static int products_check(bn_ctx* c, const void* p, const void* q, const size_t* off, size_t m, const void* out) {
+    if (!off) return fail(c, BN_ERR_INVALID_ARGUMENT, "null offsets");
+    if (off[0] != 0) return fail(c, BN_ERR_INVALID_ARGUMENT, "offsets[0] must be 0");
+    for (size_t j = 0; j < m; ++j)
+        if (off[j + 1] < off[j]) return fail(c, BN_ERR_INVALID_ARGUMENT, "offsets must not decrease");
+    if (!out || (off[m] && (!p || !q))) return fail(c, BN_ERR_INVALID_ARGUMENT, "null buffer");
+    return BN_OK;
+}
+// the workspace for every item of the call: the larger of a launch set's terms (coeffs,
+// flags) and products (slots); a lone product's chunk
+static int products_reserve(bn_ctx* c, const size_t* off, const std::vector<ProductsItem>& items) {
+    size_t need = 1;
+    for (const ProductsItem& it : items) {
+        const size_t nt = off[it.j1] - off[it.j0];
+        need = std::max(need, it.packed ? std::max(nt, it.j1 - it.j0) : std::min(nt, kChunk));
+    }
+    return reserve(c, need);
+}
+// The chunk-relative 32-bit offsets of every launch set of the call (set k: j1 - j0 + 1
+// words from at[k]) -> prod_off_d, in one copy on s in front of the call's kernels.  The
+// pinned source is rewritten by the next call, which first waits for this copy (not for
+// the kernels behind it).  The caller has ordered s after the workspace's previous user.
+static int products_offsets_upload(bn_ctx* c, const size_t* off, const std::vector<ProductsItem>& items,
+                                   hipStream_t s, std::vector<size_t>* at) {
+    size_t words = 0;
+    at->assign(items.size(), 0);
+    for (size_t k = 0; k < items.size(); ++k)
+        if (items[k].packed) {
+            (*at)[k] = words;
+            words += items[k].j1 - items[k].j0 + 1;
+        }
+    if (!words) return BN_OK;
+    if (c->prod_off_pending) {
+        HIPCHK(c, hipEventSynchronize(c->prod_off_event));
+        c->prod_off_pending = false;
+    }
+    if (words > c->prod_off_cap) {
+        RET_IF(ws_drain(c));  // queued kernels may still read the old buffer
+        if (c->prod_off_h) HIPCHK(c, hipHostFree(c->prod_off_h));
+        if (c->prod_off_d) HIPCHK(c, hipFree(c->prod_off_d));
+        c->prod_off_h = nullptr; c->prod_off_d = nullptr; c->prod_off_cap = 0;
+        const size_t cap = std::max<size_t>(words, 4096);
+        HIPCHK(c, hipHostMalloc(&c->prod_off_h, cap * 4, hipHostMallocDefault));
+        HIPCHK(c, hipMalloc(&c->prod_off_d, cap * 4));
+        c->prod_off_cap = cap;
+    }
+    for (size_t k = 0; k < items.size(); ++k)
+        if (items[k].packed)
+            for (size_t j = items[k].j0; j <= items[k].j1; ++j)
+                c->prod_off_h[(*at)[k] + (j - items[k].j0)] = (uint32_t)(off[j] - off[items[k].j0]);
+    HIPCHK(c, hipMemcpyAsync(c->prod_off_d, c->prod_off_h, words * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipEventRecord(c->prod_off_event, s));
+    c->prod_off_pending = true;
+    return BN_OK;
+}
+// Threads per block of k_miller_products.  A launch set of fewer lane pairs than fill the
+// GPU with kPairBlock-thread blocks leaves whole CUs idle while the busy ones run two waves
+// per SIMD, each at about half the lone-wave rate: smaller blocks spread the same waves
+// over more SIMDs.  $BN254MI_PRODUCTS_BLOCK (128, 256 or 512) forces one size (A/B).
+static unsigned products_block(const bn_ctx* c, size_t lanes) {
+    if (c->products_block) return c->products_block;
+    const size_t cus = c->lat_w1_max / kLatPairs;  // the device's CU count (bn_ctx_create)
+    if (lanes >= cus * kPairBlock) return kPairBlock;
+    return lanes >= cus * 256 ? 256 : 128;
+}
+// one launch set: the nt device pairs at d_p / d_q, mc products cut by d_off (mc + 1
+// device words) -> d_out[0 .. mc)
+static int products_set_dev(bn_ctx* c, const bn_g1* d_p, const bn_g2* d_q, size_t nt, const uint32_t* d_off, size_t mc,
+                            bn_gt* d_out, hipStream_t s) {
+    if (nt > c->cap || mc > c->cap) return fail(c, BN_ERR_INTERNAL, "launch set exceeds the workspace");
+    // only Gt leaves: the producers on scaled inputs (no pair at all: nothing to prepare)
+    if (nt) RET_IF(prepare(c, d_p, d_q, nt, 0, s, 1, true));
+    const size_t lanes = kPathLanes * mc;
+    const unsigned block = products_block(c, lanes);
+    k_miller_products<<<(unsigned)((lanes + block - 1) / block), block, 0, s>>>(c->coeffs, c->flags, nt, d_off, mc,
+                                                                               c->slots);
+    HIPCHK(c, hipGetLastError());
+    return run_fe(c, c->slots, mc, nullptr, d_out, nullptr, s);
+}
+static const bn_gt kGtOneImage = {{{{0xd35d438dc58f0d9dull, 0x0a78eb28f5c70b3dull, 0x666ea36f7879462cull,
+                                     0x0e0a77c19a07df2full}}}};  // read-only: no thread ever writes it
+static int products_dev(bn_ctx* c, const bn_g1* d_p, const bn_g2* d_q, const size_t* off, size_t m, bn_gt* d_out,
+                        hipStream_t s) {
+    const std::vector<ProductsItem> items = products_plan(c, off, m);
+    RET_IF(products_reserve(c, off, items));
+    RET_IF(ws_acquire(c, s));
+    WsUse use{c, s};
+    std::vector<size_t> at;
+    RET_IF(products_offsets_upload(c, off, items, s, &at));
+    for (size_t k = 0; k < items.size(); ++k) {
+        const ProductsItem& it = items[k];
+        const size_t lo = off[it.j0], nt = off[it.j1] - lo;
+        if (it.packed)
+            RET_IF(products_set_dev(c, d_p + lo, d_q + lo, nt, c->prod_off_d + at[k], it.j1 - it.j0, d_out + it.j0, s));
+        else if (nt == 0)  // mod.rs:922-924
+            HIPCHK(c, hipMemcpyAsync(d_out + it.j0, &kGtOneImage, sizeof(bn_gt), hipMemcpyHostToDevice, s));
+        else
+            RET_IF(miller_product_dev(c, d_p + lo, d_q + lo, nt, 0, d_out + it.j0, s));
+    }
+    return BN_OK;
+}
+int bn_pairing_batch_many_dev(bn_ctx* c, const bn_g1* d_p, const bn_g2* d_q, const size_t* offsets, size_t m,
+                              bn_gt* d_out, void* stream) {
+    CTX_GUARD(c);
+    if (m == 0) return BN_OK;
+    RET_IF(products_check(c, d_p, d_q, offsets, m, d_out));
+    return products_dev(c, d_p, d_q, offsets, m, d_out, pick(c, stream));
+}
+// The host form: every item staged in turn through the context's stage (its pairs, then
+// its products' Gt), the device outcome read after each (batch_host clears the word for
+// its own product), BN_ERR_FE_ZERO reported at the end with every row written.
+static int products_host(bn_ctx* c, const bn_g1* p, const bn_g2* q, const size_t* off, size_t m, bn_gt* out) {
+    const std::vector<ProductsItem> items = products_plan(c, off, m);
+    RET_IF(products_reserve(c, off, items));
+    std::vector<size_t> at;
+    RET_IF(products_offsets_upload(c, off, items, c->stream, &at));
+    bool zero = false;
+    for (size_t k = 0; k < items.size(); ++k) {
+        const ProductsItem& it = items[k];
+        const size_t lo = off[it.j0], nt = off[it.j1] - lo, mc = it.j1 - it.j0;
+        if (!it.packed) {
+            if (nt == 0) {  // mod.rs:922-924
+                gt_one(out + it.j0);
+                continue;
+            }
+            const int rc = batch_host(c, p + lo, q + lo, nt, 0, true, out + it.j0);
+            if (rc == BN_ERR_FE_ZERO) zero = true;
+            else if (rc) return rc;
+            continue;
+        }
+        RET_IF(clear_err(c, c->stream));
+        RET_IF(stage(c, nt * (sizeof(bn_g1) + sizeof(bn_g2)) + mc * sizeof(bn_gt)));
+        bn_g1* dp = (bn_g1*)c->stage;
+        bn_g2* dq = (bn_g2*)(dp + nt);
+        bn_gt* d = (bn_gt*)(dq + nt);
+        if (nt) {
+            HIPCHK(c, hipMemcpyAsync(dp, p + lo, nt * sizeof(bn_g1), hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(dq, q + lo, nt * sizeof(bn_g2), hipMemcpyHostToDevice, c->stream));
+        }
+        RET_IF(products_set_dev(c, dp, dq, nt, c->prod_off_d + at[k], mc, d, c->stream));
+        HIPCHK(c, hipMemcpyAsync(out + it.j0, d, mc * sizeof(bn_gt), hipMemcpyDeviceToHost, c->stream));
+        int bits = 0;
+        RET_IF(check_err(c, c->stream, &bits));  // synchronizes: the stage is reused
+        if (bits & (1 << BN_ERR_FE_ZERO)) zero = true;
+    }
+    if (zero) return fail(c, BN_ERR_FE_ZERO, "miller loop cannot produce zero");
+    return BN_OK;
+}
+int bn_pairing_batch_many(bn_ctx* c, const bn_g1* p, const bn_g2* q, const size_t* offsets, size_t m, bn_gt* out) {
+    if (c && !c->subs.empty()) return bn_multi_pairing_batch_many(c, p, q, offsets, m, out);
+    CTX_GUARD_HOST(c);
+    if (m == 0) return BN_OK;
+    RET_IF(products_check(c, p, q, offsets, m, out));
+    return products_host(c, p, q, offsets, m, out);
+}
+int bn_set_products_min(bn_ctx* c, size_t m) {
+    if (c && !c->subs.empty()) {
+        for (bn_ctx* d : c->subs) RET_IF(bn_set_products_min(d, m));
+        return BN_OK;
+    }
+    CTX_GUARD(c);
+    c->products_min = m;
+    return BN_OK;
+}
+int bn_set_products_chunk(bn_ctx* c, size_t terms) {
+    if (c && !c->subs.empty()) {
+        for (bn_ctx* d : c->subs) RET_IF(bn_set_products_chunk(d, terms));
+        return BN_OK;
+    }
+    CTX_GUARD(c);
+    if (terms > kChunk) return fail(c, BN_ERR_INVALID_ARGUMENT, "at most kChunk terms per launch set");
+    c->products_chunk = terms ? terms : kChunk;
+    return BN_OK;
+}
+
 int bn_set_latency_max(bn_ctx* c, size_t n) {
     if (c && !c->subs.empty()) {
         for (bn_ctx* d : c->subs) RET_IF(bn_set_latency_max(d, n));

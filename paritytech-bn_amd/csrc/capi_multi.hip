@@ -274,6 +274,46 @@ int bn_multi_g2_msm(bn_ctx* c, const bn_g2* p, const bn_fr* k_, size_t n, bn_g2*
     return BN_OK;
 }
 
+// bn_pairing_batch_many: whole products per device, balanced by terms -- device k takes
+// products [lo_k, lo_(k+1)), lo_k the first product whose offset is >= k * n / D (lo_0 = 0,
+// lo_D = m) -- each shard with its offsets rebased to its first pair, writing its own rows
+// of `out`.  The offsets are checked here, for the whole call, before any shard runs.
+int bn_multi_pairing_batch_many(bn_ctx* c, const bn_g1* p, const bn_g2* q, const size_t* off, size_t m, bn_gt* out) {
+    if (m == 0) return BN_OK;
+    if (!off) return mfail(c, BN_ERR_INVALID_ARGUMENT, "null offsets");
+    if (off[0] != 0) return mfail(c, BN_ERR_INVALID_ARGUMENT, "offsets[0] must be 0");
+    for (size_t j = 0; j < m; ++j)
+        if (off[j + 1] < off[j]) return mfail(c, BN_ERR_INVALID_ARGUMENT, "offsets must not decrease");
+    const size_t n = off[m];
+    if (!out || (n && (!p || !q))) return mfail(c, BN_ERR_INVALID_ARGUMENT, "null buffer");
+    const size_t d = c->subs.size();
+    std::vector<size_t> lo(d + 1, m);
+    lo[0] = 0;
+    for (size_t k = 1, j = 0; k < d; ++k) {
+        size_t at, unused;
+        shard(n, d, k, &at, &unused);
+        while (j < m && off[j] < at) ++j;
+        lo[k] = j;
+    }
+    std::vector<int> rc(d, BN_OK);
+    std::vector<std::thread> th;
+    for (size_t k = 0; k < d; ++k) {
+        if (lo[k + 1] <= lo[k]) continue;
+        th.emplace_back([&, k] {
+            const size_t j0 = lo[k], mk = lo[k + 1] - j0, base = off[j0];
+            std::vector<size_t> rel(mk + 1);
+            for (size_t j = 0; j <= mk; ++j) rel[j] = off[j0 + j] - base;
+            rc[k] = bn_pairing_batch_many(c->subs[k], p + base, q + base, rel.data(), mk, out + j0);
+        });
+    }
+    for (auto& t : th) t.join();
+    // a zero Miller value on one device (BN_ERR_FE_ZERO, its row zero) does not stop the others
+    for (size_t k = 0; k < d; ++k)
+        if (rc[k] != BN_OK)
+            return mfail(c, rc[k], "device " + std::to_string(c->devices[k]) + ": " + bn_last_error(c->subs[k]));
+    return BN_OK;
+}
+
 // per-device Miller products of the shards, multiplied on device 0 in device order
 static int multi_miller_product(bn_ctx* c, const bn_g1* p, const bn_g2* q, size_t n, int mode, bn_gt* result,
                                 bool* any) {

@@ -108,6 +108,20 @@ struct bn_ctx {
     size_t msm_keys_cap = 0, msm_sorted_cap = 0;
     MsmGroupWs<bn_g1> msm_g1;
     MsmGroupWs<bn_g2> msm_g2;
+    // bn_pairing_batch_many (capi.hip): calls with fewer than products_min products of at
+    // most kProductLaneMax terms run each on the single-product path; the packed path
+    // takes at most products_chunk terms per launch set.  Its chunk-relative 32-bit
+    // offsets go up through prod_off_h (pinned) into prod_off_d, one upload per call in
+    // front of its kernels; prod_off_event marks that upload done, and the next call
+    // waits for it before it rewrites prod_off_h.
+    size_t products_min = 0;
+    size_t products_chunk = 0;
+    unsigned products_block = 0;  // threads per block of k_miller_products; 0: by the launch set's size
+    uint32_t* prod_off_h = nullptr;
+    uint32_t* prod_off_d = nullptr;
+    size_t prod_off_cap = 0;  // words
+    hipEvent_t prod_off_event = nullptr;
+    bool prod_off_pending = false;
     // multi-device context (bn_ctx_create_multi): one single-device sub-context
     // per listed device; `device` is -1 and the fields above are unused
     std::vector<bn_ctx*> subs;
@@ -129,6 +143,8 @@ BN_HIDDEN int bn_multi_g1_mul_many(bn_ctx* c, const bn_g1* p, const bn_fr* k, si
 BN_HIDDEN int bn_multi_g2_mul_many(bn_ctx* c, const bn_g2* p, const bn_fr* k, size_t n, bn_g2* out);
 BN_HIDDEN int bn_multi_g1_msm(bn_ctx* c, const bn_g1* p, const bn_fr* k, size_t n, bn_g1* out);
 BN_HIDDEN int bn_multi_g2_msm(bn_ctx* c, const bn_g2* p, const bn_fr* k, size_t n, bn_g2* out);
+BN_HIDDEN int bn_multi_pairing_batch_many(bn_ctx* c, const bn_g1* p, const bn_g2* q, const size_t* offsets, size_t m,
+                                          bn_gt* out);
 BN_HIDDEN int bn_multi_destroy(bn_ctx* c);
 // capi.hip internals used by capi_multi.hip
 BN_HIDDEN int bn_internal_miller_product(bn_ctx* c, const bn_g1* p, const bn_g2* q, size_t n, int mode, bn_gt* result);

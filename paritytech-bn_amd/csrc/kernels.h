@@ -538,6 +538,14 @@ __global__ void __launch_bounds__(kPairBlock) k_miller_seg(const uint32_t* __res
                                                        const uint32_t* __restrict__ paff,
                                                        const uint8_t* __restrict__ flags, size_t n, SegPlan plan,
                                                        uint32_t* __restrict__ out);
+// One whole product per lane pair (bn_pairing_batch_many): product j < m is the pairs
+// off[j] .. off[j + 1] - 1 (at most kProductLaneMax of them, pairing.h) of the n whose
+// prescaled lines are in coeffs; its Miller value goes to element j of `out` (split
+// layout, stride m).  off: m + 1 device words, non-decreasing from 0 to n.
+__global__ void __launch_bounds__(kPairBlock) k_miller_products(const uint32_t* __restrict__ coeffs,
+                                                            const uint8_t* __restrict__ flags, size_t n,
+                                                            const uint32_t* __restrict__ off, size_t m,
+                                                            uint32_t* __restrict__ out);
 // out[e] = Horner recombination of element e's S segment values (element s * n + e of g,
 // split layout, stride S * n): x = g0; x = x^(2^len_s) * g_s; then the final
 // exponentiation when do_fe

@@ -444,6 +444,62 @@ __global__ void BN_PATH_ATTR __launch_bounds__(kPairBlock) k_miller_seg(const ui
     SEG_STAMP(1, __builtin_amdgcn_s_memrealtime());
 }
 
+// Many products in one launch (bn_pairing_batch_many): lane pair j owns product j of the
+// m in the chunk -- the pairs off[j] .. off[j + 1] - 1 of the chunk's n, whose lines
+// k_prepare(_wide)_scaled left in `coeffs` -- and runs its whole shared-squaring loop
+// (pairing.h miller_product_scaled: 64 digits and the closing lines from f = one, one
+// squaring per digit, then the line of each of its pairs).  The value goes to element j
+// of `out` (split layout, stride m): slot 0 of the final exponentiation that follows.
+// The pair loop is wave-uniform: every lane pair of a wave iterates to the largest
+// product of the wave (Kw, from the wave's own 32 offsets), and past its own count it
+// multiplies by the line one, as it does for a pair with a zero point (flags): f is
+// unchanged.  Such a lane pair still loads, from a clamped in-range pair, and discards
+// what it loaded.  An empty product and one whose every pair is zero stay at one.
+// The coefficient loads of neighbouring lane pairs are strided by the product size, so
+// they are not coalesced.
+// Products of more than kProductLaneMax terms do not come here (the balance positions
+// hold t < 64; capi.hip routes them to the single-product path).
+// Launched with kPairBlock threads per block (kernels.h: issue balance) once the lane
+// pairs fill the GPU that way, with 256 or 128 below that (capi.hip products_block).
+__global__ void BN_PATH_ATTR __launch_bounds__(kPairBlock) k_miller_products(const uint32_t* __restrict__ coeffs,
+                                                                            const uint8_t* __restrict__ flags, size_t n,
+                                                                            const uint32_t* __restrict__ off, size_t m,
+                                                                            uint32_t* __restrict__ out) {
+    static_assert(BN_LINES_PRESCALED, "k_miller_products takes the lines as the loop multiplies by them");
+    fold_table_init();
+    const Balance bal = balance_init();
+    const size_t l = lane_id(), j = l / kL, c = l % kL, nl = kL * n;
+    if (j >= m) return;
+    // the largest product among this wave's lane pairs (uniform: the wave's first product
+    // and the count of those below m)
+    const size_t j0 = (size_t)__builtin_amdgcn_readfirstlane((uint32_t)(l / 64)) * (64 / kL);
+    const size_t jn = m - j0 < (size_t)(64 / kL) ? m - j0 : (size_t)(64 / kL);
+    uint32_t Kw = 0;
+#pragma unroll 1  // (a prologue of scalar loads: nothing to gain from unrolling it)
+    for (size_t u = 0; u < jn; ++u) {
+        const uint32_t k = off[j0 + u + 1] - off[j0 + u];
+        Kw = k > Kw ? k : Kw;
+    }
+    const size_t lo = off[j], K = off[j + 1] - lo;
+    const Fq12<kF> f = miller_product_scaled(
+        (int)Kw,
+        [&](int t, int k) {
+            // past this product's own pairs: the chunk's nearest pair (Kw > 0, so n > 0)
+            const size_t pair = (size_t)t < K ? lo + (size_t)t : (lo + (size_t)t < n ? lo + (size_t)t : n - 1);
+            const size_t lt = pair * kL + c;  // the pair's lane in the per-pair arrays
+            const bool live = (size_t)t < K && !flags[lt];
+            mem_fence();  // load right before use: the pairs' lines are never held at once
+            // the line one by selects on the digits (assigned whole from an Ell held outside the
+            // lambda, that Ell became a stack object: 112 B of scratch)
+            const Fq2<kLine> one = widen<kLine>(fq2_one()), zero = widen<kLine>(fq2_zero());
+            return Ell{fq2_select(live, ld_fq2<kLine>(coeffs, nl, lt, k * 6 + 0), one),
+                       fq2_select(live, ld_fq2<kLine>(coeffs, nl, lt, k * 6 + 2), zero),
+                       fq2_select(live, ld_fq2<kLine>(coeffs, nl, lt, k * 6 + 4), zero)};
+        },
+        [&](uint32_t pos) { balance_step(bal, pos); });
+    st_fq12(out, kL * m, l, f);
+}
+
 // G2 * Fr (mod.rs:272-292) on the pairing path's two-lane layout: the chain of
 // curve.h jac_mul with lane 2i + c holding coordinate c of element i, so a batch
 // is twice the waves of a one-lane kernel (rounds 1-3) and each lane holds half the state.

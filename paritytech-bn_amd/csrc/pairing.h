@@ -170,6 +170,51 @@ BN_INLINE Fq12<kF> miller_loop_scaled(Line&& line) {
     return f;
 }
 
+// The shared-squaring loop of ONE product of pairs (mod.rs:609-640) over lines already
+// scaled by P: all 64 digits and the two closing lines from f = one, per digit one
+// squaring of the accumulator and then the line of each pair (kernels_pairing.hip
+// k_miller_products; compiled for the host by tests/native/products_emul.cpp).
+// `line(t, k)` returns line k (0 .. 86) of pair t < K.  K is the number of pairs the loop
+// runs over, which may exceed the product's own: the callable then returns the line one
+// (ell_0 = 1, ell_vw = ell_vv = 0) for the pairs past it, and for a pair with a zero
+// point -- the sparse product by it is f itself, so the value is that of the live pairs
+// alone, and one when there is none (K == 0 included).  The first line goes through
+// line_from_one_scaled whichever it is (the line one gives one).
+// `step(pos)` runs at every digit (pos = digit * 256) and line (+ 1 + pass * 64 + t): the
+// kernels' issue balance (kernels.h), whose positions hold t < 64.
+// So one lane pair takes products of at most kProductLaneMax terms: a larger t would run
+// into the next pass's positions, and the positions must not decrease.
+constexpr int kProductLaneMax = 64;
+struct NoPosStep {
+    BN_INLINE void operator()(uint32_t) const {}
+};
+template <typename Line, typename Step = NoPosStep>
+BN_INLINE Fq12<kF> miller_product_scaled(int K, Line&& line, Step&& step = Step{}) {
+    Fq12<kF> f = widen<kF>(fq12_one());
+    int idx = 0;
+#pragma unroll 1
+    for (int i = 0; i < BN_NAF_DIGITS + 2; ++i) {
+        const uint32_t dpos = (uint32_t)i << 8;
+        step(dpos);
+        const bool closing = i >= BN_NAF_DIGITS;  // the two lines after the loop: no squaring
+        if (!closing && i > 0) f = narrow12<kF>(fq12_sqr(f));
+        const int passes = closing ? 1 : 1 + (int)((kNafNonzero >> i) & 1u);
+#pragma unroll 1
+        for (int ps = 0; ps < passes; ++ps, ++idx) {
+#pragma unroll 1
+            for (int t = 0; t < K; ++t) {
+                step(dpos + 1u + ((uint32_t)ps << 6) + (uint32_t)t);
+                const Ell e = line(t, idx);
+                if (i == 0 && ps == 0 && t == 0)
+                    f = line_from_one_scaled(e);  // one * line (mod.rs:589 on f = one)
+                else
+                    f = apply_line_scaled(f, e);
+            }
+        }
+    }
+    return f;
+}
+
 // The Miller loop with the line steps inline (k_pairing_fused): the
 // coefficients of g2_precompute applied as they are produced, in
 // G2Precomp::miller_loop's order (mod.rs:579-607, 701-727)

@@ -376,6 +376,21 @@ def pairing_batch(pairs):
     return Gt(context().pairing_batch(p, q))
 
 
+def pairing_batch_many(products):
+    """[pairing_batch(pairs) for pairs in products] in one engine call (bn_pairing_batch_many).
+    products: a sequence of sequences of (G1, G2); an empty product gives Gt.one(); no
+    products give [] without a device call."""
+    products = [list(pairs) for pairs in products]
+    if not products:
+        return []
+    offsets = np.zeros(len(products) + 1, np.uintp)
+    offsets[1:] = np.cumsum([len(pairs) for pairs in products])
+    flat = [pair for pairs in products for pair in pairs]
+    p = np.stack([a.img for a, _ in flat]) if flat else np.zeros((0, 12), np.uint64)
+    q = np.stack([b.img for _, b in flat]) if flat else np.zeros((0, 24), np.uint64)
+    return [Gt(row) for row in context().pairing_batch_many(p, q, offsets)]
+
+
 def miller_loop_batch(pairs):
     pairs = list(pairs)
     q = np.stack([a.img for a, _ in pairs]) if pairs else np.zeros((0, 24), np.uint64)

@@ -39,6 +39,7 @@ EXPORTS = [
     "bn_set_latency_max", "bn_dev_status", "bn_set_fq12_op_unit",
     "bn_g1_msm", "bn_g1_msm_dev", "bn_set_msm_window", "bn_set_msm_min", "bn_msm_reserve",
     "bn_g2_msm", "bn_g2_msm_dev", "bn_g2_msm_reserve",
+    "bn_pairing_batch_many", "bn_pairing_batch_many_dev", "bn_set_products_min", "bn_set_products_chunk",
 ] + ["bn_%s_%s_many%s" % (g, op, dev) for g in ("g1", "g2") for op in ("add", "sub", "neg", "normalize", "eq")
      for dev in ("", "_dev")]
 GROUP_OPS = ("add", "sub", "neg", "normalize", "eq")
@@ -131,6 +132,10 @@ def load():
         "bn_g2_msm": ([vp, vp, vp, sz, vp], i),
         "bn_g2_msm_dev": ([vp, vp, vp, sz, vp, vp], i),
         "bn_g2_msm_reserve": ([vp, sz], i),
+        "bn_pairing_batch_many": ([vp, vp, vp, vp, sz, vp], i),
+        "bn_pairing_batch_many_dev": ([vp, vp, vp, vp, sz, vp, vp], i),
+        "bn_set_products_min": ([vp, sz], i),
+        "bn_set_products_chunk": ([vp, sz], i),
     }
     for g in ("g1", "g2"):
         for op in GROUP_OPS:
@@ -167,6 +172,27 @@ def _same_rows(*arrays):
         if a.shape[0] != n:
             raise ValueError("paired inputs have %d and %d rows" % (n, a.shape[0]))
     return n
+
+
+def _offsets(offsets, n=None):
+    """The m + 1 product offsets as a contiguous size_t array: non-decreasing from 0, and
+    ending at n when the row count is known.  Anything else raises ValueError before any
+    native call (the C ABI refuses it too)."""
+    raw = np.asarray(offsets)
+    if raw.ndim != 1 or raw.size == 0:
+        raise ValueError("offsets must be a one-dimensional sequence of m + 1 entries")
+    if raw.dtype.kind not in "iu":
+        raise ValueError("offsets must be integers")
+    if raw.dtype.kind == "i" and (raw < 0).any():
+        raise ValueError("offsets must not be negative")
+    off = np.ascontiguousarray(raw, dtype=np.uintp)
+    if off[0] != 0:
+        raise ValueError("offsets[0] must be 0, not %d" % int(off[0]))
+    if (off[1:] < off[:-1]).any():
+        raise ValueError("offsets must not decrease")
+    if n is not None and int(off[-1]) != n:
+        raise ValueError("offsets end at %d but there are %d pairs" % (int(off[-1]), n))
+    return off
 
 
 def shard_range(n, ndev, k):
@@ -286,6 +312,17 @@ class Context:
         self._check(self._L.bn_pairing_batch(self._h, _ptr(p), _ptr(q), p.shape[0], _ptr(out)))
         return out
 
+    def pairing_batch_many(self, p, q, offsets):
+        """bn_pairing_batch_many: row j of the (m, 48) result is pairing_batch of the pairs
+        offsets[j] <= i < offsets[j + 1].  offsets: m + 1 entries, non-decreasing from 0 to
+        the number of pairs (ValueError otherwise)."""
+        p, q = _arr(p, 12), _arr(q, 24)
+        off = _offsets(offsets, _same_rows(p, q))
+        m = off.shape[0] - 1
+        out = np.zeros((m, 48), np.uint64)
+        self._check(self._L.bn_pairing_batch_many(self._h, _ptr(p), _ptr(q), _ptr(off), m, _ptr(out)))
+        return out
+
     def miller_loop_batch(self, q, p):
         q, p = _arr(q, 24), _arr(p, 12)
         _same_rows(q, p)
@@ -396,6 +433,23 @@ class Context:
 
     def miller_loop_batch_dev(self, d_q, d_p, n, d_out, d_status=None, stream=None):
         self._check(self._L.bn_miller_loop_batch_dev(self._h, d_q, d_p, n, d_out, d_status, stream))
+
+    def pairing_batch_many_dev(self, d_p, d_q, offsets, d_out, stream=None):
+        """bn_pairing_batch_many_dev: d_p, d_q, d_out are device addresses, offsets a HOST
+        sequence of m + 1 entries (checked as in pairing_batch_many); the outcome is read
+        with dev_status()."""
+        off = _offsets(offsets)
+        self._check(self._L.bn_pairing_batch_many_dev(self._h, d_p, d_q, _ptr(off), off.shape[0] - 1, d_out, stream))
+
+    def set_products_min(self, m):
+        """pairing_batch_many calls with fewer than m products of at most 64 terms run each
+        product on the single-product path; 0: always the packed kernel."""
+        self._check(self._L.bn_set_products_min(self._h, m))
+
+    def set_products_chunk(self, terms):
+        """Terms per launch set of the packed path; 0: the default (2^18), which is also the
+        largest value accepted."""
+        self._check(self._L.bn_set_products_chunk(self._h, terms))
 
     def set_fe_wide_max(self, n):
         """Batches of at most n elements use the 16-lane final exponentiation (latency path)."""

@@ -1,0 +1,149 @@
+#!/usr/bin/env python3
+"""Device time of m pairing products of k terms each (n = m * k pairs), three ways, from
+HBM-resident inputs, HIP events on the launch stream, after a warm-up of every shape
+(which also allocates):
+  a  bn_pairing_batch_many_dev, the packed path forced (bn_set_products_min(0))
+  b  m sequential bn_pairing_batch_dev calls, one product each.  Above --sample products
+     only the first --sample are run and the time is scaled by m / sample: an
+     EXTRAPOLATION (the record says "b_extrapolated": true), fair because every call does
+     the same work on the same path
+  c  bn_pairing_many_dev over the same n pairs: n separate pairings, whose Gt the caller
+     would still have to multiply per product
+Before a shape is timed, the rows of (a) must equal those of (b) on the products (b) ran,
+else the script exits non-zero.  One JSON line per shape with the median / min / max of
+each form and terms/s and products/s of the medians; then per k the crossover: the
+smallest m from which (a) stays below (b).
+--forms picks the forms (a library without the new entry point can still run c: the
+baseline of an earlier commit through $BN254MI_LIB)."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "paritytech-bn_amd"))
+sys.path.insert(0, ROOT)
+
+NMAX = 1 << 18
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--ks", default="1,2,4,8")
+    ap.add_argument("--ms", default=",".join(str(1 << e) for e in range(0, 17)))
+    ap.add_argument("--forms", default="a,b,c")
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--sample", type=int, default=32, help="products form b runs at most")
+    ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
+    args = ap.parse_args()
+    import torch
+
+    from substrate_bn import Context, synth
+
+    def emit(rec):
+        line = json.dumps(rec)
+        print(line, flush=True)
+        if args.out:
+            with open(args.out, "a") as fh:
+                fh.write(line + "\n")
+
+    forms = args.forms.split(",")
+    ks = [int(v) for v in args.ks.split(",")]
+    ms = [int(v) for v in args.ms.split(",")]
+    shapes = [(k, m) for k in ks for m in ms if m * k <= NMAX]
+    nmax = max(m * k for k, m in shapes)
+    dev = torch.device("cuda", 0)
+    ctx = Context(0)
+    if "a" in forms:
+        ctx.set_products_min(0)
+    stream = torch.cuda.Stream(dev)
+    sh = stream.cuda_stream
+
+    def up(a):
+        return torch.from_numpy(np.ascontiguousarray(a).view(np.int64)).to(dev)
+
+    # P[i] = s[i] * G1, Q[i] = t[i] * G2 on the device (Jacobian images)
+    s, t = up(synth.fr_images_raw(nmax, 0x70726f31)), up(synth.fr_images_raw(nmax, 0x70726f32))
+    g1 = up(np.tile(synth.g1_one_image(), (nmax, 1)))
+    g2 = up(np.tile(synth.g2_one_image(), (nmax, 1)))
+    P = torch.empty((nmax, 12), dtype=torch.int64, device=dev)
+    Q = torch.empty((nmax, 24), dtype=torch.int64, device=dev)
+    torch.cuda.synchronize(dev)
+    ctx.g1_mul_many_dev(g1.data_ptr(), s.data_ptr(), nmax, P.data_ptr(), sh)
+    ctx.g2_mul_many_dev(g2.data_ptr(), t.data_ptr(), nmax, Q.data_ptr(), sh)
+    torch.cuda.synchronize(dev)
+    del s, t, g1, g2
+    ctx.reserve(min(nmax, NMAX))
+    out_a = torch.zeros((max(ms), 48), dtype=torch.int64, device=dev)
+    out_b = torch.zeros((args.sample, 48), dtype=torch.int64, device=dev)
+    out_c = torch.zeros((nmax, 48), dtype=torch.int64, device=dev)
+    g1_bytes, g2_bytes, gt_bytes = 96, 192, 384
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        with torch.cuda.stream(stream):
+            e0.record()
+            fn()
+            e1.record()
+        torch.cuda.synchronize(dev)
+        return e0.elapsed_time(e1)
+
+    def run(form, k, m):
+        """-> milliseconds for the whole shape (form b: scaled up from its sample)"""
+        n = m * k
+        if form == "a":
+            off = np.arange(m + 1, dtype=np.uintp) * k
+            return timed(lambda: ctx.pairing_batch_many_dev(P.data_ptr(), Q.data_ptr(), off, out_a.data_ptr(), sh))
+        if form == "b":
+            ran = min(m, args.sample)
+
+            def calls():
+                for j in range(ran):
+                    ctx.pairing_batch_dev(P.data_ptr() + j * k * g1_bytes, Q.data_ptr() + j * k * g2_bytes, k,
+                                          out_b.data_ptr() + j * gt_bytes, None, sh)
+            return timed(calls) * m / ran
+        return timed(lambda: ctx.pairing_many_dev(P.data_ptr(), Q.data_ptr(), n, out_c.data_ptr(), sh))
+
+    def stats(ts):
+        return {"median_ms": round(statistics.median(ts), 4), "min_ms": round(min(ts), 4), "max_ms": round(max(ts), 4)}
+
+    cross = {k: None for k in ks}
+    for k, m in shapes:
+        for f in forms:  # warm-up
+            run(f, k, m)
+        ctx.dev_status()
+        if "a" in forms and "b" in forms:
+            ran = min(m, args.sample)
+            if not np.array_equal(out_a[:ran].cpu().numpy(), out_b[:ran].cpu().numpy()):
+                print("MISMATCH at k=%d m=%d: the packed rows differ from bn_pairing_batch_dev's" % (k, m), file=sys.stderr)
+                sys.exit(1)
+        times = {f: [] for f in forms}
+        for _ in range(args.reps):
+            for f in forms:  # alternating
+                times[f].append(run(f, k, m))
+        rec = {"k": k, "m": m, "n": m * k, "reps": args.reps}
+        for f in forms:
+            st = stats(times[f])
+            st["terms_per_s"] = round(m * k / (st["median_ms"] * 1e-3))
+            st["products_per_s"] = round(m / (st["median_ms"] * 1e-3))
+            rec[f] = st
+        if "b" in forms:
+            rec["b_extrapolated"] = m > args.sample
+        if "a" in forms and "b" in forms:
+            if rec["a"]["median_ms"] < rec["b"]["median_ms"]:
+                if cross[k] is None:
+                    cross[k] = m
+            else:
+                cross[k] = None
+        emit(rec)
+    ctx.dev_status()
+    if "a" in forms and "b" in forms:
+        emit({"crossover_m": {str(k): cross[k] for k in ks},
+              "note": "smallest m of the sweep from which the packed path stays below m single-product calls"})
+
+
+if __name__ == "__main__":
+    main()
