@@ -64,7 +64,8 @@ void* bn_ctx_stream(bn_ctx* ctx);
  * bn_pairing_many_allgather_dev): synchronizes `stream` (NULL: the context's stream), returns
  * BN_ERR_INTERNAL or BN_ERR_FE_ZERO (a Miller value was zero: the reference panics, mod.rs:900)
  * if any such call since the last bn_dev_status (or host-buffer call, which starts from a clear
- * word) set it, else BN_OK, and clears it.  On a multi-device context it checks every device,
+ * word) set it, else BN_OK, and clears it.  bn_pairing_prepared_many_dev adds BN_ERR_INVALID_ARGUMENT
+ * (an index past the handle's points), reported after BN_ERR_INTERNAL and before BN_ERR_FE_ZERO.  On a multi-device context it checks every device,
  * each on its own context stream, and `stream` must be NULL (else BN_ERR_INVALID_ARGUMENT). */
 int bn_dev_status(bn_ctx* ctx, void* stream);
 
@@ -173,6 +174,54 @@ int bn_miller_loop_many(bn_ctx* ctx, const bn_g1* p, const bn_g2* q, size_t n, b
  * to_affine: out[(i * 87 + k) * 3 + j] = coefficient k's (ell_0, ell_vw, ell_vv)[j]
  * (G2Precomp / EllCoeffs, mod.rs:566-577).  BN_ERR_TO_AFFINE if a q is zero. */
 int bn_g2_precompute_many(bn_ctx* ctx, const bn_g2* q, size_t n, bn_fq2* out);
+
+/* ---- pairings against prepared G2 points (G2Precomp, mod.rs:566-607, 701-727) ----
+ * Verifiers pair many G1 points against a few fixed G2 points (a verifying key, an SRS element, a
+ * public key).  A bn_g2_prepared handle holds, on the device, the reference's coefficients of
+ * q[j].to_affine().precompute() for j < nq -- the 87 (ell_0, ell_vw, ell_vv) that
+ * bn_g2_precompute_many exports, 18,792 bytes per point -- so the calls below skip the line steps.
+ *   1 <= nq <= 2^16; a NULL q or out, an nq outside that range and a multi-device context are
+ *   refused with BN_ERR_INVALID_ARGUMENT before anything is read (a device context from
+ *   bn_ctx_device works).  A zero q[j] (z == 0) is legal: pairs against it give what pairing(p, zero)
+ *   gives, Gt::one().
+ *   The handle belongs to the context that made it: any other context refuses it with
+ *   BN_ERR_INVALID_ARGUMENT.  bn_g2_prepared_destroy waits for the work that uses the handle, then
+ *   frees it; bn_ctx_destroy frees the handles still alive (they must not be used afterwards).
+ *   The table is the handle's own memory: it is separate from the pairing workspace and not counted
+ *   by bn_workspace_bytes.  Filling it uses the pairing workspace (bn_reserve(nq) pre-sizes that).
+ * The _dev form takes device q and enqueues on `stream` without synchronizing (it allocates the
+ * table, and may grow the workspace and then wait for earlier work, before it enqueues). */
+typedef struct bn_g2_prepared bn_g2_prepared;
+int bn_g2_prepare(bn_ctx* ctx, const bn_g2* q, size_t nq, bn_g2_prepared** out);
+int bn_g2_prepare_dev(bn_ctx* ctx, const bn_g2* d_q, size_t nq, bn_g2_prepared** out, void* stream);
+size_t bn_g2_prepared_count(const bn_g2_prepared* prepared);
+int bn_g2_prepared_destroy(bn_ctx* ctx, bn_g2_prepared* prepared);
+
+/* out[i] = pairing(p[i], Q[qidx[i]]) for i < n, Q the handle's points: bit-identical to
+ * bn_pairing_many with q[i] = Q[qidx[i]].  qidx == NULL means index 0 for every i.  A zero p[i] or a
+ * zero Q[qidx[i]] gives Gt::one(); a zero Miller value the zero image and BN_ERR_FE_ZERO.
+ * n == 0 returns BN_OK and touches nothing.  A NULL p, out or handle with n > 0, a handle of another
+ * context and a multi-device context are refused with BN_ERR_INVALID_ARGUMENT.
+ * Host forms: every qidx[i] < nq is checked before any copy or launch; a bad index is
+ * BN_ERR_INVALID_ARGUMENT with out untouched.
+ * _dev form: d_qidx is device memory and cannot be checked on the host.  The kernel clamps a bad
+ * index (nothing outside the table is read), writes that row as the zero image and sets the sticky
+ * outcome that bn_dev_status reports as BN_ERR_INVALID_ARGUMENT (after BN_ERR_INTERNAL, before
+ * BN_ERR_FE_ZERO); every other row is correct.
+ * Every n takes one throughput kernel (k_pairing_prepared: two lanes per pairing, the lines read
+ * from the table as the loop needs them, then the final exponentiation's step machine) in launch
+ * sets of 2^18 pairs, on the workspace bn_reserve sizes.  There is no latency path: a small batch
+ * costs one throughput launch, the time of a lone lane pair's chain; callers who need small-batch
+ * latency keep bn_pairing_many. */
+int bn_pairing_prepared_many(bn_ctx* ctx, const bn_g1* p, const bn_g2_prepared* prepared, const uint32_t* qidx,
+                             size_t n, bn_gt* out);
+int bn_pairing_prepared_many_dev(bn_ctx* ctx, const bn_g1* d_p, const bn_g2_prepared* prepared,
+                                 const uint32_t* d_qidx, size_t n, bn_gt* d_out, void* stream);
+/* out[i] = G2Precomp::miller_loop (mod.rs:579-607) of Q[qidx[i]] at p[i].to_affine(): bit-identical
+ * to bn_miller_loop_many on the same pairs; a zero p[i] or Q[qidx[i]] gives Fq12::one().  Arguments
+ * as for bn_pairing_prepared_many. */
+int bn_miller_loop_prepared_many(bn_ctx* ctx, const bn_g1* p, const bn_g2_prepared* prepared, const uint32_t* qidx,
+                                 size_t n, bn_gt* out);
 
 /* ---- group path (src/groups/mod.rs:250-334, lib.rs:425-431) ---- */
 

@@ -1010,6 +1010,12 @@ static void ctx_teardown(bn_ctx* c) {
                     (void*)c->msm_sorted, (void*)c->msm_g1.buckets, (void*)c->msm_g1.parts, (void*)c->msm_g1.tmp,
                     (void*)c->msm_g2.buckets, (void*)c->msm_g2.parts, (void*)c->msm_g2.tmp})
         if (p) (void)hipFree(p);
+    for (bn_g2_prepared* h : c->prepared) {  // the handles still alive (the streams are drained)
+        if (h->table) (void)hipFree(h->table);
+        if (h->zero) (void)hipFree(h->zero);
+        delete h;
+    }
+    c->prepared.clear();
     for (auto& ev : c->ev_marks)
         for (auto e : ev) c->ev_pool.push_back(e);
     for (auto e : c->ev_pool)
@@ -1173,6 +1179,8 @@ int bn_dev_status(bn_ctx* c, void* stream) {
     RET_IF(clear_err(c, s));
     HIPCHK(c, hipStreamSynchronize(s));
     if (rc) return rc;
+    if (bits & (1 << BN_ERR_INVALID_ARGUMENT))  // bn_pairing_prepared_many_dev: an index past the handle's points
+        return fail(c, BN_ERR_INVALID_ARGUMENT, "a prepared-point index was out of range; that row is zero");
     if (bits & (1 << BN_ERR_FE_ZERO)) return fail(c, BN_ERR_FE_ZERO, "miller loop cannot produce zero");
     return BN_OK;
 }
@@ -1740,6 +1748,180 @@ int bn_g2_precompute_many(bn_ctx* c, const bn_g2* q, size_t n, bn_fq2* out) {
     RET_IF(check_err(c, c->stream, &bits));
     if (bits & (1 << BN_ERR_TO_AFFINE)) return fail(c, BN_ERR_TO_AFFINE, "ToAffineConversion");
     return BN_OK;
+}
+
+// ---------------------------------------------------------------- prepared G2 points
+// Fills a new handle with the coefficients of the nq points at q (host memory, or device
+// memory when q_dev) on stream s: per chunk, k_prepare(_wide) with G1::one() as the G1 side
+// (mode 0: a zero q is flagged, not an error; scale 0: the reference's coefficients, as
+// bn_g2_precompute_many) into the workspace, then k_prepared_repack into the table.  The
+// caller holds the lock and has ordered s after the workspace's previous user.
+static int g2_prepare_fill(bn_ctx* c, bn_g2_prepared* h, const bn_g2* q, bool q_dev, hipStream_t s) {
+    const size_t nq = h->nq;
+    HIPCHK(c, hipMalloc(&h->table, nq * (size_t)kPreparedWords * 4));
+    HIPCHK(c, hipMalloc(&h->zero, nq));
+    const size_t mmax = nq < kChunk ? nq : kChunk;
+    RET_IF(reserve(c, mmax));
+    const size_t o_q = round256(mmax * sizeof(bn_g1));
+    RET_IF(stage(c, o_q + (q_dev ? 0 : mmax * sizeof(bn_g2))));
+    for (size_t off = 0; off < nq; off += kChunk) {
+        const size_t m = (nq - off) < kChunk ? (nq - off) : kChunk;
+        bn_g1* dp = (bn_g1*)c->stage;
+        const bn_g2* dq = q + off;
+        if (!q_dev) {
+            bn_g2* st = (bn_g2*)((uint8_t*)c->stage + o_q);
+            HIPCHK(c, hipMemcpyAsync(st, q + off, m * sizeof(bn_g2), hipMemcpyHostToDevice, s));
+            dq = st;
+        }
+        k_g1_fill_one<<<grid_for(m), kBlock, 0, s>>>(dp, m);
+        RET_IF(prepare(c, dp, dq, m, 0, s, 0));
+        k_prepared_repack<<<grid_for(kPathLanes * m), kBlock, 0, s>>>(c->coeffs, c->flags, m,
+                                                                     h->table + off * (size_t)kPreparedWords,
+                                                                     h->zero + off);
+        HIPCHK(c, hipGetLastError());
+    }
+    return BN_OK;
+}
+static int g2_prepare(bn_ctx* c, const bn_g2* q, bool q_dev, size_t nq, bn_g2_prepared** out, hipStream_t s) {
+    bn_g2_prepared* h = new bn_g2_prepared();
+    h->nq = nq;
+    int rc = g2_prepare_fill(c, h, q, q_dev, s);
+    if (rc == BN_OK && !q_dev && hipStreamSynchronize(s) != hipSuccess) rc = fail(c, BN_ERR_HIP, "hipStreamSynchronize");
+    if (rc != BN_OK) {
+        (void)hipStreamSynchronize(s);  // nothing queued may still write the table
+        if (h->table) (void)hipFree(h->table);
+        if (h->zero) (void)hipFree(h->zero);
+        delete h;
+        return rc;
+    }
+    c->prepared.push_back(h);
+    *out = h;
+    return BN_OK;
+}
+// refused before anything is read: a NULL q or out, nq outside 1 .. 2^16
+static int g2_prepare_args(bn_ctx* c, const void* q, size_t nq, bn_g2_prepared** out) {
+    if (!q || !out) return fail(c, BN_ERR_INVALID_ARGUMENT, "null buffer");
+    if (nq < 1 || nq > kPreparedMax) return fail(c, BN_ERR_INVALID_ARGUMENT, "nq outside 1 .. 2^16");
+    return BN_OK;
+}
+
+int bn_g2_prepare(bn_ctx* c, const bn_g2* q, size_t nq, bn_g2_prepared** out) {
+    if (out) *out = nullptr;
+    CTX_GUARD(c);
+    RET_IF(g2_prepare_args(c, q, nq, out));
+    RET_IF(ws_acquire(c, c->stream));
+    WsUse use{c, c->stream};
+    return g2_prepare(c, q, false, nq, out, c->stream);
+}
+
+int bn_g2_prepare_dev(bn_ctx* c, const bn_g2* d_q, size_t nq, bn_g2_prepared** out, void* stream) {
+    if (out) *out = nullptr;
+    CTX_GUARD(c);
+    RET_IF(g2_prepare_args(c, d_q, nq, out));
+    const hipStream_t s = pick(c, stream);
+    // (the workspace may grow in the fill: reserve() drains the previous users itself)
+    RET_IF(ws_acquire(c, s));
+    WsUse use{c, s};
+    return g2_prepare(c, d_q, true, nq, out, s);
+}
+
+size_t bn_g2_prepared_count(const bn_g2_prepared* h) { return h ? h->nq : 0; }
+
+// a live handle of this context (looked up, not dereferenced: another context's handle,
+// or a destroyed one, is refused)
+static bool prepared_live(const bn_ctx* c, const bn_g2_prepared* h) {
+    return h && std::find(c->prepared.begin(), c->prepared.end(), h) != c->prepared.end();
+}
+
+int bn_g2_prepared_destroy(bn_ctx* c, bn_g2_prepared* h) {
+    CTX_GUARD(c);
+    if (!prepared_live(c, h)) return fail(c, BN_ERR_INVALID_ARGUMENT, "not a live prepared handle of this context");
+    RET_IF(ws_drain(c));  // every call that reads the table has recorded ws_event behind its work
+    c->prepared.erase(std::find(c->prepared.begin(), c->prepared.end(), h));
+    (void)hipFree(h->table);
+    (void)hipFree(h->zero);
+    delete h;
+    return BN_OK;
+}
+
+// n pairings (fe) or Miller values of device arrays against the handle on stream s, every n
+// through k_pairing_prepared in launch sets of kChunk; the caller holds the lock
+static int prepared_dev_impl(bn_ctx* c, const bn_g1* d_p, const bn_g2_prepared* h, const uint32_t* d_qidx, size_t n,
+                             bn_gt* d_out, bool fe, hipStream_t s) {
+    if (fe) {
+        // the kernel returns the step program's last result as the Gt, as k_pairing_full
+        if (!c->fe_last_out) return fail(c, BN_ERR_INTERNAL, "step program does not end in its output");
+        RET_IF(reserve(c, n < kChunk ? n : kChunk));
+    }
+    RET_IF(ws_acquire(c, s));
+    WsUse use{c, s};
+    for (size_t off = 0; off < n; off += kChunk) {
+        const size_t m = (n - off) < kChunk ? (n - off) : kChunk;
+        launch_pairing_prepared(fe, d_p + off, h->table, h->zero, (uint32_t)h->nq, d_qidx ? d_qidx + off : nullptr, m,
+                                c->d_prog, c->fe_steps, c->slots, d_out + off, c->d_err, s);
+        HIPCHK(c, hipGetLastError());
+    }
+    return BN_OK;
+}
+static int prepared_args(bn_ctx* c, const void* p, const bn_g2_prepared* h, const void* out) {
+    if (!p || !out || !h) return fail(c, BN_ERR_INVALID_ARGUMENT, "null buffer");
+    if (!prepared_live(c, h)) return fail(c, BN_ERR_INVALID_ARGUMENT, "not a live prepared handle of this context");
+    return BN_OK;
+}
+// the host forms: indices checked first, then per chunk stage, copy, launch, read back,
+// synchronize (the device bits read per chunk, as bn_pairing_many's pageable form)
+static int prepared_host(bn_ctx* c, const bn_g1* p, const bn_g2_prepared* h, const uint32_t* qidx, size_t n,
+                         bn_gt* out, bool fe) {
+    if (qidx)
+        for (size_t i = 0; i < n; ++i)
+            if (qidx[i] >= h->nq) return fail(c, BN_ERR_INVALID_ARGUMENT, "prepared-point index out of range");
+    for (size_t off = 0; off < n; off += kChunk) {
+        const size_t m = (n - off) < kChunk ? (n - off) : kChunk;
+        const size_t o_idx = round256(m * sizeof(bn_g1));
+        const size_t o_out = o_idx + round256(m * sizeof(uint32_t));
+        RET_IF(stage(c, o_out + m * sizeof(bn_gt)));
+        uint8_t* base = (uint8_t*)c->stage;
+        bn_g1* dp = (bn_g1*)base;
+        uint32_t* didx = (uint32_t*)(base + o_idx);
+        bn_gt* dout = (bn_gt*)(base + o_out);
+        RET_IF(clear_err(c, c->stream));
+        HIPCHK(c, hipMemcpyAsync(dp, p + off, m * sizeof(bn_g1), hipMemcpyHostToDevice, c->stream));
+        if (qidx) HIPCHK(c, hipMemcpyAsync(didx, qidx + off, m * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        RET_IF(prepared_dev_impl(c, dp, h, qidx ? didx : nullptr, m, dout, fe, c->stream));
+        HIPCHK(c, hipMemcpyAsync(out + off, dout, m * sizeof(bn_gt), hipMemcpyDeviceToHost, c->stream));
+        int bits = 0;
+        RET_IF(check_err(c, c->stream, &bits));
+        if (bits & (1 << BN_ERR_FE_ZERO)) return fail(c, BN_ERR_FE_ZERO, "miller loop cannot produce zero");
+    }
+    return BN_OK;
+}
+
+int bn_pairing_prepared_many(bn_ctx* c, const bn_g1* p, const bn_g2_prepared* h, const uint32_t* qidx, size_t n,
+                             bn_gt* out) {
+    CTX_GUARD_HOST(c);
+    if (n == 0) return BN_OK;
+    RET_IF(prepared_args(c, p, h, out));
+    const int rc = prepared_host(c, p, h, qidx, n, out, true);
+    (void)hipStreamSynchronize(c->stream);  // an early error may leave copies queued
+    return rc;
+}
+
+int bn_miller_loop_prepared_many(bn_ctx* c, const bn_g1* p, const bn_g2_prepared* h, const uint32_t* qidx, size_t n,
+                                 bn_gt* out) {
+    CTX_GUARD_HOST(c);
+    if (n == 0) return BN_OK;
+    RET_IF(prepared_args(c, p, h, out));
+    const int rc = prepared_host(c, p, h, qidx, n, out, false);
+    (void)hipStreamSynchronize(c->stream);
+    return rc;
+}
+
+int bn_pairing_prepared_many_dev(bn_ctx* c, const bn_g1* d_p, const bn_g2_prepared* h, const uint32_t* d_qidx,
+                                 size_t n, bn_gt* d_out, void* stream) {
+    CTX_GUARD(c);
+    if (n == 0) return BN_OK;
+    RET_IF(prepared_args(c, d_p, h, d_out));
+    return prepared_dev_impl(c, d_p, h, d_qidx, n, d_out, true, pick(c, stream));
 }
 
 int bn_g1_mul_many_dev(bn_ctx* c, const bn_g1* d_p, const bn_fr* d_k, size_t n, bn_g1* d_out, void* stream) {

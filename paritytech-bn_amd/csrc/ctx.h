@@ -23,6 +23,16 @@ struct MsmGroupWs {
     size_t buckets_cap = 0, parts_cap = 0, tmp_cap = 0;
 };
 
+// bn_g2_prepare's handle: the 87 line coefficients of each of nq affine G2 points
+// (kernels.h kPreparedWords words per point) and a zero flag per point, device-resident,
+// owned by the single-device context whose `prepared` list holds it (which frees the
+// handles still alive when destroyed).
+struct bn_g2_prepared {
+    size_t nq = 0;
+    uint32_t* table = nullptr;
+    uint8_t* zero = nullptr;  // zero[j] != 0: q[j] was G2::zero(), its table row is never used
+};
+
 struct bn_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -122,6 +132,11 @@ struct bn_ctx {
     size_t prod_off_cap = 0;  // words
     hipEvent_t prod_off_event = nullptr;
     bool prod_off_pending = false;
+    // the bn_g2_prepared handles this context made and has not destroyed yet (capi.hip).
+    // Their tables are their own memory, not part of the workspace; the calls that read
+    // them order themselves through ws_event like every workspace user, which is what
+    // bn_g2_prepared_destroy waits for.
+    std::vector<bn_g2_prepared*> prepared;
     // multi-device context (bn_ctx_create_multi): one single-device sub-context
     // per listed device; `device` is -1 and the fields above are unused
     std::vector<bn_ctx*> subs;

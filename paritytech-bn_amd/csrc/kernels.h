@@ -602,6 +602,29 @@ __global__ void __launch_bounds__(kPairBlock) k_pairing_full(const bn_g1* __rest
                                                           size_t n, const uint32_t* __restrict__ prog, int nsteps,
                                                           uint32_t* __restrict__ slots, bn_gt* __restrict__ out,
                                                           int* __restrict__ err);
+// kernels_prepared.hip: pairings against a table of prepared G2 points (bn_g2_prepared).
+// Table layout: [point][line 0..86][ell_0, ell_vw, ell_vv][coordinate c0, c1][9 digits], each
+// coordinate the nine contiguous digits at the kLine bound that ld_fq2<kLine> returns, so
+// lane 2i + c of the split layout reads its own coordinate as one 36-byte run.
+constexpr int kPreparedLineWords = 3 * 2 * 9;
+constexpr int kPreparedWords = BN_NUM_COEFFS * kPreparedLineWords;  // 4,698 words = 18,792 B per point
+constexpr size_t kPreparedMax = size_t(1) << 16;                    // points per handle
+// the G1 side of the fill: out[i] = G1::one() for i < n (k_prepare converts a G1 point too)
+__global__ void __launch_bounds__(kBlock) k_g1_fill_one(bn_g1* __restrict__ out, size_t n);
+// the lines k_prepare(_wide) left in `coeffs` for m pairs (unscaled: scale = 0) and their
+// zero flags -> rows 0 .. m - 1 of `table` / `zero`
+__global__ void __launch_bounds__(kBlock) k_prepared_repack(const uint32_t* __restrict__ coeffs,
+                                                            const uint8_t* __restrict__ flags, size_t m,
+                                                            uint32_t* __restrict__ table, uint8_t* __restrict__ zero);
+// out[i] = pairing (FinalExp) or Miller value of (p[i], point qidx[i] of the table); qidx
+// may be null (index 0).  An index >= nq is clamped, its row is the zero image and
+// BN_ERR_INVALID_ARGUMENT is set in *err.  prog / nsteps / slots: the final exponentiation's
+// step program and slots (FinalExp only), as k_pairing_full.  The kernel is the template
+// k_pairing_prepared<bool FinalExp> of kernels_prepared.hip, instantiated there; this
+// launches it on kPathLanes * n threads in kPairBlock-thread blocks on stream s.
+void launch_pairing_prepared(bool final_exp, const bn_g1* p, const uint32_t* table, const uint8_t* qzero, uint32_t nq,
+                             const uint32_t* qidx, size_t n, const uint32_t* prog, int nsteps, uint32_t* slots,
+                             bn_gt* out, int* err, hipStream_t s);
 __global__ void __launch_bounds__(kBlock) k_fe_out(const uint32_t* __restrict__ slots, size_t n, int out_slot, const uint8_t* __restrict__ flags,
                          bn_gt* __restrict__ out, uint8_t* __restrict__ ok, int* __restrict__ err);
 // kernels_wide.hip (fq12_wide.h): final exponentiation and product reduction on 16-lane groups

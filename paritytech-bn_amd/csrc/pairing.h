@@ -265,6 +265,51 @@ BN_INLINE Fq12<kF> miller_fused(const G2Aff<B>& q, const Fq<PB>& px, const Fq<PB
     return miller_fused(q, px, py, doubling_coeff(), static_cast<Step&&>(step));
 }
 
+// ---------------------------------------------------------------- prepared G2
+// G2Precomp::miller_loop (mod.rs:579-607) over the reference's own coefficients of a
+// fixed Q (AffineG2::precompute, not scaled by any P: what bn_g2_precompute_many exports
+// and a bn_g2_prepared table holds), each line applied as
+//   mul_by_024(ell_0 * s0, ell_vw * sy, ell_vv * sx).
+// Two forms (kernels_prepared.hip k_pairing_prepared; compiled for the host by
+// tests/native/prepared_emul.cpp):
+//   Miller form: s0 = NoScale{} (ell_0 as stored, no product), sy = y_P, sx = x_P of the
+//     affine P -- apply_line's operands, so the value is G2Precomp::miller_loop's.
+//   Gt form: for P = (X, Y, Z) Jacobian, s0 = Z^3, sy = Y, sx = X Z: every line is the
+//     affine line times Z^3, an element of Fq*, so the Miller value is off by a power of
+//     Z, which the final exponentiation sends to one (the argument above scaled_inputs
+//     below, with the factor on the G1 side alone).  No inversion.
+// `line(k)` returns coefficient k (0 .. 86), fetched right before its use; `step(i)` runs
+// at the start of digit i (the kernels' issue balance, kernels.h).
+struct NoScale {};
+BN_INLINE Fq2<kLine> ell_0_scaled(const Fq2<kLine>& e, NoScale) { return e; }
+template <int SB>
+BN_INLINE Fq2<kLine> ell_0_scaled(const Fq2<kLine>& e, const Fq<SB>& s0) {
+    return narrow<kLine>(fq2_scale(e, s0));
+}
+template <typename S0, int PB, typename Line, typename Step = NoStep>
+BN_INLINE Fq12<kF> miller_prepared(Line&& line, const S0& s0, const Fq<PB>& sy, const Fq<PB>& sx,
+                                   Step&& step = Step{}) {
+    // the line as the loop multiplies by it (apply_line's operands)
+    auto at = [&](int k) {
+        const Ell c = line(k);
+        return Ell{ell_0_scaled(c.ell_0, s0), narrow<kLine>(fq2_scale(c.ell_vw, sy)),
+                   narrow<kLine>(fq2_scale(c.ell_vv, sx))};
+    };
+    Fq12<kF> f = widen<kF>(fq12_one());
+    int idx = 0;
+#pragma unroll 1
+    for (int i = 0; i < BN_NAF_DIGITS; ++i) {
+        step(i);
+        const Ell e = at(idx++);
+        // digit 0: one^2 * line is the line itself (line_from_one)
+        f = i == 0 ? line_from_one_scaled(e) : apply_line_scaled(narrow12<kF>(fq12_sqr(f)), e);
+        if ((kNafNonzero >> i) & 1u) f = apply_line_scaled(f, at(idx++));
+    }
+    f = apply_line_scaled(f, at(idx++));
+    f = apply_line_scaled(f, at(idx));
+    return f;
+}
+
 // ---------------------------------------------------------------- scaled inputs
 // Where only Gt leaves a pairing, the Miller loop can run on scaled coordinates instead
 // of affine ones, which takes to_affine's inversion away.  The line steps are
@@ -275,6 +320,10 @@ BN_INLINE Fq12<kF> miller_fused(const G2Aff<B>& q, const Fq<PB>& px, const Fq<PB
 // mixed_addition_step and through mul_by_q, whose constants carry no weight and whose
 // conjugation fixes l.  The Miller value changes by a power of l, an element of Fq*,
 // which the final exponentiation sends to one ((p - 1) divides (p^6 - 1)): the same Gt.
+// (miller_prepared's Gt form above is the case of an affine, fixed Q whose lines are
+// already computed: only the G1 side is scaled, l = Z_P, and since the stored ell_vw and
+// ell_vv multiply y_P = Y / Z^3 and x_P = X / Z^2, the whole line is taken times Z^3:
+// ell_0 Z^3, ell_vw Y, ell_vv X Z.)
 // With l = N(Z_Q) Z_P, N = Z_Q.c0^2 + Z_Q.c1^2, nothing is inverted:
 //   l^2 X_P / Z_P^2 = N^2 X_P,  l^3 Y_P / Z_P^3 = N^3 Y_P,
 //   l / Z_Q = Z_P conj(Z_Q) = m:  l^2 X_Q / Z_Q^2 = m^2 X_Q,  l^3 Y_Q / Z_Q^3 = m^3 Y_Q.

@@ -21,7 +21,9 @@ and the wire formats and validation around it:
 
 plus the batched forms the reference lacks (pairing_many, g1_mul_many, and the
 multi-scalar multiplications g1_msm / g2_msm = sum of points[i] * scalars[i]) that
-the engine exists for.  Values keep the reference's memory images (canonical
+the engine exists for, and pairings against fixed G2 points prepared once (G2Prepared,
+pairing_prepared_many, miller_loop_prepared_many: the reference's G2Precomp held on the
+device).  Values keep the reference's memory images (canonical
 Montgomery, little-endian u64 limbs), so a Gt compares equal exactly when the
 reference's derived PartialEq would.  Every computation runs on the GPU; there
 is no CPU fallback.
@@ -448,6 +450,80 @@ def g2_msm(points, scalars):
     if p.shape[0] == 0:
         return G2.zero()
     return G2(context().g2_msm(p, k))
+
+
+class G2Prepared:
+    """The line coefficients of fixed G2 points held on the device (bn_g2_prepare; the
+    reference's G2Precomp, mod.rs:566-577, per point): what a verifier builds once from its
+    verifying key, SRS element or public keys and then pairs many G1 points against
+    (pairing_prepared_many, miller_loop_prepared_many).  Built from a sequence of G2 (or an
+    (n, 24) image array), 1 .. 65536 of them; zero points are allowed.  len() is the number
+    of points.  Release it with close(), a `with` block, or by dropping it; it belongs to
+    the engine context it was built on (the process-wide one unless `ctx` is given)."""
+
+    def __init__(self, points, ctx=None):
+        self._h = None
+        q = _images(points, 24)
+        if not 1 <= q.shape[0] <= 1 << 16:
+            raise ValueError("G2Prepared takes 1 .. 65536 points, not %d" % q.shape[0])
+        self._ctx = ctx if ctx is not None else context()
+        self._n = q.shape[0]
+        self._h = self._ctx.g2_prepare(q)
+
+    def __len__(self):
+        return self._n
+
+    @property
+    def closed(self):
+        return self._h is None
+
+    def _handle(self):
+        if self._h is None:
+            raise ValueError("this G2Prepared is closed")
+        return self._h
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        # (a context closed first has freed its handles itself)
+        if h is not None and getattr(self._ctx, "handle", None):
+            self._ctx.g2_prepared_destroy(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _prepared_rows(method, ps, prepared, idx):
+    p = _images(ps, 12)
+    h = prepared._handle()
+    if p.shape[0] == 0:
+        return []
+    ix = _native._indices(idx if idx is None or isinstance(idx, np.ndarray) else list(idx), p.shape[0], len(prepared))
+    return [Gt(row) for row in getattr(prepared._ctx, method)(p, h, ix)]
+
+
+def pairing_prepared_many(ps, prepared, idx=None):
+    """[pairing(ps[i], prepared[idx[i]])] in one engine call (bn_pairing_prepared_many), the same
+    Gt as pairing() on each pair.  ps: a sequence of G1 or an (n, 12) image array; idx: one
+    index per pair, or None for prepared point 0 throughout.  An index outside the prepared
+    points, a negative one and a closed G2Prepared raise ValueError before any device call;
+    no pairs give []."""
+    return _prepared_rows("pairing_prepared_many", ps, prepared, idx)
+
+
+def miller_loop_prepared_many(ps, prepared, idx=None):
+    """The Miller values of the same pairs (G2Precomp::miller_loop at ps[i].to_affine(),
+    mod.rs:579-607) as Gt-shaped values, before any final exponentiation
+    (bn_miller_loop_prepared_many).  Arguments as pairing_prepared_many."""
+    return _prepared_rows("miller_loop_prepared_many", ps, prepared, idx)
 
 
 def g2_affine_new_many(x, y):

@@ -40,6 +40,8 @@ EXPORTS = [
     "bn_g1_msm", "bn_g1_msm_dev", "bn_set_msm_window", "bn_set_msm_min", "bn_msm_reserve",
     "bn_g2_msm", "bn_g2_msm_dev", "bn_g2_msm_reserve",
     "bn_pairing_batch_many", "bn_pairing_batch_many_dev", "bn_set_products_min", "bn_set_products_chunk",
+    "bn_g2_prepare", "bn_g2_prepare_dev", "bn_g2_prepared_count", "bn_g2_prepared_destroy",
+    "bn_pairing_prepared_many", "bn_pairing_prepared_many_dev", "bn_miller_loop_prepared_many",
 ] + ["bn_%s_%s_many%s" % (g, op, dev) for g in ("g1", "g2") for op in ("add", "sub", "neg", "normalize", "eq")
      for dev in ("", "_dev")]
 GROUP_OPS = ("add", "sub", "neg", "normalize", "eq")
@@ -136,6 +138,13 @@ def load():
         "bn_pairing_batch_many_dev": ([vp, vp, vp, vp, sz, vp, vp], i),
         "bn_set_products_min": ([vp, sz], i),
         "bn_set_products_chunk": ([vp, sz], i),
+        "bn_g2_prepare": ([vp, vp, sz, ctypes.POINTER(vp)], i),
+        "bn_g2_prepare_dev": ([vp, vp, sz, ctypes.POINTER(vp), vp], i),
+        "bn_g2_prepared_count": ([vp], sz),
+        "bn_g2_prepared_destroy": ([vp, vp], i),
+        "bn_pairing_prepared_many": ([vp, vp, vp, vp, sz, vp], i),
+        "bn_pairing_prepared_many_dev": ([vp, vp, vp, vp, sz, vp, vp], i),
+        "bn_miller_loop_prepared_many": ([vp, vp, vp, vp, sz, vp], i),
     }
     for g in ("g1", "g2"):
         for op in GROUP_OPS:
@@ -195,6 +204,25 @@ def _offsets(offsets, n=None):
     return off
 
 
+def _indices(idx, n, nq):
+    """The n prepared-point indices as a contiguous uint32 array, or None (every pair takes
+    point 0) when idx is None.  A wrong count, a negative index, one that is not an integer
+    and one >= nq raise ValueError before any native call (the C ABI's host forms refuse the
+    last too)."""
+    if idx is None:
+        return None
+    raw = np.asarray(idx)
+    if raw.ndim != 1 or raw.shape[0] != n:
+        raise ValueError("idx must hold one index per pair (%d), not shape %s" % (n, raw.shape))
+    if raw.dtype.kind not in "iu":
+        raise ValueError("idx must be integers")
+    if raw.dtype.kind == "i" and (raw < 0).any():
+        raise ValueError("idx must not be negative")
+    if n and int(raw.max()) >= nq:
+        raise ValueError("idx holds %d but there are %d prepared points" % (int(raw.max()), nq))
+    return np.ascontiguousarray(raw, dtype=np.uint32)
+
+
 def shard_range(n, ndev, k):
     """[lo, hi) of shard k of n elements over ndev devices (the C ABI's split)."""
     lo, hi = ctypes.c_size_t(), ctypes.c_size_t()
@@ -246,7 +274,8 @@ class Context:
 
     def dev_status(self, stream=None):
         """bn_dev_status: synchronize and raise on the sticky device outcome of the
-        status-less _dev calls (BN_ERR_INTERNAL, BN_ERR_FE_ZERO); clears it."""
+        status-less _dev calls (BN_ERR_INTERNAL, then BN_ERR_INVALID_ARGUMENT: a prepared-point
+        index out of range, then BN_ERR_FE_ZERO); clears it."""
         self._check(self._L.bn_dev_status(self._h, stream))
 
     def close(self):
@@ -344,6 +373,49 @@ class Context:
         out = np.zeros((q.shape[0], 87, 24), np.uint64)
         self._check(self._L.bn_g2_precompute_many(self._h, _ptr(q), q.shape[0], _ptr(out)))
         return out
+
+    # ---- pairings against prepared G2 points (bn_g2_prepared)
+    def g2_prepare(self, q):
+        """bn_g2_prepare: a handle (int) holding the line coefficients of the rows of q on the
+        device; release it with g2_prepared_destroy (substrate_bn.G2Prepared does)."""
+        q = _arr(q, 24)
+        h = ctypes.c_void_p()
+        self._check(self._L.bn_g2_prepare(self._h, _ptr(q), q.shape[0], ctypes.byref(h)))
+        return h.value
+
+    def g2_prepare_dev(self, d_q, nq, stream=None):
+        h = ctypes.c_void_p()
+        self._check(self._L.bn_g2_prepare_dev(self._h, d_q, nq, ctypes.byref(h), stream))
+        return h.value
+
+    def g2_prepared_count(self, handle):
+        return int(self._L.bn_g2_prepared_count(handle))
+
+    def g2_prepared_destroy(self, handle):
+        self._check(self._L.bn_g2_prepared_destroy(self._h, handle))
+
+    def _prepared_many(self, fn, p, handle, idx):
+        p = _arr(p, 12)
+        n = p.shape[0]
+        ix = _indices(idx, n, self.g2_prepared_count(handle))
+        out = np.zeros((n, 48), np.uint64)
+        self._check(fn(self._h, _ptr(p), handle, None if ix is None else _ptr(ix), n, _ptr(out)))
+        return out
+
+    def pairing_prepared_many(self, p, handle, idx=None):
+        """bn_pairing_prepared_many: row i = pairing(p[i], Q[idx[i]]) for the handle's points Q;
+        idx None passes a NULL index (every pair takes Q[0]).  Indices are checked here
+        (ValueError) before the call."""
+        return self._prepared_many(self._L.bn_pairing_prepared_many, p, handle, idx)
+
+    def miller_loop_prepared_many(self, p, handle, idx=None):
+        """bn_miller_loop_prepared_many: the Miller values of the same pairs."""
+        return self._prepared_many(self._L.bn_miller_loop_prepared_many, p, handle, idx)
+
+    def pairing_prepared_many_dev(self, d_p, handle, d_idx, n, d_out, stream=None):
+        """bn_pairing_prepared_many_dev: device addresses (d_idx may be None); an index past the
+        handle's points makes that row zero and dev_status() raise BN_ERR_INVALID_ARGUMENT."""
+        self._check(self._L.bn_pairing_prepared_many_dev(self._h, d_p, handle, d_idx, n, d_out, stream))
 
     def final_exponentiation_many(self, f):
         f = _arr(f, 48)

@@ -25,7 +25,7 @@ os.environ.setdefault("BN254MI_LIB", os.path.join(ROOT, "paritytech-bn_amd", "li
 
 from substrate_bn import _native, synth  # noqa: E402
 
-TUS = ["pairing", "fe", "wide", "latency_w2", "group", "msm", "msm_g2", "gtpow", "codec", "util", "reduce", "tail"]  # every unit (Makefile dbg)
+TUS = ["pairing", "prepared", "fe", "wide", "latency_w2", "group", "msm", "msm_g2", "gtpow", "codec", "util", "reduce", "tail"]  # every unit (Makefile dbg)
 
 
 def counters(L):
@@ -60,6 +60,12 @@ def main():
     seg.set_latency_max(0)
     seg.pairing_many(p[:2048], q[:2048])
     seg.final_exponentiation_many(seg.miller_loop_many(p[:64], q[:64]))
+    # pairings against prepared G2 points (k_pairing_prepared, both forms; the fill's repack)
+    prepared = ctx.g2_prepare(q[:4])
+    idx = (np.arange(n) % 4).astype(np.uint32)
+    ctx.pairing_prepared_many(p, prepared, idx)
+    ctx.miller_loop_prepared_many(p[:256], prepared, idx[:256])
+    ctx.g2_prepared_destroy(prepared)
     ctx.gt_pow_many(gt, synth.fr_images(n, 3, lo=0))
     for op in ("mul", "sqr", "inv", "cyc_sqr", "exp_by_neg_z", "frob1", "frob2", "frob3"):
         ctx.fq12_op_many(op, gt[:256], gt[256:512] if op == "mul" else None)
