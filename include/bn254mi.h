@@ -223,6 +223,44 @@ int bn_pairing_prepared_many_dev(bn_ctx* ctx, const bn_g1* d_p, const bn_g2_prep
 int bn_miller_loop_prepared_many(bn_ctx* ctx, const bn_g1* p, const bn_g2_prepared* prepared, const uint32_t* qidx,
                                  size_t n, bn_gt* out);
 
+/* out[j] = pairing_batch over terms offsets[j] <= i < offsets[j+1], for j < m, where the G2 side
+ * of term i is the handle's point Q[qidx[i]], or, when qidx[i] == BN_QIDX_FRESH, the next unused
+ * entry of q: bn_pairing_batch_many with the fixed G2 points (a Groth16 verifying key's beta,
+ * gamma, delta) taken from a bn_g2_prepared handle, so that their line steps are not recomputed
+ * and their points are not uploaded.  Every out[j] is bit-identical to bn_pairing_batch over the
+ * same terms with the G2 points written out.
+ *   p: n = offsets[m] G1 points in term order.  q: only the fresh terms' G2 points, compacted, in
+ *   term order (nf entries, nf = the number of BN_QIDX_FRESH in qidx).  qidx (n entries) and
+ *   offsets (m + 1 entries, non-decreasing from 0) are HOST memory in both forms.
+ *   A term with a zero p[i], a zero fresh q or a zero table point is skipped; an empty or
+ *   all-skipped product gives Gt::one().  A zero Miller product makes that out[j] the zero image
+ *   and the call return BN_ERR_FE_ZERO with every other row written (the _dev form reports it
+ *   through bn_dev_status).
+ *   Refused with BN_ERR_INVALID_ARGUMENT before any buffer is read, out untouched: malformed
+ *   offsets; a NULL qidx, out or handle; a NULL p with n > 0; a NULL q with nf > 0; an index that
+ *   is neither BN_QIDX_FRESH nor below the handle's count; a handle of another context or a
+ *   destroyed one; a multi-device context (its device contexts work); any product of more than 64
+ *   terms.  m == 0 returns BN_OK and touches nothing.
+ * There is no alone path and bn_set_products_min does not apply: every product runs one per lane
+ * pair of the packed kernel (k_miller_products_mapped), so a small call costs the time of one lane
+ * pair's chain, as with the prepared calls above.  Callers who need small-batch
+ * latency, or products of more than 64 terms, keep bn_pairing_batch.
+ * Per launch set (cut at product boundaries, at most bn_set_products_chunk terms and 2^18
+ * products): the line producers over the fresh terms only, k_prepared_expand over the prepared
+ * ones (the table's lines scaled by the term's Jacobian P; no inversion), the products' loop, one
+ * final exponentiation per product.  bn_reserve(n) guarantees that sets of at most n terms and n
+ * products allocate no workspace.  Two buffers grow on first use and are not counted by
+ * bn_workspace_bytes: the per-term map (up to 3 words per term, uploaded with the offsets) and,
+ * in the _dev form, the gathered G1 points of a set's fresh terms (96 bytes each).
+ * The _dev form enqueues on `stream` without synchronizing, reads qidx and offsets before it
+ * returns, and may wait for the previous call's upload of its offsets (not for its kernels). */
+#define BN_QIDX_FRESH 0xffffffffu
+int bn_pairing_batch_prepared_many(bn_ctx* ctx, const bn_g1* p, const bn_g2* q, const bn_g2_prepared* prepared,
+                                   const uint32_t* qidx, const size_t* offsets, size_t m, bn_gt* out);
+int bn_pairing_batch_prepared_many_dev(bn_ctx* ctx, const bn_g1* d_p, const bn_g2* d_q,
+                                       const bn_g2_prepared* prepared, const uint32_t* qidx, const size_t* offsets,
+                                       size_t m, bn_gt* d_out, void* stream);
+
 /* ---- group path (src/groups/mod.rs:250-334, lib.rs:425-431) ---- */
 
 /* out[i] = p[i] * k[i]: the reference's double-and-add chain (mod.rs:272-292), so the

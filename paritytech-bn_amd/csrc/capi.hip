@@ -1000,6 +1000,9 @@ static void ctx_teardown(bn_ctx* c) {
     if (c->prod_off_event) (void)hipEventDestroy(c->prod_off_event);
     if (c->prod_off_h) (void)hipHostFree(c->prod_off_h);
     if (c->prod_off_d) (void)hipFree(c->prod_off_d);
+    if (c->prod_map_h) (void)hipHostFree(c->prod_map_h);
+    if (c->prod_map_d) (void)hipFree(c->prod_map_d);
+    if (c->prod_fresh) (void)hipFree(c->prod_fresh);
     for (hipEvent_t e : {c->ev_in[0], c->ev_in[1], c->ev_comp[0], c->ev_comp[1], c->ev_out[0], c->ev_out[1]})
         if (e) (void)hipEventDestroy(e);
     if (c->pin) (void)hipHostFree(c->pin);
@@ -1922,6 +1925,214 @@ int bn_pairing_prepared_many_dev(bn_ctx* c, const bn_g1* d_p, const bn_g2_prepar
     if (n == 0) return BN_OK;
     RET_IF(prepared_args(c, d_p, h, d_out));
     return prepared_dev_impl(c, d_p, h, d_qidx, n, d_out, true, pick(c, stream));
+}
+
+// ---- products with prepared terms (bn_pairing_batch_prepared_many)
+// One launch set, products [j0, j1): nf fresh terms (the call's fresh terms f0 .. f0 + nf - 1,
+// which is where their points start in the compacted q) and np prepared ones; its words
+// start at off_at in prod_off_d (j1 - j0 + 1 set-relative offsets) and at map_at in
+// prod_map_d: the term map (nf + np words), the prepared slots' terms and table indices
+// (np each), the fresh slots' terms (nf).  Every product runs on the packed path (no alone
+// path), so the sets are products_plan's packed runs.
+struct PreparedSet {
+    size_t j0, j1, nf, np, f0, off_at, map_at;
+};
+static std::vector<PreparedSet> prepared_products_plan(const bn_ctx* c, const uint32_t* qidx, const size_t* off,
+                                                       size_t m) {
+    std::vector<PreparedSet> sets;
+    size_t f0 = 0, off_at = 0, map_at = 0;
+    for (size_t j = 0; j < m;) {
+        size_t e = j + 1;
+        while (e < m && e - j < kChunk && off[e + 1] - off[j] <= c->products_chunk) ++e;
+        size_t nf = 0;
+        for (size_t i = off[j]; i < off[e]; ++i) nf += qidx[i] == BN_QIDX_FRESH ? 1 : 0;
+        const size_t nt = off[e] - off[j];
+        sets.push_back({j, e, nf, nt - nf, f0, off_at, map_at});
+        f0 += nf;
+        off_at += e - j + 1;
+        map_at += 3 * nt;
+        j = e;
+    }
+    return sets;
+}
+// Refusals, before any point buffer is read (qidx and offsets are the host's control arrays)
+static int prepared_products_check(bn_ctx* c, const void* p, const void* q, const bn_g2_prepared* h,
+                                   const uint32_t* qidx, const size_t* off, size_t m, const void* out) {
+    if (!off) return fail(c, BN_ERR_INVALID_ARGUMENT, "null offsets");
+    if (off[0] != 0) return fail(c, BN_ERR_INVALID_ARGUMENT, "offsets[0] must be 0");
+    for (size_t j = 0; j < m; ++j)
+        if (off[j + 1] < off[j]) return fail(c, BN_ERR_INVALID_ARGUMENT, "offsets must not decrease");
+    if (!qidx || !out || !h) return fail(c, BN_ERR_INVALID_ARGUMENT, "null buffer");
+    if (!prepared_live(c, h)) return fail(c, BN_ERR_INVALID_ARGUMENT, "not a live prepared handle of this context");
+    if (off[m] && !p) return fail(c, BN_ERR_INVALID_ARGUMENT, "null buffer");
+    for (size_t j = 0; j < m; ++j)
+        if (off[j + 1] - off[j] > (size_t)kProductLaneMax)
+            return fail(c, BN_ERR_INVALID_ARGUMENT, "a product of more than 64 terms; use bn_pairing_batch");
+    size_t nf = 0;
+    for (size_t i = 0; i < off[m]; ++i) {
+        if (qidx[i] == BN_QIDX_FRESH) ++nf;
+        else if (qidx[i] >= h->nq) return fail(c, BN_ERR_INVALID_ARGUMENT, "prepared-point index out of range");
+    }
+    if (nf && !q) return fail(c, BN_ERR_INVALID_ARGUMENT, "null buffer");
+    return BN_OK;
+}
+static int grow_words(bn_ctx* c, uint32_t** h, uint32_t** d, size_t* cap, size_t words) {
+    if (words <= *cap) return BN_OK;
+    RET_IF(ws_drain(c));  // queued kernels may still read the old buffer
+    if (*h) HIPCHK(c, hipHostFree(*h));
+    if (*d) HIPCHK(c, hipFree(*d));
+    *h = nullptr; *d = nullptr; *cap = 0;
+    const size_t n = std::max<size_t>(words, 4096);
+    HIPCHK(c, hipHostMalloc(h, n * 4, hipHostMallocDefault));
+    HIPCHK(c, hipMalloc(d, n * 4));
+    *cap = n;
+    return BN_OK;
+}
+// The offsets and per-term words of every set -> prod_off_d / prod_map_d, two copies on s in
+// front of the call's kernels, under products_offsets_upload's discipline (one event for
+// both pinned sources).  compact_p: the host form stages a set's G1 points fresh first, then
+// prepared, so prepared slot k's term is nf + k; otherwise terms are the caller's, set-relative.
+static int prepared_products_upload(bn_ctx* c, const uint32_t* qidx, const size_t* off,
+                                    const std::vector<PreparedSet>& sets, bool compact_p, hipStream_t s) {
+    if (c->prod_off_pending) {
+        HIPCHK(c, hipEventSynchronize(c->prod_off_event));
+        c->prod_off_pending = false;
+    }
+    const PreparedSet& last = sets.back();
+    const size_t off_words = last.off_at + (last.j1 - last.j0 + 1);
+    const size_t map_words = last.map_at + 3 * (last.nf + last.np);
+    RET_IF(grow_words(c, &c->prod_off_h, &c->prod_off_d, &c->prod_off_cap, off_words));
+    RET_IF(grow_words(c, &c->prod_map_h, &c->prod_map_d, &c->prod_map_cap, map_words));
+    for (const PreparedSet& st : sets) {
+        const size_t lo = off[st.j0], nt = st.nf + st.np;
+        for (size_t j = st.j0; j <= st.j1; ++j) c->prod_off_h[st.off_at + (j - st.j0)] = (uint32_t)(off[j] - lo);
+        uint32_t* map = c->prod_map_h + st.map_at;
+        uint32_t* pterm = map + nt;
+        uint32_t* pidx = pterm + st.np;
+        uint32_t* fterm = pidx + st.np;
+        size_t kf = 0, kp = 0;
+        for (size_t t = 0; t < nt; ++t) {
+            const uint32_t qi = qidx[lo + t];
+            if (qi == BN_QIDX_FRESH) {
+                fterm[kf] = (uint32_t)t;
+                map[t] = (uint32_t)kf++;
+            } else {
+                pterm[kp] = (uint32_t)(compact_p ? st.nf + kp : t);
+                pidx[kp] = qi;
+                map[t] = kMapRegionB | (uint32_t)kp++;
+            }
+        }
+    }
+    HIPCHK(c, hipMemcpyAsync(c->prod_off_d, c->prod_off_h, off_words * 4, hipMemcpyHostToDevice, s));
+    if (map_words)
+        HIPCHK(c, hipMemcpyAsync(c->prod_map_d, c->prod_map_h, map_words * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipEventRecord(c->prod_off_event, s));
+    c->prod_off_pending = true;
+    return BN_OK;
+}
+static int prepared_products_reserve(bn_ctx* c, const std::vector<PreparedSet>& sets) {
+    size_t need = 1;
+    for (const PreparedSet& st : sets) need = std::max(need, std::max(st.nf + st.np, st.j1 - st.j0));
+    return reserve(c, need);
+}
+// one launch set: the nf fresh pairs at d_pf / d_qf through the producers into region A of
+// the workspace, the np prepared terms (G1 points d_pp[pterm[k]]) through k_prepared_expand
+// into region B behind it, the products' loop over both, the final exponentiation
+static int prepared_products_set_dev(bn_ctx* c, const PreparedSet& st, const bn_g1* d_pf, const bn_g2* d_qf,
+                                     const bn_g1* d_pp, const bn_g2_prepared* h, bn_gt* d_out, hipStream_t s) {
+    const size_t nf = st.nf, np = st.np, mc = st.j1 - st.j0;
+    if (nf + np > c->cap || mc > c->cap) return fail(c, BN_ERR_INTERNAL, "launch set exceeds the workspace");
+    const uint32_t* map = c->prod_map_d + st.map_at;
+    if (nf) RET_IF(prepare(c, d_pf, d_qf, nf, 0, s, 1, true));
+    if (np) {
+        launch_prepared_expand(d_pp, map + nf + np, map + nf + 2 * np, h->table, h->zero, (uint32_t)h->nq, np,
+                               c->coeffs + nf * (size_t)kCoeffFq * 9, c->flags + kPathLanes * nf, s);
+        HIPCHK(c, hipGetLastError());
+    }
+    const size_t lanes = kPathLanes * mc;
+    const unsigned block = products_block(c, lanes);
+    k_miller_products_mapped<<<(unsigned)((lanes + block - 1) / block), block, 0, s>>>(
+        c->coeffs, c->flags, nf, np, map, c->prod_off_d + st.off_at, mc, c->slots);
+    HIPCHK(c, hipGetLastError());
+    return run_fe(c, c->slots, mc, nullptr, d_out, nullptr, s);
+}
+
+int bn_pairing_batch_prepared_many_dev(bn_ctx* c, const bn_g1* d_p, const bn_g2* d_q, const bn_g2_prepared* h,
+                                       const uint32_t* qidx, const size_t* offsets, size_t m, bn_gt* d_out,
+                                       void* stream) {
+    CTX_GUARD(c);
+    if (m == 0) return BN_OK;
+    RET_IF(prepared_products_check(c, d_p, d_q, h, qidx, offsets, m, d_out));
+    const hipStream_t s = pick(c, stream);
+    const std::vector<PreparedSet> sets = prepared_products_plan(c, qidx, offsets, m);
+    RET_IF(prepared_products_reserve(c, sets));
+    size_t nfmax = 0;
+    for (const PreparedSet& st : sets) nfmax = std::max(nfmax, st.nf);
+    if (nfmax > c->prod_fresh_cap) {
+        RET_IF(ws_drain(c));
+        if (c->prod_fresh) HIPCHK(c, hipFree(c->prod_fresh));
+        c->prod_fresh = nullptr;
+        c->prod_fresh_cap = 0;
+        const size_t cap = std::max<size_t>(nfmax, 4096);
+        HIPCHK(c, hipMalloc(&c->prod_fresh, cap * sizeof(bn_g1)));
+        c->prod_fresh_cap = cap;
+    }
+    RET_IF(ws_acquire(c, s));
+    WsUse use{c, s};
+    RET_IF(prepared_products_upload(c, qidx, offsets, sets, false, s));
+    for (const PreparedSet& st : sets) {
+        const size_t lo = offsets[st.j0];
+        if (st.nf) {
+            launch_g1_gather(d_p + lo, c->prod_map_d + st.map_at + st.nf + 3 * st.np, st.nf, c->prod_fresh, s);
+            HIPCHK(c, hipGetLastError());
+        }
+        RET_IF(prepared_products_set_dev(c, st, c->prod_fresh, d_q + st.f0, d_p + lo, h, d_out + st.j0, s));
+    }
+    return BN_OK;
+}
+// The host form: every set staged in turn (its G1 points compacted, fresh first; its fresh
+// G2 points; its products' Gt), the device outcome read after each, BN_ERR_FE_ZERO reported
+// at the end with every row written.
+static int prepared_products_host(bn_ctx* c, const bn_g1* p, const bn_g2* q, const bn_g2_prepared* h,
+                                  const uint32_t* qidx, const size_t* off, size_t m, bn_gt* out) {
+    const std::vector<PreparedSet> sets = prepared_products_plan(c, qidx, off, m);
+    RET_IF(prepared_products_reserve(c, sets));
+    RET_IF(prepared_products_upload(c, qidx, off, sets, true, c->stream));
+    bool zero = false;
+    std::vector<bn_g1> hp;
+    for (const PreparedSet& st : sets) {
+        const size_t lo = off[st.j0], nt = st.nf + st.np, mc = st.j1 - st.j0;
+        RET_IF(clear_err(c, c->stream));
+        const size_t o_q = round256(nt * sizeof(bn_g1));
+        const size_t o_out = o_q + round256(st.nf * sizeof(bn_g2));
+        RET_IF(stage(c, o_out + mc * sizeof(bn_gt)));
+        uint8_t* base = (uint8_t*)c->stage;
+        bn_g1* dp = (bn_g1*)base;
+        bn_g2* dq = (bn_g2*)(base + o_q);
+        bn_gt* d = (bn_gt*)(base + o_out);
+        hp.resize(nt);  // (the previous set's copy has completed: check_err synchronizes)
+        size_t kf = 0, kp = st.nf;
+        for (size_t t = 0; t < nt; ++t) hp[qidx[lo + t] == BN_QIDX_FRESH ? kf++ : kp++] = p[lo + t];
+        if (nt) HIPCHK(c, hipMemcpyAsync(dp, hp.data(), nt * sizeof(bn_g1), hipMemcpyHostToDevice, c->stream));
+        if (st.nf)
+            HIPCHK(c, hipMemcpyAsync(dq, q + st.f0, st.nf * sizeof(bn_g2), hipMemcpyHostToDevice, c->stream));
+        RET_IF(prepared_products_set_dev(c, st, dp, dq, dp, h, d, c->stream));
+        HIPCHK(c, hipMemcpyAsync(out + st.j0, d, mc * sizeof(bn_gt), hipMemcpyDeviceToHost, c->stream));
+        int bits = 0;
+        RET_IF(check_err(c, c->stream, &bits));  // synchronizes: the stage and hp are reused
+        if (bits & (1 << BN_ERR_FE_ZERO)) zero = true;
+    }
+    if (zero) return fail(c, BN_ERR_FE_ZERO, "miller loop cannot produce zero");
+    return BN_OK;
+}
+int bn_pairing_batch_prepared_many(bn_ctx* c, const bn_g1* p, const bn_g2* q, const bn_g2_prepared* h,
+                                   const uint32_t* qidx, const size_t* offsets, size_t m, bn_gt* out) {
+    CTX_GUARD_HOST(c);
+    if (m == 0) return BN_OK;
+    RET_IF(prepared_products_check(c, p, q, h, qidx, offsets, m, out));
+    const int rc = prepared_products_host(c, p, q, h, qidx, offsets, m, out);
+    (void)hipStreamSynchronize(c->stream);  // an early error may leave copies queued
+    return rc;
 }
 
 int bn_g1_mul_many_dev(bn_ctx* c, const bn_g1* d_p, const bn_fr* d_k, size_t n, bn_g1* d_out, void* stream) {

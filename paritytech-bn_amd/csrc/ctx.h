@@ -132,6 +132,15 @@ struct bn_ctx {
     size_t prod_off_cap = 0;  // words
     hipEvent_t prod_off_event = nullptr;
     bool prod_off_pending = false;
+    // bn_pairing_batch_prepared_many: the per-term words of every launch set of a call (per
+    // set the term map, then the prepared slots' terms and table indices, then the fresh
+    // slots' terms), uploaded with the offsets under the same event; and the _dev form's
+    // gathered G1 points of a set's fresh terms.  Both grow on first use, like prod_off_*.
+    uint32_t* prod_map_h = nullptr;
+    uint32_t* prod_map_d = nullptr;
+    size_t prod_map_cap = 0;  // words
+    bn_g1* prod_fresh = nullptr;
+    size_t prod_fresh_cap = 0;  // points
     // the bn_g2_prepared handles this context made and has not destroyed yet (capi.hip).
     // Their tables are their own memory, not part of the workspace; the calls that read
     // them order themselves through ws_event like every workspace user, which is what

@@ -546,6 +546,15 @@ __global__ void __launch_bounds__(kPairBlock) k_miller_products(const uint32_t* 
                                                             const uint8_t* __restrict__ flags, size_t n,
                                                             const uint32_t* __restrict__ off, size_t m,
                                                             uint32_t* __restrict__ out);
+// The same over lines in two regions (bn_pairing_batch_prepared_many): the nf fresh terms'
+// at coeffs / flags (lane stride kL * nf), the np prepared terms' behind them (lane stride
+// kL * np); term t of the nf + np is slot map[t] & 0x7fffffff of region B (bit 31 set) or A.
+constexpr uint32_t kMapRegionB = 0x80000000u;
+__global__ void __launch_bounds__(kPairBlock) k_miller_products_mapped(const uint32_t* __restrict__ coeffs,
+                                                                   const uint8_t* __restrict__ flags, size_t nf,
+                                                                   size_t np, const uint32_t* __restrict__ map,
+                                                                   const uint32_t* __restrict__ off, size_t m,
+                                                                   uint32_t* __restrict__ out);
 // out[e] = Horner recombination of element e's S segment values (element s * n + e of g,
 // split layout, stride S * n): x = g0; x = x^(2^len_s) * g_s; then the final
 // exponentiation when do_fe
@@ -625,6 +634,14 @@ __global__ void __launch_bounds__(kBlock) k_prepared_repack(const uint32_t* __re
 void launch_pairing_prepared(bool final_exp, const bn_g1* p, const uint32_t* table, const uint8_t* qzero, uint32_t nq,
                              const uint32_t* qidx, size_t n, const uint32_t* prog, int nsteps, uint32_t* slots,
                              bn_gt* out, int* err, hipStream_t s);
+// k_prepared_expand: the lines of point pidx[s] of the table scaled by term pterm[s] of p
+// (Gt form), s < np, into coeffs / flags in the producers' layout (lane stride kL * np): the
+// operands of apply_line_scaled, for k_miller_products_mapped's region B
+void launch_prepared_expand(const bn_g1* p, const uint32_t* pterm, const uint32_t* pidx, const uint32_t* table,
+                            const uint8_t* qzero, uint32_t nq, size_t np, uint32_t* coeffs, uint8_t* flags,
+                            hipStream_t s);
+// k_g1_gather: out[i] = p[term[i]], i < n
+void launch_g1_gather(const bn_g1* p, const uint32_t* term, size_t n, bn_g1* out, hipStream_t s);
 __global__ void __launch_bounds__(kBlock) k_fe_out(const uint32_t* __restrict__ slots, size_t n, int out_slot, const uint8_t* __restrict__ flags,
                          bn_gt* __restrict__ out, uint8_t* __restrict__ ok, int* __restrict__ err);
 // kernels_wide.hip (fq12_wide.h): final exponentiation and product reduction on 16-lane groups

@@ -500,6 +500,64 @@ __global__ void BN_PATH_ATTR __launch_bounds__(kPairBlock) k_miller_products(con
     st_fq12(out, kL * m, l, f);
 }
 
+// The same with the terms' lines in two regions of `coeffs` (bn_pairing_batch_prepared_many):
+// region A, the nf fresh terms' lines from k_prepare(_wide)_scaled (lane stride kL * nf), and
+// behind it region B, the np prepared terms' lines from k_prepared_expand (lane stride
+// kL * np); `flags` likewise (kL * nf bytes, then kL * np).  Term t of the launch set's
+// n = nf + np (the terms off[j] .. off[j + 1] - 1 of product j, in the caller's order) is
+// looked up through map[t]: bit 31 selects region B, the low bits are the term's slot in
+// its region.  Everything else is k_miller_products: the wave-uniform pair loop to the
+// wave's largest product, the line one past a product's own count and for a flagged term,
+// the loads of such a lane pair from a clamped in-range term (whose map word is read), the
+// launch shape and the block size (capi.hip products_block).
+__global__ void BN_PATH_ATTR __launch_bounds__(kPairBlock)
+k_miller_products_mapped(const uint32_t* __restrict__ coeffs, const uint8_t* __restrict__ flags, size_t nf, size_t np,
+                         const uint32_t* __restrict__ map, const uint32_t* __restrict__ off, size_t m,
+                         uint32_t* __restrict__ out) {
+    static_assert(BN_LINES_PRESCALED, "k_miller_products_mapped takes the lines as the loop multiplies by them");
+    fold_table_init();
+    const Balance bal = balance_init();
+    const size_t l = lane_id(), j = l / kL, c = l % kL, n = nf + np;
+    if (j >= m) return;
+    const size_t j0 = (size_t)__builtin_amdgcn_readfirstlane((uint32_t)(l / 64)) * (64 / kL);
+    const size_t jn = m - j0 < (size_t)(64 / kL) ? m - j0 : (size_t)(64 / kL);
+    uint32_t Kw = 0;
+#pragma unroll 1
+    for (size_t u = 0; u < jn; ++u) {
+        const uint32_t k = off[j0 + u + 1] - off[j0 + u];
+        Kw = k > Kw ? k : Kw;
+    }
+    const size_t lo = off[j], K = off[j + 1] - lo;
+    const uint32_t* coeffs_b = coeffs + nf * (size_t)kCoeffFq * 9;  // region A: kCoeffFq x 9 words per term
+    const uint8_t* flags_b = flags + kL * nf;
+    // past this product's own terms: the set's nearest term (only called with Kw > 0, so n > 0)
+    auto term_of = [&](int t) {
+        return (size_t)t < K ? lo + (size_t)t : (lo + (size_t)t < n ? lo + (size_t)t : n - 1);
+    };
+    // The map word of the NEXT line's term is fetched while the current line is multiplied in
+    // (the loop visits t = 0 .. Kw - 1 in turn, pass after pass): read at its use, the word's
+    // load would sit in front of every line's loads on the lane pair's dependent chain.
+    uint32_t wnext = Kw ? map[term_of(0)] : 0u;
+    const Fq12<kF> f = miller_product_scaled(
+        (int)Kw,
+        [&](int t, int k) {
+            const uint32_t w = wnext;
+            const bool rb = (w >> 31) != 0;
+            const size_t lt = (size_t)(w & 0x7fffffffu) * kL + c;  // the term's lane in its region's arrays
+            const size_t nl = kL * (rb ? np : nf);
+            const uint32_t* base = rb ? coeffs_b : coeffs;
+            const bool live = (size_t)t < K && !(rb ? flags_b : flags)[lt];
+            mem_fence();  // load right before use: the terms' lines are never held at once
+            const Fq2<kLine> one = widen<kLine>(fq2_one()), zero = widen<kLine>(fq2_zero());
+            const Fq2<kLine> e0 = ld_fq2<kLine>(base, nl, lt, k * 6 + 0), e1 = ld_fq2<kLine>(base, nl, lt, k * 6 + 2),
+                             e2 = ld_fq2<kLine>(base, nl, lt, k * 6 + 4);
+            wnext = map[term_of(t + 1 < (int)Kw ? t + 1 : 0)];  // behind the line's loads: not waited for here
+            return Ell{fq2_select(live, e0, one), fq2_select(live, e1, zero), fq2_select(live, e2, zero)};
+        },
+        [&](uint32_t pos) { balance_step(bal, pos); });
+    st_fq12(out, kL * m, l, f);
+}
+
 // G2 * Fr (mod.rs:272-292) on the pairing path's two-lane layout: the chain of
 // curve.h jac_mul with lane 2i + c holding coordinate c of element i, so a batch
 // is twice the waves of a one-lane kernel (rounds 1-3) and each lane holds half the state.

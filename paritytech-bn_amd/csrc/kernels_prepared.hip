@@ -139,6 +139,70 @@ k_pairing_prepared(const bn_g1* __restrict__ p, const uint32_t* __restrict__ tab
     }
 }
 
+// The prepared terms of a launch set of bn_pairing_batch_prepared_many: prepared slot s < np is
+// term pterm[s] of p against point pidx[s] of the table; its 87 lines are written as the
+// products' loop multiplies by them (pairing.h prepared_line_scaled in k_pairing_prepared's Gt
+// form: ell_0 Z^3, ell_vw Y, ell_vv X Z of the Jacobian P, no inversion) into `coeffs` in the
+// producers' lane-strided layout (lane stride kL * np), and the term's flag (P zero or table
+// point zero) into flags[kL * s + c].  The host has checked every index; one >= nq is still
+// clamped before any address is formed.
+// kExpandSplit lane pairs share a term: lane pair g = r * np + s takes lines r, r + 29, r + 58
+// (a wave's lane pairs are neighbouring slots at one r, so the stores stay coalesced) and forms
+// Z^3 and X Z itself.  With one lane pair per term the kernel was a chain of 87 load - scale -
+// store rounds, 0.245 ms at 3,072 terms where the GPU is nearly empty.
+// Loads and stores bound it, not issue: no two-waves-per-SIMD attribute, so its 71 VGPRs let
+// two blocks share a CU.
+constexpr int kExpandSplit = 29;
+static_assert(BN_NUM_COEFFS % kExpandSplit == 0, "k_prepared_expand: every lane pair the same number of lines");
+__global__ void __launch_bounds__(kPairBlock)
+k_prepared_expand(const bn_g1* __restrict__ p, const uint32_t* __restrict__ pterm, const uint32_t* __restrict__ pidx,
+                  const uint32_t* __restrict__ table, const uint8_t* __restrict__ qzero, uint32_t nq, size_t np,
+                  uint32_t* __restrict__ coeffs, uint8_t* __restrict__ flags) {
+    fold_table_init();
+    const size_t l = lane_id(), g = l / kL, nl = kL * np;
+    if (g >= np * kExpandSplit) return;
+    const size_t s = g % np, ls = s * kL + l % kL;  // the slot, and this lane's place in its arrays
+    const int r = (int)(g / np);
+    const uint32_t jr = pidx[s], j = jr < nq ? jr : 0u;
+    const uint32_t* row = table + (size_t)j * kPreparedWords + (l % kL) * 9;
+    const bn_g1& pt = p[pterm[s]];
+    uint32_t wz[8];
+    ld_words(&pt.z, wz);
+    if (r == 0) flags[ls] = words_zero(wz) || qzero[j] != 0 || jr >= nq ? 1 : 0;
+    const Fq<2> pz = fq_load_ref(wz), px = ld_ref(pt.x), py = ld_ref(pt.y);
+    const auto s0 = fq_mul(fq_sqr(pz), pz), sx = fq_mul(px, pz);
+#pragma unroll
+    for (int i = 0; i < BN_NUM_COEFFS / kExpandSplit; ++i) {
+        const int k = r + i * kExpandSplit;
+        const uint32_t* w = row + k * kPreparedLineWords;
+        const Ell e = prepared_line_scaled(Ell{ld_prepared(w), ld_prepared(w + 18), ld_prepared(w + 36)}, s0, py, sx);
+        st_fq2(coeffs, nl, ls, k * 6 + 0, e.ell_0);
+        st_fq2(coeffs, nl, ls, k * 6 + 2, e.ell_vw);
+        st_fq2(coeffs, nl, ls, k * 6 + 4, e.ell_vv);
+    }
+}
+
+// out[i] = p[term[i]], i < n: the G1 points of a launch set's fresh terms, contiguous, for the
+// producers (bn_pairing_batch_prepared_many_dev; the host form compacts while it stages).
+// One thread per 16-byte sixth of a point.
+__global__ void __launch_bounds__(kBlock) k_g1_gather(const bn_g1* __restrict__ p, const uint32_t* __restrict__ term,
+                                                      size_t n, bn_g1* __restrict__ out) {
+    constexpr size_t kParts = sizeof(bn_g1) / sizeof(uint4);
+    const size_t t = lane_id(), i = t / kParts, part = t % kParts;
+    if (i >= n) return;
+    reinterpret_cast<uint4*>(out + i)[part] = reinterpret_cast<const uint4*>(p + term[i])[part];
+}
+
+void launch_prepared_expand(const bn_g1* p, const uint32_t* pterm, const uint32_t* pidx, const uint32_t* table,
+                            const uint8_t* qzero, uint32_t nq, size_t np, uint32_t* coeffs, uint8_t* flags,
+                            hipStream_t s) {
+    k_prepared_expand<<<grid_pair(kPathLanes * np * kExpandSplit), kPairBlock, 0, s>>>(p, pterm, pidx, table, qzero, nq,
+                                                                                       np, coeffs, flags);
+}
+void launch_g1_gather(const bn_g1* p, const uint32_t* term, size_t n, bn_g1* out, hipStream_t s) {
+    k_g1_gather<<<grid_for(n * (sizeof(bn_g1) / sizeof(uint4))), kBlock, 0, s>>>(p, term, n, out);
+}
+
 void launch_pairing_prepared(bool final_exp, const bn_g1* p, const uint32_t* table, const uint8_t* qzero, uint32_t nq,
                              const uint32_t* qidx, size_t n, const uint32_t* prog, int nsteps, uint32_t* slots,
                              bn_gt* out, int* err, hipStream_t s) {

@@ -286,15 +286,18 @@ template <int SB>
 BN_INLINE Fq2<kLine> ell_0_scaled(const Fq2<kLine>& e, const Fq<SB>& s0) {
     return narrow<kLine>(fq2_scale(e, s0));
 }
+// one stored line as the loop multiplies by it (apply_line_scaled's operands).  Also what
+// k_prepared_expand writes per line for the prepared terms of a product
+// (kernels_prepared.hip; compiled for the host by tests/native/products_prepared_emul.cpp).
+template <typename S0, int PB>
+BN_INLINE Ell prepared_line_scaled(const Ell& c, const S0& s0, const Fq<PB>& sy, const Fq<PB>& sx) {
+    return Ell{ell_0_scaled(c.ell_0, s0), narrow<kLine>(fq2_scale(c.ell_vw, sy)),
+               narrow<kLine>(fq2_scale(c.ell_vv, sx))};
+}
 template <typename S0, int PB, typename Line, typename Step = NoStep>
 BN_INLINE Fq12<kF> miller_prepared(Line&& line, const S0& s0, const Fq<PB>& sy, const Fq<PB>& sx,
                                    Step&& step = Step{}) {
-    // the line as the loop multiplies by it (apply_line's operands)
-    auto at = [&](int k) {
-        const Ell c = line(k);
-        return Ell{ell_0_scaled(c.ell_0, s0), narrow<kLine>(fq2_scale(c.ell_vw, sy)),
-                   narrow<kLine>(fq2_scale(c.ell_vv, sx))};
-    };
+    auto at = [&](int k) { return prepared_line_scaled(line(k), s0, sy, sx); };
     Fq12<kF> f = widen<kF>(fq12_one());
     int idx = 0;
 #pragma unroll 1

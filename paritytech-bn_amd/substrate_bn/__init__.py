@@ -23,7 +23,8 @@ plus the batched forms the reference lacks (pairing_many, g1_mul_many, and the
 multi-scalar multiplications g1_msm / g2_msm = sum of points[i] * scalars[i]) that
 the engine exists for, and pairings against fixed G2 points prepared once (G2Prepared,
 pairing_prepared_many, miller_loop_prepared_many: the reference's G2Precomp held on the
-device).  Values keep the reference's memory images (canonical
+device; pairing_batch_prepared_many: many products whose terms mix fresh and prepared
+points).  Values keep the reference's memory images (canonical
 Montgomery, little-endian u64 limbs), so a Gt compares equal exactly when the
 reference's derived PartialEq would.  Every computation runs on the GPU; there
 is no CPU fallback.
@@ -524,6 +525,36 @@ def miller_loop_prepared_many(ps, prepared, idx=None):
     mod.rs:579-607) as Gt-shaped values, before any final exponentiation
     (bn_miller_loop_prepared_many).  Arguments as pairing_prepared_many."""
     return _prepared_rows("miller_loop_prepared_many", ps, prepared, idx)
+
+
+def pairing_batch_prepared_many(products, prepared):
+    """[pairing_batch(pairs) for pairs in products] in one engine call
+    (bn_pairing_batch_prepared_many) where a term's G2 side may be a prepared point: each
+    term is (G1, G2), a fresh point, or (G1, int), index into `prepared` (a G2Prepared),
+    whose line steps are then not recomputed.  The same Gt as pairing_batch with the points
+    written out.  An index outside the prepared points, a product of more than 64 terms and
+    a closed G2Prepared raise ValueError before any device call; an empty product gives
+    Gt.one(); no products give [] without a device call."""
+    products = [list(terms) for terms in products]
+    h = prepared._handle()
+    nq = len(prepared)
+    for terms in products:
+        if len(terms) > _native.PRODUCT_LANE_MAX:
+            raise ValueError("a product of %d terms (at most %d); use pairing_batch"
+                             % (len(terms), _native.PRODUCT_LANE_MAX))
+        for _, b in terms:
+            if isinstance(b, (int, np.integer)) and not 0 <= int(b) < nq:
+                raise ValueError("prepared-point index %d outside 0 .. %d" % (int(b), nq - 1))
+    if not products:
+        return []
+    offsets = np.zeros(len(products) + 1, np.uintp)
+    offsets[1:] = np.cumsum([len(terms) for terms in products])
+    flat = [term for terms in products for term in terms]
+    fresh = [b for _, b in flat if not isinstance(b, (int, np.integer))]
+    qidx = np.array([int(b) if isinstance(b, (int, np.integer)) else _native.QIDX_FRESH for _, b in flat], np.uint32)
+    p = np.stack([a.img for a, _ in flat]) if flat else np.zeros((0, 12), np.uint64)
+    q = np.stack([b.img for b in fresh]) if fresh else np.zeros((0, 24), np.uint64)
+    return [Gt(row) for row in prepared._ctx.pairing_batch_prepared_many(p, q, h, qidx, offsets)]
 
 
 def g2_affine_new_many(x, y):

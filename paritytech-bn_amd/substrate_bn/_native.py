@@ -42,6 +42,7 @@ EXPORTS = [
     "bn_pairing_batch_many", "bn_pairing_batch_many_dev", "bn_set_products_min", "bn_set_products_chunk",
     "bn_g2_prepare", "bn_g2_prepare_dev", "bn_g2_prepared_count", "bn_g2_prepared_destroy",
     "bn_pairing_prepared_many", "bn_pairing_prepared_many_dev", "bn_miller_loop_prepared_many",
+    "bn_pairing_batch_prepared_many", "bn_pairing_batch_prepared_many_dev",
 ] + ["bn_%s_%s_many%s" % (g, op, dev) for g in ("g1", "g2") for op in ("add", "sub", "neg", "normalize", "eq")
      for dev in ("", "_dev")]
 GROUP_OPS = ("add", "sub", "neg", "normalize", "eq")
@@ -145,6 +146,8 @@ def load():
         "bn_pairing_prepared_many": ([vp, vp, vp, vp, sz, vp], i),
         "bn_pairing_prepared_many_dev": ([vp, vp, vp, vp, sz, vp, vp], i),
         "bn_miller_loop_prepared_many": ([vp, vp, vp, vp, sz, vp], i),
+        "bn_pairing_batch_prepared_many": ([vp, vp, vp, vp, vp, vp, sz, vp], i),
+        "bn_pairing_batch_prepared_many_dev": ([vp, vp, vp, vp, vp, vp, sz, vp, vp], i),
     }
     for g in ("g1", "g2"):
         for op in GROUP_OPS:
@@ -221,6 +224,33 @@ def _indices(idx, n, nq):
     if n and int(raw.max()) >= nq:
         raise ValueError("idx holds %d but there are %d prepared points" % (int(raw.max()), nq))
     return np.ascontiguousarray(raw, dtype=np.uint32)
+
+
+QIDX_FRESH = 0xffffffff   # BN_QIDX_FRESH: the term's G2 point is the next entry of q
+PRODUCT_LANE_MAX = 64     # terms per product of pairing_batch_prepared_many
+
+
+def _term_indices(qidx, n, nq):
+    """The n per-term words of pairing_batch_prepared_many as a contiguous uint32 array: each
+    QIDX_FRESH or a prepared-point index < nq.  Anything else raises ValueError before any
+    native call (the C ABI refuses it too).  Returns (array, number of fresh terms)."""
+    raw = np.asarray(qidx)
+    if raw.ndim != 1 or raw.shape[0] != n:
+        raise ValueError("qidx must hold one entry per term (%d), not shape %s" % (n, raw.shape))
+    if n and raw.dtype.kind not in "iu":
+        raise ValueError("qidx must be integers")
+    if n and raw.dtype.kind == "i" and (raw < 0).any():
+        raise ValueError("qidx must not be negative")
+    raw = raw.astype(np.uint64)
+    fresh = raw == QIDX_FRESH
+    if (~fresh & (raw >= nq)).any():
+        raise ValueError("qidx holds %d but there are %d prepared points" % (int(raw[~fresh].max()), nq))
+    return np.ascontiguousarray(raw, dtype=np.uint32), int(fresh.sum())
+
+
+def _product_lengths(off):
+    if off.shape[0] > 1 and int((off[1:] - off[:-1]).max()) > PRODUCT_LANE_MAX:
+        raise ValueError("a product of more than %d terms; use pairing_batch" % PRODUCT_LANE_MAX)
 
 
 def shard_range(n, ndev, k):
@@ -416,6 +446,41 @@ class Context:
         """bn_pairing_prepared_many_dev: device addresses (d_idx may be None); an index past the
         handle's points makes that row zero and dev_status() raise BN_ERR_INVALID_ARGUMENT."""
         self._check(self._L.bn_pairing_prepared_many_dev(self._h, d_p, handle, d_idx, n, d_out, stream))
+
+    def pairing_batch_prepared_many(self, p, q, handle, qidx, offsets):
+        """bn_pairing_batch_prepared_many: row j of the (m, 48) result is pairing_batch of the
+        terms offsets[j] <= i < offsets[j + 1], term i pairing p[i] with the handle's point
+        qidx[i], or with the next unused row of q where qidx[i] == QIDX_FRESH (q holds only
+        those terms' points, in term order).  Indices, offsets, the row count of q and the
+        64-term limit per product are checked here (ValueError) before the call; the empty
+        call returns without one."""
+        p = _arr(p, 12)
+        n = p.shape[0]
+        off = _offsets(offsets, n)
+        _product_lengths(off)
+        ix, nf = _term_indices(qidx, n, self.g2_prepared_count(handle))
+        q = np.zeros((0, 24), np.uint64) if q is None else _arr(q, 24)
+        if q.shape[0] != nf:
+            raise ValueError("q has %d rows but %d terms are fresh" % (q.shape[0], nf))
+        m = off.shape[0] - 1
+        out = np.zeros((m, 48), np.uint64)
+        if m == 0:
+            return out
+        self._check(self._L.bn_pairing_batch_prepared_many(self._h, _ptr(p) if n else None, _ptr(q) if nf else None,
+                                                           handle, _ptr(ix), _ptr(off), m, _ptr(out)))
+        return out
+
+    def pairing_batch_prepared_many_dev(self, d_p, d_q, handle, qidx, offsets, d_out, stream=None):
+        """bn_pairing_batch_prepared_many_dev: d_p, d_q (the fresh terms' points, compacted) and
+        d_out are device addresses; qidx and offsets are HOST sequences, checked as in
+        pairing_batch_prepared_many; the outcome is read with dev_status()."""
+        off = _offsets(offsets)
+        _product_lengths(off)
+        ix, _ = _term_indices(qidx, int(off[-1]), self.g2_prepared_count(handle))
+        if off.shape[0] == 1:
+            return
+        self._check(self._L.bn_pairing_batch_prepared_many_dev(self._h, d_p, d_q, handle, _ptr(ix), _ptr(off),
+                                                               off.shape[0] - 1, d_out, stream))
 
     def final_exponentiation_many(self, f):
         f = _arr(f, 48)

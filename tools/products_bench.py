@@ -14,7 +14,15 @@ else the script exits non-zero.  One JSON line per shape with the median / min /
 each form and terms/s and products/s of the medians; then per k the crossover: the
 smallest m from which (a) stays below (b).
 --forms picks the forms (a library without the new entry point can still run c: the
-baseline of an earlier commit through $BN254MI_LIB)."""
+baseline of an earlier commit through $BN254MI_LIB).
+
+--prepared F: instead, products of k terms whose first F are fresh and whose others are
+drawn from a bn_g2_prepared handle of nq = 3 points (a Groth16 product is k = 4, F = 1), two
+ways in the same alternating rounds:
+  p  bn_pairing_batch_prepared_many_dev (the fresh terms' G2 points compacted)
+  a  bn_pairing_batch_many_dev on the same terms with every G2 point written out
+The rows of the two must be equal before a shape is timed, else the script exits non-zero.
+One JSON line per shape with both forms and p's time over a's."""
 import argparse
 import json
 import os
@@ -38,6 +46,8 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--sample", type=int, default=32, help="products form b runs at most")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
+    ap.add_argument("--prepared", type=int, default=None, metavar="F",
+                    help="time the prepared-terms call: the first F terms of each product are fresh")
     args = ap.parse_args()
     import torch
 
@@ -110,6 +120,10 @@ def main():
     def stats(ts):
         return {"median_ms": round(statistics.median(ts), 4), "min_ms": round(min(ts), 4), "max_ms": round(max(ts), 4)}
 
+    if args.prepared is not None:
+        prepared_sweep(args, ctx, torch, dev, sh, shapes, P, Q, timed, stats, emit)
+        return
+
     cross = {k: None for k in ks}
     for k, m in shapes:
         for f in forms:  # warm-up
@@ -143,6 +157,60 @@ def main():
     if "a" in forms and "b" in forms:
         emit({"crossover_m": {str(k): cross[k] for k in ks},
               "note": "smallest m of the sweep from which the packed path stays below m single-product calls"})
+
+
+def prepared_sweep(args, ctx, torch, dev, sh, shapes, P, Q, timed, stats, emit):
+    """The --prepared F sweep over `shapes` = [(k, m)]: the handle's points are Q[0 .. 2], a
+    product's prepared terms take them in turn, its fresh terms take Q from row 3 on."""
+    F, nq = args.prepared, 3
+    handle = ctx.g2_prepare_dev(Q.data_ptr(), nq, sh)
+    out_p = torch.zeros((max(m for _, m in shapes), 48), dtype=torch.int64, device=dev)
+    out_a = torch.zeros_like(out_p)
+    for k, m in shapes:
+        f = min(F, k)
+        n = m * k
+        off = np.arange(m + 1, dtype=np.uintp) * k
+        t = np.arange(n) % k                                  # position inside the product
+        fresh = t < f
+        qidx = np.where(fresh, 0xFFFFFFFF, (t - f) % nq).astype(np.uint32)
+        nf = int(fresh.sum())
+        with torch.cuda.stream(torch.cuda.ExternalStream(sh)):
+            base = nq if nq + nf <= Q.shape[0] else 0
+            Qf = Q[base:base + nf].contiguous() if nf else Q[:1]  # the compacted fresh points
+            Qfull = torch.empty((n, 24), dtype=torch.int64, device=dev)
+            mask = torch.from_numpy(fresh).to(dev)
+            if nf:
+                Qfull[mask] = Qf
+            if nf < n:
+                Qfull[~mask] = Q[torch.from_numpy(qidx[~fresh].astype(np.int64)).to(dev)]
+        torch.cuda.synchronize(dev)
+
+        def run(form):
+            if form == "p":
+                return timed(lambda: ctx.pairing_batch_prepared_many_dev(P.data_ptr(), Qf.data_ptr(), handle, qidx,
+                                                                         off, out_p.data_ptr(), sh))
+            return timed(lambda: ctx.pairing_batch_many_dev(P.data_ptr(), Qfull.data_ptr(), off, out_a.data_ptr(), sh))
+
+        for form in ("p", "a"):  # warm-up
+            run(form)
+        ctx.dev_status()
+        if not np.array_equal(out_p[:m].cpu().numpy(), out_a[:m].cpu().numpy()):
+            print("MISMATCH at k=%d m=%d F=%d: the prepared call's rows differ from bn_pairing_batch_many_dev's"
+                  % (k, m, f), file=sys.stderr)
+            sys.exit(1)
+        times = {"p": [], "a": []}
+        for _ in range(args.reps):
+            for form in ("p", "a"):  # alternating
+                times[form].append(run(form))
+        rec = {"k": k, "m": m, "n": n, "fresh": f, "nq": nq, "reps": args.reps}
+        for form in ("p", "a"):
+            st = stats(times[form])
+            st["products_per_s"] = round(m / (st["median_ms"] * 1e-3))
+            rec[form] = st
+        rec["p_over_a"] = round(rec["p"]["median_ms"] / rec["a"]["median_ms"], 4)
+        emit(rec)
+    ctx.dev_status()
+    ctx.g2_prepared_destroy(handle)
 
 
 if __name__ == "__main__":
