@@ -1,62 +1,19 @@
 // capi.hip -- host side of the C ABI (include/bn254mi.h): context, workspace,
-// chunking, the final-exponentiation step program, and kernel launches.
-#include <hip/hip_runtime.h>
+// chunking, the final-exponentiation step program, and kernel launches.  The pairing
+// products and prepared points are in capi_products.hip, the multi-scalar multiplication
+// in capi_msm.hip; capi_internal.h is what the three share.
 #include <stdlib.h>
-#include <string.h>
 
-#include <algorithm>
 #include <array>
 #include <initializer_list>
-#include <mutex>
-#include <string>
 #include <thread>
 #include <vector>
 
-#include "kernels.h"
+#include "capi_internal.h"
 
 using namespace bn;
 
-#include "ctx.h"
-
 namespace {
-
-int fail(bn_ctx* c, int code, const std::string& msg) {
-    if (c) c->err = msg;
-    return code;
-}
-#define HIPCHK(ctx, x)                                                                   \
-    do {                                                                                 \
-        hipError_t e_ = (x);                                                             \
-        if (e_ != hipSuccess)                                                            \
-            return fail(ctx, BN_ERR_HIP, std::string(#x ": ") + hipGetErrorString(e_)); \
-    } while (0)
-
-#define RET_IF(x)              \
-    do {                       \
-        int r_ = (x);          \
-        if (r_) return r_;     \
-    } while (0)
-
-// order this call's device work after the workspace's previous user (see bn_ctx)
-int ws_acquire(bn_ctx* c, hipStream_t s) {
-    if (c->ws_pending) HIPCHK(c, hipStreamWaitEvent(s, c->ws_event, 0));
-    return BN_OK;
-}
-// ... and mark this call's work as the workspace's latest user (scope exit)
-struct WsUse {
-    bn_ctx* c;
-    hipStream_t s;
-    ~WsUse() {
-        if (hipEventRecord(c->ws_event, s) == hipSuccess) c->ws_pending = true;
-    }
-};
-// before freeing workspace buffers: wait until no queued work can still read them
-int ws_drain(bn_ctx* c) {
-    if (c->ws_pending) HIPCHK(c, hipEventSynchronize(c->ws_event));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return BN_OK;
-}
-
 constexpr int kFeSlots = 32;  // slot 0: Miller value, 1: easy-part result, 2..: temporaries
 // batches up to this size take the latency path (segmented Miller loop, Horner
 // + final exponentiation on 16-lane groups); measured crossover with the
@@ -226,40 +183,6 @@ uint32_t build_final_exp(Prog& P) {
     return V;
 }
 
-int reserve(bn_ctx* c, size_t n) {
-    if (n <= c->cap) return BN_OK;
-    n = n < 1024 ? 1024 : n;
-    if (c->cap) {
-        int r = ws_drain(c);
-        if (r) return r;
-    }
-    if (c->coeffs) HIPCHK(c, hipFree(c->coeffs));
-    if (c->paff) HIPCHK(c, hipFree(c->paff));
-    if (c->slots) HIPCHK(c, hipFree(c->slots));
-    if (c->flags) HIPCHK(c, hipFree(c->flags));
-    c->coeffs = nullptr; c->paff = nullptr; c->slots = nullptr; c->flags = nullptr; c->cap = 0;
-    HIPCHK(c, hipMalloc(&c->coeffs, n * (size_t)kCoeffFq * 9 * 4));
-    HIPCHK(c, hipMalloc(&c->paff, n * kPathLanes * 2 * 9 * 4));
-    HIPCHK(c, hipMalloc(&c->slots, n * (size_t)kFeSlots * kSlotWords * 4));
-    HIPCHK(c, hipMalloc(&c->flags, n * kPathLanes));
-    c->cap = n;
-    return BN_OK;
-}
-int stage(bn_ctx* c, size_t bytes) {
-    if (bytes <= c->stage_bytes) return BN_OK;
-    if (c->stage) {
-        int r = ws_drain(c);
-        if (r) return r;
-        HIPCHK(c, hipFree(c->stage));
-    }
-    c->stage = nullptr;
-    c->stage_bytes = 0;
-    HIPCHK(c, hipMalloc(&c->stage, bytes));
-    c->stage_bytes = bytes;
-    return BN_OK;
-}
-hipStream_t pick(bn_ctx* c, void* s) { return s ? (hipStream_t)s : c->stream; }
-
 // ---------------------------------------------------------------- host pipeline helpers
 // pairs per piece of bn_pairing_many's host pipeline: 2^17 once a call has two
 // such pieces, else 2^16 (the pipeline starts above one 2^16 piece).  Piece-size
@@ -268,7 +191,6 @@ hipStream_t pick(bn_ctx* c, void* s) { return s ? (hipStream_t)s : c->stream; }
 // 163-172 / 83 ms for 2^18.
 constexpr size_t kHostPiece = size_t(1) << 17;
 constexpr size_t kHostPieceSmall = size_t(1) << 16;
-size_t round256(size_t b) { return (b + 255) & ~(size_t)255; }
 // pinned bounce buffers of bn_pairing_many (grown, never shrunk); the caller
 // has drained the copy streams, which are the buffers' only device users
 int pin_reserve(bn_ctx* c, size_t bytes) {
@@ -298,35 +220,6 @@ void par_copy(void* dst, const void* src, size_t bytes) {
     }
     memcpy(dst, src, std::min(per, bytes));
     for (auto& t : th) t.join();
-}
-
-// to_affine + the 87 line coefficients of m pairs into c->coeffs / paff / flags:
-// eight lanes per pair (k_prepare_wide, about a third of the step latency) while
-// the batch leaves the GPU underfilled, two lanes per pair (k_prepare) otherwise
-// (scale: 1 for the Miller-loop consumers, 0 for the coefficient export)
-// scaled_inputs: the caller ends in a final exponentiation and outputs nothing but Gt
-// (pairing_batch), so the producers may run on scaled coordinates (pairing.h
-// scaled_inputs: no to_affine inversion); lines and paff are then not the reference's
-static int prepare(bn_ctx* c, const bn_g1* d_p, const bn_g2* d_q, size_t m, int mode, hipStream_t s, int scale = 1,
-                   bool scaled_inputs = false) {
-    if (scaled_inputs && mode == 0 && scale == 1) {
-        if (m <= c->prepare_wide_max)
-            k_prepare_wide_scaled<<<grid_pair(kPrepareWideLanes * m), kPairBlock, 0, s>>>(d_p, d_q, m, c->coeffs,
-                                                                                         c->paff, c->flags);
-        else
-            k_prepare_scaled<<<grid_pair(kPathLanes * m), kPairBlock, 0, s>>>(d_p, d_q, m, c->coeffs, c->paff,
-                                                                              c->flags);
-        HIPCHK(c, hipGetLastError());
-        return BN_OK;
-    }
-    if (m <= c->prepare_wide_max)
-        k_prepare_wide<<<grid_pair(kPrepareWideLanes * m), kPairBlock, 0, s>>>(d_p, d_q, m, c->coeffs, c->paff,
-                                                                              c->flags, c->d_err, mode, scale);
-    else
-        k_prepare<<<grid_pair(kPathLanes * m), kPairBlock, 0, s>>>(d_p, d_q, m, c->coeffs, c->paff, c->flags, c->d_err,
-                                                                   mode, scale);
-    HIPCHK(c, hipGetLastError());
-    return BN_OK;
 }
 
 // Miller values of n pairs into slot 0 (lane-strided, stride = n); n <= c->cap
@@ -436,27 +329,6 @@ static void launch_fe_ds(bn_ctx* c, const uint32_t* f, size_t n, bn_gt* out, uin
     c->tail_epoch = c->tail_epoch + 1 < (1u << 29) ? c->tail_epoch + 1 : 1u;
     const int per = 3 * n * kLatPairs <= c->lat_w1_max ? 3 : 1;  // (lat_w1_max = CUs x kLatPairs)
     k_fe_ds<<<(unsigned)(per * n), kTailBlock, 0, s>>>(f, n, out, ok, c->d_err, c->fe_ds_ws, c->tail_epoch, per);
-}
-// final exponentiation of the n split-layout values of `f` (stride n) -> out
-// (device Gt images): the wide layout for small batches, else the step machine
-// (whose program reads and writes the slots from slot 0: f must be slot 0)
-int run_fe(bn_ctx* c, const uint32_t* f, size_t n, const uint8_t* flags, bn_gt* out, uint8_t* ok, hipStream_t s) {
-    if (n <= c->fe_ds_max && n <= c->fe_wide_max) {  // digit-sliced blocks per value (kernels_tail.hip k_fe_ds)
-        launch_fe_ds(c, f, n, out, ok, s);
-        HIPCHK(c, hipGetLastError());
-        return BN_OK;
-    }
-    if (n <= c->fe_wide_max) {
-        k_fe_wide<<<wide_blocks(n), kBlock, 0, s>>>(f, n, n, out, ok, c->d_err, wide_duo(n) ? 1 : 0);
-        HIPCHK(c, hipGetLastError());
-        return BN_OK;
-    }
-    if (f != c->slots) return fail(c, BN_ERR_INVALID_ARGUMENT, "internal: step-machine FE input must be slot 0");
-    k_fq12_vm<<<grid_pair(kPathLanes * n), kPairBlock, 0, s>>>(c->d_prog, c->fe_steps, c->slots, n);
-    HIPCHK(c, hipGetLastError());
-    k_fe_out<<<grid_for(kPathLanes * n), kBlock, 0, s>>>(c->slots, n, c->fe_out, flags, out, ok, c->d_err);
-    HIPCHK(c, hipGetLastError());
-    return BN_OK;
 }
 
 // ---- pairing_batch / miller_loop_batch: segmented Miller loop + device reduction
@@ -767,9 +639,96 @@ bool use_latency_product(const bn_ctx* c, size_t n) {
     return n <= c->latency_max && n <= c->fe_wide_max && n <= kChunk;
 }
 
+}  // namespace
+
+// ---- shared with capi_products.hip and capi_msm.hip (declared in capi_internal.h)
+int bn::reserve(bn_ctx* c, size_t n) {
+    if (n <= c->cap) return BN_OK;
+    n = n < 1024 ? 1024 : n;
+    if (c->cap) {
+        int r = ws_drain(c);
+        if (r) return r;
+    }
+    if (c->coeffs) HIPCHK(c, hipFree(c->coeffs));
+    if (c->paff) HIPCHK(c, hipFree(c->paff));
+    if (c->slots) HIPCHK(c, hipFree(c->slots));
+    if (c->flags) HIPCHK(c, hipFree(c->flags));
+    c->coeffs = nullptr; c->paff = nullptr; c->slots = nullptr; c->flags = nullptr; c->cap = 0;
+    HIPCHK(c, hipMalloc(&c->coeffs, n * (size_t)kCoeffFq * 9 * 4));
+    HIPCHK(c, hipMalloc(&c->paff, n * kPathLanes * 2 * 9 * 4));
+    HIPCHK(c, hipMalloc(&c->slots, n * (size_t)kFeSlots * kSlotWords * 4));
+    HIPCHK(c, hipMalloc(&c->flags, n * kPathLanes));
+    c->cap = n;
+    return BN_OK;
+}
+int bn::stage(bn_ctx* c, size_t bytes) {
+    if (bytes <= c->stage_bytes) return BN_OK;
+    if (c->stage) {
+        int r = ws_drain(c);
+        if (r) return r;
+        HIPCHK(c, hipFree(c->stage));
+    }
+    c->stage = nullptr;
+    c->stage_bytes = 0;
+    HIPCHK(c, hipMalloc(&c->stage, bytes));
+    c->stage_bytes = bytes;
+    return BN_OK;
+}
+
+// to_affine + the 87 line coefficients of m pairs into c->coeffs / paff / flags:
+// eight lanes per pair (k_prepare_wide, about a third of the step latency) while
+// the batch leaves the GPU underfilled, two lanes per pair (k_prepare) otherwise
+// (scale: 1 for the Miller-loop consumers, 0 for the coefficient export)
+// scaled_inputs: the caller ends in a final exponentiation and outputs nothing but Gt
+// (pairing_batch), so the producers may run on scaled coordinates (pairing.h
+// scaled_inputs: no to_affine inversion); lines and paff are then not the reference's
+int bn::prepare(bn_ctx* c, const bn_g1* d_p, const bn_g2* d_q, size_t m, int mode, hipStream_t s, int scale,
+                bool scaled_inputs) {
+    if (scaled_inputs && mode == 0 && scale == 1) {
+        if (m <= c->prepare_wide_max)
+            k_prepare_wide_scaled<<<grid_pair(kPrepareWideLanes * m), kPairBlock, 0, s>>>(d_p, d_q, m, c->coeffs,
+                                                                                         c->paff, c->flags);
+        else
+            k_prepare_scaled<<<grid_pair(kPathLanes * m), kPairBlock, 0, s>>>(d_p, d_q, m, c->coeffs, c->paff,
+                                                                              c->flags);
+        HIPCHK(c, hipGetLastError());
+        return BN_OK;
+    }
+    if (m <= c->prepare_wide_max)
+        k_prepare_wide<<<grid_pair(kPrepareWideLanes * m), kPairBlock, 0, s>>>(d_p, d_q, m, c->coeffs, c->paff,
+                                                                              c->flags, c->d_err, mode, scale);
+    else
+        k_prepare<<<grid_pair(kPathLanes * m), kPairBlock, 0, s>>>(d_p, d_q, m, c->coeffs, c->paff, c->flags, c->d_err,
+                                                                   mode, scale);
+    HIPCHK(c, hipGetLastError());
+    return BN_OK;
+}
+
+// final exponentiation of the n split-layout values of `f` (stride n) -> out
+// (device Gt images): the wide layout for small batches, else the step machine
+// (whose program reads and writes the slots from slot 0: f must be slot 0)
+int bn::run_fe(bn_ctx* c, const uint32_t* f, size_t n, const uint8_t* flags, bn_gt* out, uint8_t* ok, hipStream_t s) {
+    if (n <= c->fe_ds_max && n <= c->fe_wide_max) {  // digit-sliced blocks per value (kernels_tail.hip k_fe_ds)
+        launch_fe_ds(c, f, n, out, ok, s);
+        HIPCHK(c, hipGetLastError());
+        return BN_OK;
+    }
+    if (n <= c->fe_wide_max) {
+        k_fe_wide<<<wide_blocks(n), kBlock, 0, s>>>(f, n, n, out, ok, c->d_err, wide_duo(n) ? 1 : 0);
+        HIPCHK(c, hipGetLastError());
+        return BN_OK;
+    }
+    if (f != c->slots) return fail(c, BN_ERR_INVALID_ARGUMENT, "internal: step-machine FE input must be slot 0");
+    k_fq12_vm<<<grid_pair(kPathLanes * n), kPairBlock, 0, s>>>(c->d_prog, c->fe_steps, c->slots, n);
+    HIPCHK(c, hipGetLastError());
+    k_fe_out<<<grid_for(kPathLanes * n), kBlock, 0, s>>>(c->slots, n, c->fe_out, flags, out, ok, c->d_err);
+    HIPCHK(c, hipGetLastError());
+    return BN_OK;
+}
+
 // the whole product of n device pairs into *d_out; the caller holds the workspace
-int miller_product_dev(bn_ctx* c, const bn_g1* d_p, const bn_g2* d_q, size_t n, int mode, bn_gt* d_out,
-                       hipStream_t s) {
+int bn::miller_product_dev(bn_ctx* c, const bn_g1* d_p, const bn_g2* d_q, size_t n, int mode, bn_gt* d_out,
+                           hipStream_t s) {
     if (use_latency_product(c, n)) return latency_product(c, d_p, d_q, n, mode, mode == 0, d_out, s);
     const size_t nchunks = (n + kChunk - 1) / kChunk;
     const size_t m0 = n < kChunk ? n : kChunk;
@@ -777,43 +736,48 @@ int miller_product_dev(bn_ctx* c, const bn_g1* d_p, const bn_g2* d_q, size_t n, 
     RET_IF(reserve(c, m0));
     if (nchunks * plan.S > c->cap) return fail(c, BN_ERR_INVALID_ARGUMENT, "too many chunks");
     uint32_t* parts = parts_region(c, nchunks);
-    for (size_t k = 0; k < nchunks; ++k) {
-        const size_t off = k * kChunk, m = (n - off) < kChunk ? (n - off) : kChunk;
-        RET_IF(chunk_product(c, d_p + off, d_q + off, m, mode, mode == 0, plan, parts, nchunks, k, s));
-    }
+    size_t k = 0;
+    for (auto [off, m] : chunks(n))
+        RET_IF(chunk_product(c, d_p + off, d_q + off, m, mode, mode == 0, plan, parts, nchunks, k++, s));
     return finish_product(c, plan, nchunks, mode == 0, d_out, s);
 }
 
-// the device outcome bits of the calls since the last clear; a wave hand-off that
-// ran out of its wait cap (BN_ERR_INTERNAL) fails the call here, whatever else is set
-int check_err(bn_ctx* c, hipStream_t s, int* out_bits) {
-    int h = 0;
-    HIPCHK(c, hipMemcpyAsync(&h, c->d_err, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    *out_bits = h;
-    if (h & (1 << BN_ERR_INTERNAL)) return fail(c, BN_ERR_INTERNAL, "device wave hand-off timed out; result discarded");
-    return BN_OK;
+// The Miller product of n host pairs -> *out (host image), then pairing_batch's
+// final exponentiation when do_fe; mode 0 skips pairs with a zero point, mode 1
+// (miller_loop_batch) rejects them.  Chunks of kChunk pairs are staged in turn.
+// BN_ERR_TO_AFFINE / BN_ERR_FE_ZERO come from the device bits.
+int bn::batch_host(bn_ctx* c, const bn_g1* p, const bn_g2* q, size_t n, int mode, bool do_fe, bn_gt* out) {
+    RET_IF(clear_err(c, c->stream));
+    const size_t m0 = n < kChunk ? n : kChunk;  // the largest chunk is the first
+    void* at[3];
+    RET_IF(stage_regions(c, {m0 * sizeof(bn_g1), m0 * sizeof(bn_g2), sizeof(bn_gt)}, at));
+    bn_g1* dp = (bn_g1*)at[0];
+    bn_g2* dq = (bn_g2*)at[1];
+    bn_gt* d = (bn_gt*)at[2];
+    if (use_latency_product(c, n)) {
+        HIPCHK(c, hipMemcpyAsync(dp, p, n * sizeof(bn_g1), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(dq, q, n * sizeof(bn_g2), hipMemcpyHostToDevice, c->stream));
+        RET_IF(latency_product(c, dp, dq, n, mode, do_fe ? 1 : 0, d, c->stream));
+    } else {
+        const size_t nchunks = (n + kChunk - 1) / kChunk;
+        const SegPlan plan = batch_plan(m0);
+        RET_IF(reserve(c, m0));
+        if (nchunks * plan.S > c->cap) return fail(c, BN_ERR_INVALID_ARGUMENT, "too many chunks");
+        uint32_t* parts = parts_region(c, nchunks);
+        size_t k = 0;
+        for (auto [off, m] : chunks(n)) {
+            HIPCHK(c, hipMemcpyAsync(dp, p + off, m * sizeof(bn_g1), hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(dq, q + off, m * sizeof(bn_g2), hipMemcpyHostToDevice, c->stream));
+            RET_IF(chunk_product(c, dp, dq, m, mode, do_fe ? 1 : 0, plan, parts, nchunks, k, c->stream));
+            if (++k < nchunks) HIPCHK(c, hipStreamSynchronize(c->stream));  // the stage is reused
+        }
+        RET_IF(finish_product(c, plan, nchunks, do_fe, d, c->stream));
+    }
+    HIPCHK(c, hipMemcpyAsync(out, d, sizeof(bn_gt), hipMemcpyDeviceToHost, c->stream));
+    int bits = 0;
+    RET_IF(check_err(c, c->stream, &bits));
+    return outcome(c, bits, kBitToAffine | kBitFeZero);
 }
-int clear_err(bn_ctx* c, hipStream_t s) {
-    HIPCHK(c, hipMemsetAsync(c->d_err, 0, sizeof(int), s));
-    return BN_OK;
-}
-
-}  // namespace
-
-#define CTX_GUARD(ctx)                                 \
-    if (!(ctx)) return BN_ERR_INVALID_ARGUMENT;        \
-    if (!(ctx)->subs.empty())                          \
-        return fail((ctx), BN_ERR_INVALID_ARGUMENT,    \
-                    "not available on a multi-device context; use bn_ctx_device()"); \
-    std::lock_guard<std::mutex> lock_((ctx)->mu);      \
-    HIPCHK(ctx, hipSetDevice((ctx)->device))
-// host-buffer entry points: the lock for the whole call, and the context stream
-// ordered after the workspace's previous user
-#define CTX_GUARD_HOST(ctx)                \
-    CTX_GUARD(ctx);                        \
-    RET_IF(ws_acquire((ctx), (ctx)->stream)); \
-    WsUse ws_use_{(ctx), (ctx)->stream}
 
 // k_g1_mul2 (two chains per lane) once half the batch gives every CU one
 // kPairBlock-thread block: 8.82 -> 8.36 ms at config 3's 2^18
@@ -821,7 +785,7 @@ int clear_err(bn_ctx* c, hipStream_t s) {
 // kPairBlock-thread blocks (two waves on every SIMD, kernels.h issue balance)
 // once the batch gives every CU one such block, else kBlock
 constexpr size_t kG1MulPairBlockMin = (size_t)256 * kPairBlock;
-static void g1_mul_launch(const bn_g1* d_p, const bn_fr* d_k, size_t n, bn_g1* d_out, hipStream_t s) {
+void bn::g1_mul_launch(const bn_g1* d_p, const bn_fr* d_k, size_t n, bn_g1* d_out, hipStream_t s) {
     if ((n + 1) / 2 >= kG1MulPairBlockMin)
         k_g1_mul2<<<grid_pair((n + 1) / 2), kPairBlock, 0, s>>>(d_p, d_k, n, d_out);
     else if (n >= kG1MulPairBlockMin)
@@ -833,7 +797,7 @@ static void g1_mul_launch(const bn_g1* d_p, const bn_fr* d_k, size_t n, bn_g1* d
 // kernel of rounds 1-3 (profiles/r4m_ab_g2_split.txt)
 // (two chains per lane pair, as k_g1_mul2, measured 15 % slower at 2^16: one wave per
 // SIMD; profiles/r5s_ab_g2_mul2.txt, removed after the A/B)
-static void g2_mul_launch(const bn_g2* d_p, const bn_fr* d_k, size_t n, bn_g2* d_out, hipStream_t s) {
+void bn::g2_mul_launch(const bn_g2* d_p, const bn_fr* d_k, size_t n, bn_g2* d_out, hipStream_t s) {
     k_g2_mul_split<<<grid_pair(kPathLanes * n), kPairBlock, 0, s>>>(d_p, d_k, n, d_out);
 }
 
@@ -842,15 +806,13 @@ static int host_mul(bn_ctx* c, const P* p, const bn_fr* k, size_t n, P* out, K l
     CTX_GUARD_HOST(c);
     if (n == 0) return BN_OK;
     if (!p || !k || !out) return fail(c, BN_ERR_INVALID_ARGUMENT, "null buffer");
-    RET_IF(stage(c, n * (2 * sizeof(P) + sizeof(bn_fr))));
-    P* dp = (P*)c->stage;
-    P* dout = dp + n;
-    bn_fr* dk = (bn_fr*)(dout + n);
-    HIPCHK(c, hipMemcpyAsync(dp, p, n * sizeof(P), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(dk, k, n * sizeof(bn_fr), hipMemcpyHostToDevice, c->stream));
-    launch(dp, dk, n, dout, c->stream);
+    void* at[3];
+    RET_IF(stage_regions(c, {n * sizeof(P), n * sizeof(P), n * sizeof(bn_fr)}, at));
+    HIPCHK(c, hipMemcpyAsync(at[0], p, n * sizeof(P), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(at[2], k, n * sizeof(bn_fr), hipMemcpyHostToDevice, c->stream));
+    launch((const P*)at[0], (const bn_fr*)at[2], n, (P*)at[1], c->stream);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(out, dout, n * sizeof(P), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out, at[1], n * sizeof(P), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return BN_OK;
 }
@@ -869,29 +831,20 @@ static int staged(bn_ctx* c, size_t n, std::initializer_list<HostIn> ins, std::i
         if (!b.p) return fail(c, BN_ERR_INVALID_ARGUMENT, "null buffer");
     for (const auto& b : outs)
         if (!b.p) return fail(c, BN_ERR_INVALID_ARGUMENT, "null buffer");
-    for (size_t off = 0; off < n; off += kChunk) {
-        const size_t m = (n - off) < kChunk ? (n - off) : kChunk;
-        size_t bytes = 0;
-        for (const auto& b : ins) bytes += (b.elem * m + 255) & ~(size_t)255;
-        for (const auto& b : outs) bytes += (b.elem * m + 255) & ~(size_t)255;
-        RET_IF(stage(c, bytes));
-        std::vector<void*> dev;
-        uint8_t* at = (uint8_t*)c->stage;
-        for (const auto& b : ins) {
-            HIPCHK(c, hipMemcpyAsync(at, (const uint8_t*)b.p + off * b.elem, m * b.elem, hipMemcpyHostToDevice, c->stream));
-            dev.push_back(at);
-            at += (b.elem * m + 255) & ~(size_t)255;
-        }
-        for (const auto& b : outs) {
-            dev.push_back(at);
-            at += (b.elem * m + 255) & ~(size_t)255;
-        }
+    std::vector<size_t> bytes;
+    std::vector<void*> dev(ins.size() + outs.size());
+    for (auto [off, m] : chunks(n)) {
+        bytes.clear();
+        for (const auto& b : ins) bytes.push_back(b.elem * m);
+        for (const auto& b : outs) bytes.push_back(b.elem * m);
+        RET_IF(stage_regions(c, bytes.data(), bytes.size(), dev.data()));
+        size_t k = 0;
+        for (const auto& b : ins)
+            HIPCHK(c, hipMemcpyAsync(dev[k++], (const uint8_t*)b.p + off * b.elem, m * b.elem, hipMemcpyHostToDevice, c->stream));
         RET_IF(launch(dev.data(), m, c->stream));
         HIPCHK(c, hipGetLastError());
-        size_t k = ins.size();
-        for (const auto& b : outs) {
+        for (const auto& b : outs)
             HIPCHK(c, hipMemcpyAsync((uint8_t*)b.p + off * b.elem, dev[k++], m * b.elem, hipMemcpyDeviceToHost, c->stream));
-        }
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
     return BN_OK;
@@ -1034,10 +987,7 @@ void* bn_ctx_stream(bn_ctx* c) { return c ? (void*)c->stream : nullptr; }
 size_t bn_workspace_bytes(size_t n) { return ws_bytes(n); }
 
 int bn_reserve(bn_ctx* c, size_t n) {
-    if (c && !c->subs.empty()) {
-        for (bn_ctx* d : c->subs) RET_IF(bn_reserve(d, n / c->subs.size() + 1));
-        return BN_OK;
-    }
+    if (is_multi(c)) return for_each_sub(c, [&](bn_ctx* d) { return bn_reserve(d, n / c->subs.size() + 1); });
     CTX_GUARD(c);
     return reserve(c, n < kChunk ? n : kChunk);
 }
@@ -1061,13 +1011,19 @@ static int pairing_many_dev_impl(bn_ctx* c, const bn_g1* d_p, const bn_g2* d_q, 
     RET_IF(reserve(c, n < kChunk ? n : kChunk));
     RET_IF(ws_acquire(c, s));
     WsUse use{c, s};
-    for (size_t off = 0; off < n; off += kChunk) {
-        const size_t m = (n - off) < kChunk ? (n - off) : kChunk;
+    for (auto [off, m] : chunks(n)) {
         std::array<hipEvent_t, 5> ev{};
         if (c->timing)
             for (auto& e : ev) e = take_event(c);
         auto mark = [&](int k) {
             if (c->timing && ev[k]) (void)hipEventRecord(ev[k], s);
+        };
+        // a branch's end: the marks from k on, the launches' outcome, the events kept
+        auto done = [&](int k) -> int {
+            for (; k <= 4; ++k) mark(k);
+            HIPCHK(c, hipGetLastError());
+            if (c->timing) c->ev_marks.push_back(ev);
+            return BN_OK;
         };
         mark(0);
         if (m <= c->fe_wide_max && m <= c->latency_max && m <= c->fe_ds_max) {
@@ -1076,24 +1032,14 @@ static int pairing_many_dev_impl(bn_ctx* c, const bn_g1* d_p, const bn_g2* d_q, 
             launch_latency(c, d_p + off, d_q + off, m, nullptr, slot_region(c, kRegionSeg), 0, s);
             HIPCHK(c, hipGetLastError());
             launch_fe_ds(c, slot_region(c, kRegionSeg), m, d_out + off, nullptr, s);
-            mark(1);
-            mark(2);
-            mark(3);
-            mark(4);
-            HIPCHK(c, hipGetLastError());
-            if (c->timing) c->ev_marks.push_back(ev);
+            RET_IF(done(1));
             continue;
         }
         if (m <= c->fe_wide_max && m <= c->latency_max) {
             // the whole pairing in one launch: line producer + wide Miller loop and FE
             // (kernels_wide.hip k_pairing_latency)
             launch_latency(c, d_p + off, d_q + off, m, d_out + off, nullptr, 0, s);
-            mark(1);
-            mark(2);
-            mark(3);
-            mark(4);
-            HIPCHK(c, hipGetLastError());
-            if (c->timing) c->ev_marks.push_back(ev);
+            RET_IF(done(1));
             continue;
         }
         if (m <= c->fe_wide_max) {
@@ -1107,21 +1053,13 @@ static int pairing_many_dev_impl(bn_ctx* c, const bn_g1* d_p, const bn_g2* d_q, 
             mark(2);
             k_horner_wide<<<wide_blocks(m), kBlock, 0, s>>>(slot_region(c, kRegionSeg), m, plan, 1, d_out + off,
                                                               c->d_err, wide_duo(m) ? 1 : 0);
-            mark(3);
-            mark(4);
-            HIPCHK(c, hipGetLastError());
-            if (c->timing) c->ev_marks.push_back(ev);
+            RET_IF(done(3));
             continue;
         }
         if (c->miller_form == 3 && c->fe_last_out) {
             k_pairing_full<<<grid_pair(kPathLanes * m), kPairBlock, 0, s>>>(d_p + off, d_q + off, m, c->d_prog,
                                                                        c->fe_steps, c->slots, d_out + off, c->d_err);
-            mark(1);
-            mark(2);
-            mark(3);
-            mark(4);
-            HIPCHK(c, hipGetLastError());
-            if (c->timing) c->ev_marks.push_back(ev);
+            RET_IF(done(1));
             continue;
         }
         if (c->miller_form == 1 || c->miller_form == 3) {  // form 3 without fe_last_out: the fused form
@@ -1146,9 +1084,7 @@ static int pairing_many_dev_impl(bn_ctx* c, const bn_g1* d_p, const bn_g2* d_q, 
         mark(3);
         k_fe_out<<<grid_for(kPathLanes * m), kBlock, 0, s>>>(c->slots, m, c->fe_out, c->flags, d_out + off, nullptr,
                                                              c->d_err);
-        mark(4);
-        HIPCHK(c, hipGetLastError());
-        if (c->timing) c->ev_marks.push_back(ev);
+        RET_IF(done(4));
     }
     return BN_OK;
 }
@@ -1182,10 +1118,7 @@ int bn_dev_status(bn_ctx* c, void* stream) {
     RET_IF(clear_err(c, s));
     HIPCHK(c, hipStreamSynchronize(s));
     if (rc) return rc;
-    if (bits & (1 << BN_ERR_INVALID_ARGUMENT))  // bn_pairing_prepared_many_dev: an index past the handle's points
-        return fail(c, BN_ERR_INVALID_ARGUMENT, "a prepared-point index was out of range; that row is zero");
-    if (bits & (1 << BN_ERR_FE_ZERO)) return fail(c, BN_ERR_FE_ZERO, "miller loop cannot produce zero");
-    return BN_OK;
+    return outcome(c, bits, kBitBadIndex | kBitFeZero);
 }
 
 int bn_set_phase_timing(bn_ctx* c, int enable) {
@@ -1265,27 +1198,23 @@ static int pairing_many_host(bn_ctx* c, const bn_g1* p, const bn_g2* q, size_t n
     for (size_t k = np >= 2 ? np - 2 : 0; k < np; ++k) RET_IF(drain(k));
     int bits = 0;
     RET_IF(check_err(c, c->stream, &bits));
-    if (bits & (1 << BN_ERR_FE_ZERO)) return fail(c, BN_ERR_FE_ZERO, "miller loop cannot produce zero");
-    return BN_OK;
+    return outcome(c, bits, kBitFeZero);
 }
 
 // the A/B form ($BN254MI_HOST_PIPELINE=0): hipMemcpyAsync straight from and to
 // the caller's (pageable) buffers, one chunk at a time on the context stream
 static int pairing_many_pageable(bn_ctx* c, const bn_g1* p, const bn_g2* q, size_t n, bn_gt* out) {
-    for (size_t off = 0; off < n; off += kChunk) {
-        const size_t m = (n - off) < kChunk ? (n - off) : kChunk;
-        RET_IF(stage(c, m * (sizeof(bn_g1) + sizeof(bn_g2) + sizeof(bn_gt))));
-        bn_g1* dp = (bn_g1*)c->stage;
-        bn_g2* dq = (bn_g2*)(dp + m);
-        bn_gt* dout = (bn_gt*)(dq + m);
+    for (auto [off, m] : chunks(n)) {
+        void* at[3];
+        RET_IF(stage_regions(c, {m * sizeof(bn_g1), m * sizeof(bn_g2), m * sizeof(bn_gt)}, at));
         RET_IF(clear_err(c, c->stream));
-        HIPCHK(c, hipMemcpyAsync(dp, p + off, m * sizeof(bn_g1), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(dq, q + off, m * sizeof(bn_g2), hipMemcpyHostToDevice, c->stream));
-        RET_IF(pairing_many_dev_impl(c, dp, dq, m, dout, c->stream));
-        HIPCHK(c, hipMemcpyAsync(out + off, dout, m * sizeof(bn_gt), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(at[0], p + off, m * sizeof(bn_g1), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(at[1], q + off, m * sizeof(bn_g2), hipMemcpyHostToDevice, c->stream));
+        RET_IF(pairing_many_dev_impl(c, (bn_g1*)at[0], (bn_g2*)at[1], m, (bn_gt*)at[2], c->stream));
+        HIPCHK(c, hipMemcpyAsync(out + off, at[2], m * sizeof(bn_gt), hipMemcpyDeviceToHost, c->stream));
         int bits = 0;
         RET_IF(check_err(c, c->stream, &bits));
-        if (bits & (1 << BN_ERR_FE_ZERO)) return fail(c, BN_ERR_FE_ZERO, "miller loop cannot produce zero");
+        RET_IF(outcome(c, bits, kBitFeZero));
     }
     return BN_OK;
 }
@@ -1308,90 +1237,32 @@ int bn_pairing_many(bn_ctx* c, const bn_g1* p, const bn_g2* q, size_t n, bn_gt* 
     return rc;
 }
 
-// The Miller product of n host pairs -> *out (host image), then pairing_batch's
-// final exponentiation when do_fe; mode 0 skips pairs with a zero point, mode 1
-// (miller_loop_batch) rejects them.  Chunks of kChunk pairs are staged in turn.
-// BN_ERR_TO_AFFINE / BN_ERR_FE_ZERO come from the device bits.
-static int batch_host(bn_ctx* c, const bn_g1* p, const bn_g2* q, size_t n, int mode, bool do_fe, bn_gt* out) {
-    RET_IF(clear_err(c, c->stream));
-    if (use_latency_product(c, n)) {
-        RET_IF(stage(c, n * (sizeof(bn_g1) + sizeof(bn_g2)) + sizeof(bn_gt)));
-        bn_g1* dp = (bn_g1*)c->stage;
-        bn_g2* dq = (bn_g2*)(dp + n);
-        bn_gt* d = (bn_gt*)(dq + n);
-        HIPCHK(c, hipMemcpyAsync(dp, p, n * sizeof(bn_g1), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(dq, q, n * sizeof(bn_g2), hipMemcpyHostToDevice, c->stream));
-        RET_IF(latency_product(c, dp, dq, n, mode, do_fe ? 1 : 0, d, c->stream));
-        HIPCHK(c, hipMemcpyAsync(out, d, sizeof(bn_gt), hipMemcpyDeviceToHost, c->stream));
-        int bits = 0;
-        RET_IF(check_err(c, c->stream, &bits));
-        if (bits & (1 << BN_ERR_TO_AFFINE)) return fail(c, BN_ERR_TO_AFFINE, "ToAffineConversion");
-        if (bits & (1 << BN_ERR_FE_ZERO)) return fail(c, BN_ERR_FE_ZERO, "miller loop cannot produce zero");
-        return BN_OK;
-    }
-    const size_t nchunks = (n + kChunk - 1) / kChunk;
-    const size_t m0 = n < kChunk ? n : kChunk;
-    const SegPlan plan = batch_plan(m0);
-    RET_IF(reserve(c, m0));
-    if (nchunks * plan.S > c->cap) return fail(c, BN_ERR_INVALID_ARGUMENT, "too many chunks");
-    uint32_t* parts = parts_region(c, nchunks);
-    for (size_t k = 0; k < nchunks; ++k) {
-        const size_t off = k * kChunk, m = (n - off) < kChunk ? (n - off) : kChunk;
-        RET_IF(stage(c, m * (sizeof(bn_g1) + sizeof(bn_g2)) + sizeof(bn_gt)));
-        bn_g1* dp = (bn_g1*)c->stage;
-        bn_g2* dq = (bn_g2*)(dp + m);
-        HIPCHK(c, hipMemcpyAsync(dp, p + off, m * sizeof(bn_g1), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(dq, q + off, m * sizeof(bn_g2), hipMemcpyHostToDevice, c->stream));
-        RET_IF(chunk_product(c, dp, dq, m, mode, do_fe ? 1 : 0, plan, parts, nchunks, k, c->stream));
-        if (k + 1 < nchunks) HIPCHK(c, hipStreamSynchronize(c->stream));  // the stage is reused
-    }
-    bn_gt* d = (bn_gt*)c->stage;  // the stage holds at least one Gt past the inputs
-    RET_IF(finish_product(c, plan, nchunks, do_fe, d, c->stream));
-    HIPCHK(c, hipMemcpyAsync(out, d, sizeof(bn_gt), hipMemcpyDeviceToHost, c->stream));
-    int bits = 0;
-    RET_IF(check_err(c, c->stream, &bits));
-    if (bits & (1 << BN_ERR_TO_AFFINE)) return fail(c, BN_ERR_TO_AFFINE, "ToAffineConversion");
-    if (bits & (1 << BN_ERR_FE_ZERO)) return fail(c, BN_ERR_FE_ZERO, "miller loop cannot produce zero");
-    return BN_OK;
-}
-
 // the Miller product of n host pairs on one single-device context (its lock held)
 int bn_internal_miller_product(bn_ctx* c, const bn_g1* p, const bn_g2* q, size_t n, int mode, bn_gt* result) {
     CTX_GUARD_HOST(c);
     return batch_host(c, p, q, n, mode, false, result);
 }
 
-void bn_internal_gt_one(bn_gt* out);
-static void gt_one(bn_gt* out) { bn_internal_gt_one(out); }
-void bn_internal_gt_one(bn_gt* out) {  // Fq12::one() image: c0.c0.c0 = R mod p
-    memset(out, 0, sizeof(bn_gt));
-    out->c[0].l[0] = 0xd35d438dc58f0d9dull;
-    out->c[0].l[1] = 0x0a78eb28f5c70b3dull;
-    out->c[0].l[2] = 0x666ea36f7879462cull;
-    out->c[0].l[3] = 0x0e0a77c19a07df2full;
-}
+void bn_internal_gt_one(bn_gt* out) { gt_one(out); }
 
 // final exponentiation of n host images; ok may be null
 static int final_exp_host(bn_ctx* c, const bn_gt* f, size_t n, bn_gt* out, uint8_t* ok, int* zero_seen) {
     *zero_seen = 0;
-    for (size_t off = 0; off < n; off += kChunk) {
-        const size_t m = (n - off) < kChunk ? (n - off) : kChunk;
+    for (auto [off, m] : chunks(n)) {
         RET_IF(reserve(c, m));
-        RET_IF(stage(c, m * (2 * sizeof(bn_gt) + 1)));
-        bn_gt* din = (bn_gt*)c->stage;
-        bn_gt* dout = din + m;
-        uint8_t* dok = (uint8_t*)(dout + m);
-        HIPCHK(c, hipMemcpyAsync(din, f + off, m * sizeof(bn_gt), hipMemcpyHostToDevice, c->stream));
-        k_gt_load<<<grid_for(kPathLanes * m), kBlock, 0, c->stream>>>(din, m, c->slots);
+        void* at[3];  // in, out, ok
+        RET_IF(stage_regions(c, {m * sizeof(bn_gt), m * sizeof(bn_gt), m}, at));
+        HIPCHK(c, hipMemcpyAsync(at[0], f + off, m * sizeof(bn_gt), hipMemcpyHostToDevice, c->stream));
+        k_gt_load<<<grid_for(kPathLanes * m), kBlock, 0, c->stream>>>((const bn_gt*)at[0], m, c->slots);
         HIPCHK(c, hipGetLastError());
-        RET_IF(run_fe(c, c->slots, m, nullptr, dout, dok, c->stream));
-        HIPCHK(c, hipMemcpyAsync(out + off, dout, m * sizeof(bn_gt), hipMemcpyDeviceToHost, c->stream));
-        if (ok) HIPCHK(c, hipMemcpyAsync(ok + off, dok, m, hipMemcpyDeviceToHost, c->stream));
+        RET_IF(run_fe(c, c->slots, m, nullptr, (bn_gt*)at[1], (uint8_t*)at[2], c->stream));
+        HIPCHK(c, hipMemcpyAsync(out + off, at[1], m * sizeof(bn_gt), hipMemcpyDeviceToHost, c->stream));
+        if (ok) HIPCHK(c, hipMemcpyAsync(ok + off, at[2], m, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
     int bits = 0;
     RET_IF(check_err(c, c->stream, &bits));
-    *zero_seen = (bits & (1 << BN_ERR_FE_ZERO)) != 0;
+    *zero_seen = (bits & kBitFeZero) != 0;
     return BN_OK;
 }
 
@@ -1426,9 +1297,6 @@ static int batch_dev(bn_ctx* c, const bn_g1* d_p, const bn_g2* d_q, size_t n, bn
     WsUse use{c, s};
     HIPCHK(c, hipMemsetAsync(c->d_err, 0, sizeof(int), s));
     if (n == 0) {  // pairing_batch: mod.rs:922-924; the shared loop starts from one (mod.rs:610)
-        // a constant-initialized, read-only image: no thread ever writes it
-        static const bn_gt kGtOne = {{{{0xd35d438dc58f0d9dull, 0x0a78eb28f5c70b3dull, 0x666ea36f7879462cull,
-                                        0x0e0a77c19a07df2full}}}};
         HIPCHK(c, hipMemcpyAsync(d_out, &kGtOne, sizeof(bn_gt), hipMemcpyHostToDevice, s));
     } else {
         RET_IF(miller_product_dev(c, d_p, d_q, n, mode, d_out, s));
@@ -1449,239 +1317,22 @@ int bn_miller_loop_batch_dev(bn_ctx* c, const bn_g2* d_q, const bn_g1* d_p, size
     CTX_GUARD(c);
     return batch_dev(c, d_p, d_q, n, d_out, d_status, 1, pick(c, stream));
 }
-// ---- many products in one call (bn_pairing_batch_many)
-// One unit of a call's work, products [j0, j1).  packed: one launch set of the packed
-// path -- k_prepare(_wide)_scaled over its terms, k_miller_products (a lane pair per
-// product), the final exponentiation over its products; every product has at most
-// kProductLaneMax terms, together at most products_chunk (a single product may exceed
-// that), and there are at most kChunk products.  Otherwise j1 == j0 + 1: one product on
-// the single-product path (miller_product_dev in mode 0, as bn_pairing_batch_dev).
-struct ProductsItem {
-    size_t j0, j1;
-    bool packed;
-};
-static std::vector<ProductsItem> products_plan(const bn_ctx* c, const size_t* off, size_t m) {
-    size_t nshort = 0;
-    for (size_t j = 0; j < m; ++j) nshort += off[j + 1] - off[j] <= (size_t)kProductLaneMax ? 1 : 0;
-    // fewer short products than products_min: each alone (a lone two-lane chain takes
-    // milliseconds where the single-product path's 16-lane groups take 0.8 ms)
-    const bool pack = nshort > 0 && nshort >= c->products_min;
-    std::vector<ProductsItem> items;
-    for (size_t j = 0; j < m;) {
-        if (!pack || off[j + 1] - off[j] > (size_t)kProductLaneMax) {
-            items.push_back({j, j + 1, false});
-            ++j;
-            continue;
-        }
-        size_t e = j + 1;
-        while (e < m && e - j < kChunk && off[e + 1] - off[e] <= (size_t)kProductLaneMax &&
-               off[e + 1] - off[j] <= c->products_chunk)
-            ++e;
-        items.push_back({j, e, true});
-        j = e;
-    }
-    return items;
-}
-// offsets: m + 1 host entries, non-decreasing from 0; then the buffers (n = offsets[m])
-static int products_check(bn_ctx* c, const void* p, const void* q, const size_t* off, size_t m, const void* out) {
-    if (!off) return fail(c, BN_ERR_INVALID_ARGUMENT, "null offsets");
-    if (off[0] != 0) return fail(c, BN_ERR_INVALID_ARGUMENT, "offsets[0] must be 0");
-    for (size_t j = 0; j < m; ++j)
-        if (off[j + 1] < off[j]) return fail(c, BN_ERR_INVALID_ARGUMENT, "offsets must not decrease");
-    if (!out || (off[m] && (!p || !q))) return fail(c, BN_ERR_INVALID_ARGUMENT, "null buffer");
-    return BN_OK;
-}
-// the workspace for every item of the call: the larger of a launch set's terms (coeffs,
-// flags) and products (slots); a lone product's chunk
-static int products_reserve(bn_ctx* c, const size_t* off, const std::vector<ProductsItem>& items) {
-    size_t need = 1;
-    for (const ProductsItem& it : items) {
-        const size_t nt = off[it.j1] - off[it.j0];
-        need = std::max(need, it.packed ? std::max(nt, it.j1 - it.j0) : std::min(nt, kChunk));
-    }
-    return reserve(c, need);
-}
-// The chunk-relative 32-bit offsets of every launch set of the call (set k: j1 - j0 + 1
-// words from at[k]) -> prod_off_d, in one copy on s in front of the call's kernels.  The
-// pinned source is rewritten by the next call, which first waits for this copy (not for
-// the kernels behind it).  The caller has ordered s after the workspace's previous user.
-static int products_offsets_upload(bn_ctx* c, const size_t* off, const std::vector<ProductsItem>& items,
-                                   hipStream_t s, std::vector<size_t>* at) {
-    size_t words = 0;
-    at->assign(items.size(), 0);
-    for (size_t k = 0; k < items.size(); ++k)
-        if (items[k].packed) {
-            (*at)[k] = words;
-            words += items[k].j1 - items[k].j0 + 1;
-        }
-    if (!words) return BN_OK;
-    if (c->prod_off_pending) {
-        HIPCHK(c, hipEventSynchronize(c->prod_off_event));
-        c->prod_off_pending = false;
-    }
-    if (words > c->prod_off_cap) {
-        RET_IF(ws_drain(c));  // queued kernels may still read the old buffer
-        if (c->prod_off_h) HIPCHK(c, hipHostFree(c->prod_off_h));
-        if (c->prod_off_d) HIPCHK(c, hipFree(c->prod_off_d));
-        c->prod_off_h = nullptr; c->prod_off_d = nullptr; c->prod_off_cap = 0;
-        const size_t cap = std::max<size_t>(words, 4096);
-        HIPCHK(c, hipHostMalloc(&c->prod_off_h, cap * 4, hipHostMallocDefault));
-        HIPCHK(c, hipMalloc(&c->prod_off_d, cap * 4));
-        c->prod_off_cap = cap;
-    }
-    for (size_t k = 0; k < items.size(); ++k)
-        if (items[k].packed)
-            for (size_t j = items[k].j0; j <= items[k].j1; ++j)
-                c->prod_off_h[(*at)[k] + (j - items[k].j0)] = (uint32_t)(off[j] - off[items[k].j0]);
-    HIPCHK(c, hipMemcpyAsync(c->prod_off_d, c->prod_off_h, words * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipEventRecord(c->prod_off_event, s));
-    c->prod_off_pending = true;
-    return BN_OK;
-}
-// Threads per block of k_miller_products.  A launch set of fewer lane pairs than fill the
-// GPU with kPairBlock-thread blocks leaves whole CUs idle while the busy ones run two waves
-// per SIMD, each at about half the lone-wave rate: smaller blocks spread the same waves
-// over more SIMDs.  $BN254MI_PRODUCTS_BLOCK (128, 256 or 512) forces one size (A/B).
-static unsigned products_block(const bn_ctx* c, size_t lanes) {
-    if (c->products_block) return c->products_block;
-    const size_t cus = c->lat_w1_max / kLatPairs;  // the device's CU count (bn_ctx_create)
-    if (lanes >= cus * kPairBlock) return kPairBlock;
-    return lanes >= cus * 256 ? 256 : 128;
-}
-// one launch set: the nt device pairs at d_p / d_q, mc products cut by d_off (mc + 1
-// device words) -> d_out[0 .. mc)
-static int products_set_dev(bn_ctx* c, const bn_g1* d_p, const bn_g2* d_q, size_t nt, const uint32_t* d_off, size_t mc,
-                            bn_gt* d_out, hipStream_t s) {
-    if (nt > c->cap || mc > c->cap) return fail(c, BN_ERR_INTERNAL, "launch set exceeds the workspace");
-    // only Gt leaves: the producers on scaled inputs (no pair at all: nothing to prepare)
-    if (nt) RET_IF(prepare(c, d_p, d_q, nt, 0, s, 1, true));
-    const size_t lanes = kPathLanes * mc;
-    const unsigned block = products_block(c, lanes);
-    k_miller_products<<<(unsigned)((lanes + block - 1) / block), block, 0, s>>>(c->coeffs, c->flags, nt, d_off, mc,
-                                                                               c->slots);
-    HIPCHK(c, hipGetLastError());
-    return run_fe(c, c->slots, mc, nullptr, d_out, nullptr, s);
-}
-static const bn_gt kGtOneImage = {{{{0xd35d438dc58f0d9dull, 0x0a78eb28f5c70b3dull, 0x666ea36f7879462cull,
-                                     0x0e0a77c19a07df2full}}}};  // read-only: no thread ever writes it
-static int products_dev(bn_ctx* c, const bn_g1* d_p, const bn_g2* d_q, const size_t* off, size_t m, bn_gt* d_out,
-                        hipStream_t s) {
-    const std::vector<ProductsItem> items = products_plan(c, off, m);
-    RET_IF(products_reserve(c, off, items));
-    RET_IF(ws_acquire(c, s));
-    WsUse use{c, s};
-    std::vector<size_t> at;
-    RET_IF(products_offsets_upload(c, off, items, s, &at));
-    for (size_t k = 0; k < items.size(); ++k) {
-        const ProductsItem& it = items[k];
-        const size_t lo = off[it.j0], nt = off[it.j1] - lo;
-        if (it.packed)
-            RET_IF(products_set_dev(c, d_p + lo, d_q + lo, nt, c->prod_off_d + at[k], it.j1 - it.j0, d_out + it.j0, s));
-        else if (nt == 0)  // mod.rs:922-924
-            HIPCHK(c, hipMemcpyAsync(d_out + it.j0, &kGtOneImage, sizeof(bn_gt), hipMemcpyHostToDevice, s));
-        else
-            RET_IF(miller_product_dev(c, d_p + lo, d_q + lo, nt, 0, d_out + it.j0, s));
-    }
-    return BN_OK;
-}
-int bn_pairing_batch_many_dev(bn_ctx* c, const bn_g1* d_p, const bn_g2* d_q, const size_t* offsets, size_t m,
-                              bn_gt* d_out, void* stream) {
-    CTX_GUARD(c);
-    if (m == 0) return BN_OK;
-    RET_IF(products_check(c, d_p, d_q, offsets, m, d_out));
-    return products_dev(c, d_p, d_q, offsets, m, d_out, pick(c, stream));
-}
-// The host form: every item staged in turn through the context's stage (its pairs, then
-// its products' Gt), the device outcome read after each (batch_host clears the word for
-// its own product), BN_ERR_FE_ZERO reported at the end with every row written.
-static int products_host(bn_ctx* c, const bn_g1* p, const bn_g2* q, const size_t* off, size_t m, bn_gt* out) {
-    const std::vector<ProductsItem> items = products_plan(c, off, m);
-    RET_IF(products_reserve(c, off, items));
-    std::vector<size_t> at;
-    RET_IF(products_offsets_upload(c, off, items, c->stream, &at));
-    bool zero = false;
-    for (size_t k = 0; k < items.size(); ++k) {
-        const ProductsItem& it = items[k];
-        const size_t lo = off[it.j0], nt = off[it.j1] - lo, mc = it.j1 - it.j0;
-        if (!it.packed) {
-            if (nt == 0) {  // mod.rs:922-924
-                gt_one(out + it.j0);
-                continue;
-            }
-            const int rc = batch_host(c, p + lo, q + lo, nt, 0, true, out + it.j0);
-            if (rc == BN_ERR_FE_ZERO) zero = true;
-            else if (rc) return rc;
-            continue;
-        }
-        RET_IF(clear_err(c, c->stream));
-        RET_IF(stage(c, nt * (sizeof(bn_g1) + sizeof(bn_g2)) + mc * sizeof(bn_gt)));
-        bn_g1* dp = (bn_g1*)c->stage;
-        bn_g2* dq = (bn_g2*)(dp + nt);
-        bn_gt* d = (bn_gt*)(dq + nt);
-        if (nt) {
-            HIPCHK(c, hipMemcpyAsync(dp, p + lo, nt * sizeof(bn_g1), hipMemcpyHostToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync(dq, q + lo, nt * sizeof(bn_g2), hipMemcpyHostToDevice, c->stream));
-        }
-        RET_IF(products_set_dev(c, dp, dq, nt, c->prod_off_d + at[k], mc, d, c->stream));
-        HIPCHK(c, hipMemcpyAsync(out + it.j0, d, mc * sizeof(bn_gt), hipMemcpyDeviceToHost, c->stream));
-        int bits = 0;
-        RET_IF(check_err(c, c->stream, &bits));  // synchronizes: the stage is reused
-        if (bits & (1 << BN_ERR_FE_ZERO)) zero = true;
-    }
-    if (zero) return fail(c, BN_ERR_FE_ZERO, "miller loop cannot produce zero");
-    return BN_OK;
-}
-int bn_pairing_batch_many(bn_ctx* c, const bn_g1* p, const bn_g2* q, const size_t* offsets, size_t m, bn_gt* out) {
-    if (c && !c->subs.empty()) return bn_multi_pairing_batch_many(c, p, q, offsets, m, out);
-    CTX_GUARD_HOST(c);
-    if (m == 0) return BN_OK;
-    RET_IF(products_check(c, p, q, offsets, m, out));
-    return products_host(c, p, q, offsets, m, out);
-}
-int bn_set_products_min(bn_ctx* c, size_t m) {
-    if (c && !c->subs.empty()) {
-        for (bn_ctx* d : c->subs) RET_IF(bn_set_products_min(d, m));
-        return BN_OK;
-    }
-    CTX_GUARD(c);
-    c->products_min = m;
-    return BN_OK;
-}
-int bn_set_products_chunk(bn_ctx* c, size_t terms) {
-    if (c && !c->subs.empty()) {
-        for (bn_ctx* d : c->subs) RET_IF(bn_set_products_chunk(d, terms));
-        return BN_OK;
-    }
-    CTX_GUARD(c);
-    if (terms > kChunk) return fail(c, BN_ERR_INVALID_ARGUMENT, "at most kChunk terms per launch set");
-    c->products_chunk = terms ? terms : kChunk;
-    return BN_OK;
-}
 
 int bn_set_latency_max(bn_ctx* c, size_t n) {
-    if (c && !c->subs.empty()) {
-        for (bn_ctx* d : c->subs) RET_IF(bn_set_latency_max(d, n));
-        return BN_OK;
-    }
+    if (is_multi(c)) return for_each_sub(c, [&](bn_ctx* d) { return bn_set_latency_max(d, n); });
     CTX_GUARD(c);
     c->latency_max = n;
     return BN_OK;
 }
 int bn_set_fq12_op_unit(bn_ctx* c, int unit) {
-    if (c && !c->subs.empty()) {
-        for (bn_ctx* d : c->subs) RET_IF(bn_set_fq12_op_unit(d, unit));
-        return BN_OK;
-    }
+    if (is_multi(c)) return for_each_sub(c, [&](bn_ctx* d) { return bn_set_fq12_op_unit(d, unit); });
     CTX_GUARD(c);
     if (unit != 0 && unit != 1) return fail(c, BN_ERR_INVALID_ARGUMENT, "unit must be 0 or 1");
     c->fq12_op_unit = unit;
     return BN_OK;
 }
 int bn_set_fe_wide_max(bn_ctx* c, size_t n) {
-    if (c && !c->subs.empty()) {
-        for (bn_ctx* d : c->subs) RET_IF(bn_set_fe_wide_max(d, n));
-        return BN_OK;
-    }
+    if (is_multi(c)) return for_each_sub(c, [&](bn_ctx* d) { return bn_set_fe_wide_max(d, n); });
     CTX_GUARD(c);
     c->fe_wide_max = n;
     return BN_OK;
@@ -1702,19 +1353,16 @@ int bn_miller_loop_many(bn_ctx* c, const bn_g1* p, const bn_g2* q, size_t n, bn_
     CTX_GUARD_HOST(c);
     if (n == 0) return BN_OK;
     if (!p || !q || !out) return fail(c, BN_ERR_INVALID_ARGUMENT, "null buffer");
-    for (size_t off = 0; off < n; off += kChunk) {
-        const size_t m = (n - off) < kChunk ? (n - off) : kChunk;
+    for (auto [off, m] : chunks(n)) {
         RET_IF(reserve(c, m));
-        RET_IF(stage(c, m * (sizeof(bn_g1) + sizeof(bn_g2) + sizeof(bn_gt))));
-        bn_g1* dp = (bn_g1*)c->stage;
-        bn_g2* dq = (bn_g2*)(dp + m);
-        bn_gt* dout = (bn_gt*)(dq + m);
-        HIPCHK(c, hipMemcpyAsync(dp, p + off, m * sizeof(bn_g1), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(dq, q + off, m * sizeof(bn_g2), hipMemcpyHostToDevice, c->stream));
-        RET_IF(miller_values(c, dp, dq, m, 0, c->stream));
-        k_gt_store<<<grid_for(kPathLanes * m), kBlock, 0, c->stream>>>(c->slots, m, m, dout);
+        void* at[3];
+        RET_IF(stage_regions(c, {m * sizeof(bn_g1), m * sizeof(bn_g2), m * sizeof(bn_gt)}, at));
+        HIPCHK(c, hipMemcpyAsync(at[0], p + off, m * sizeof(bn_g1), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(at[1], q + off, m * sizeof(bn_g2), hipMemcpyHostToDevice, c->stream));
+        RET_IF(miller_values(c, (const bn_g1*)at[0], (const bn_g2*)at[1], m, 0, c->stream));
+        k_gt_store<<<grid_for(kPathLanes * m), kBlock, 0, c->stream>>>(c->slots, m, m, (bn_gt*)at[2]);
         HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(out + off, dout, m * sizeof(bn_gt), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(out + off, at[2], m * sizeof(bn_gt), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
     return BN_OK;
@@ -1725,414 +1373,26 @@ int bn_g2_precompute_many(bn_ctx* c, const bn_g2* q, size_t n, bn_fq2* out) {
     if (n == 0) return BN_OK;
     if (!q || !out) return fail(c, BN_ERR_INVALID_ARGUMENT, "null buffer");
     RET_IF(clear_err(c, c->stream));
-    bn_g1 one;  // k_prepare converts a G1 point too; G1::one() (z = 1) is never zero
-    memset(&one, 0, sizeof one);
-    one.x.l[0] = 0xd35d438dc58f0d9dull, one.x.l[1] = 0x0a78eb28f5c70b3dull;  // Fq::one(): R mod p
-    one.x.l[2] = 0x666ea36f7879462cull, one.x.l[3] = 0x0e0a77c19a07df2full;
-    one.z = one.x;
-    for (size_t off = 0; off < n; off += kChunk) {
-        const size_t m = (n - off) < kChunk ? (n - off) : kChunk;
+    // k_prepare converts a G1 point too; G1::one() (x = z = 1, y = 0 here) is never zero
+    const bn_g1 one = {kFqOne, {}, kFqOne};
+    for (auto [off, m] : chunks(n)) {
         RET_IF(reserve(c, m));
         const size_t out_bytes = m * (size_t)BN_NUM_COEFFS * 3 * sizeof(bn_fq2);
-        RET_IF(stage(c, m * (sizeof(bn_g1) + sizeof(bn_g2)) + out_bytes));
-        bn_g1* dp = (bn_g1*)c->stage;
-        bn_g2* dq = (bn_g2*)(dp + m);
-        bn_fq2* dout = (bn_fq2*)(dq + m);
+        void* at[3];
+        RET_IF(stage_regions(c, {m * sizeof(bn_g1), m * sizeof(bn_g2), out_bytes}, at));
         std::vector<bn_g1> ones(m, one);
-        HIPCHK(c, hipMemcpyAsync(dp, ones.data(), m * sizeof(bn_g1), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(dq, q + off, m * sizeof(bn_g2), hipMemcpyHostToDevice, c->stream));
-        RET_IF(prepare(c, dp, dq, m, 1, c->stream, 0));  // the reference's (unscaled) coefficients
-        k_coeffs_store<<<grid_for(kPathLanes * m), kBlock, 0, c->stream>>>(c->coeffs, m, dout);
+        HIPCHK(c, hipMemcpyAsync(at[0], ones.data(), m * sizeof(bn_g1), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(at[1], q + off, m * sizeof(bn_g2), hipMemcpyHostToDevice, c->stream));
+        // the reference's (unscaled) coefficients
+        RET_IF(prepare(c, (const bn_g1*)at[0], (const bn_g2*)at[1], m, 1, c->stream, 0));
+        k_coeffs_store<<<grid_for(kPathLanes * m), kBlock, 0, c->stream>>>(c->coeffs, m, (bn_fq2*)at[2]);
         HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(out + off * BN_NUM_COEFFS * 3, dout, out_bytes, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(out + off * BN_NUM_COEFFS * 3, at[2], out_bytes, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
     int bits = 0;
     RET_IF(check_err(c, c->stream, &bits));
-    if (bits & (1 << BN_ERR_TO_AFFINE)) return fail(c, BN_ERR_TO_AFFINE, "ToAffineConversion");
-    return BN_OK;
-}
-
-// ---------------------------------------------------------------- prepared G2 points
-// Fills a new handle with the coefficients of the nq points at q (host memory, or device
-// memory when q_dev) on stream s: per chunk, k_prepare(_wide) with G1::one() as the G1 side
-// (mode 0: a zero q is flagged, not an error; scale 0: the reference's coefficients, as
-// bn_g2_precompute_many) into the workspace, then k_prepared_repack into the table.  The
-// caller holds the lock and has ordered s after the workspace's previous user.
-static int g2_prepare_fill(bn_ctx* c, bn_g2_prepared* h, const bn_g2* q, bool q_dev, hipStream_t s) {
-    const size_t nq = h->nq;
-    HIPCHK(c, hipMalloc(&h->table, nq * (size_t)kPreparedWords * 4));
-    HIPCHK(c, hipMalloc(&h->zero, nq));
-    const size_t mmax = nq < kChunk ? nq : kChunk;
-    RET_IF(reserve(c, mmax));
-    const size_t o_q = round256(mmax * sizeof(bn_g1));
-    RET_IF(stage(c, o_q + (q_dev ? 0 : mmax * sizeof(bn_g2))));
-    for (size_t off = 0; off < nq; off += kChunk) {
-        const size_t m = (nq - off) < kChunk ? (nq - off) : kChunk;
-        bn_g1* dp = (bn_g1*)c->stage;
-        const bn_g2* dq = q + off;
-        if (!q_dev) {
-            bn_g2* st = (bn_g2*)((uint8_t*)c->stage + o_q);
-            HIPCHK(c, hipMemcpyAsync(st, q + off, m * sizeof(bn_g2), hipMemcpyHostToDevice, s));
-            dq = st;
-        }
-        k_g1_fill_one<<<grid_for(m), kBlock, 0, s>>>(dp, m);
-        RET_IF(prepare(c, dp, dq, m, 0, s, 0));
-        k_prepared_repack<<<grid_for(kPathLanes * m), kBlock, 0, s>>>(c->coeffs, c->flags, m,
-                                                                     h->table + off * (size_t)kPreparedWords,
-                                                                     h->zero + off);
-        HIPCHK(c, hipGetLastError());
-    }
-    return BN_OK;
-}
-static int g2_prepare(bn_ctx* c, const bn_g2* q, bool q_dev, size_t nq, bn_g2_prepared** out, hipStream_t s) {
-    bn_g2_prepared* h = new bn_g2_prepared();
-    h->nq = nq;
-    int rc = g2_prepare_fill(c, h, q, q_dev, s);
-    if (rc == BN_OK && !q_dev && hipStreamSynchronize(s) != hipSuccess) rc = fail(c, BN_ERR_HIP, "hipStreamSynchronize");
-    if (rc != BN_OK) {
-        (void)hipStreamSynchronize(s);  // nothing queued may still write the table
-        if (h->table) (void)hipFree(h->table);
-        if (h->zero) (void)hipFree(h->zero);
-        delete h;
-        return rc;
-    }
-    c->prepared.push_back(h);
-    *out = h;
-    return BN_OK;
-}
-// refused before anything is read: a NULL q or out, nq outside 1 .. 2^16
-static int g2_prepare_args(bn_ctx* c, const void* q, size_t nq, bn_g2_prepared** out) {
-    if (!q || !out) return fail(c, BN_ERR_INVALID_ARGUMENT, "null buffer");
-    if (nq < 1 || nq > kPreparedMax) return fail(c, BN_ERR_INVALID_ARGUMENT, "nq outside 1 .. 2^16");
-    return BN_OK;
-}
-
-int bn_g2_prepare(bn_ctx* c, const bn_g2* q, size_t nq, bn_g2_prepared** out) {
-    if (out) *out = nullptr;
-    CTX_GUARD(c);
-    RET_IF(g2_prepare_args(c, q, nq, out));
-    RET_IF(ws_acquire(c, c->stream));
-    WsUse use{c, c->stream};
-    return g2_prepare(c, q, false, nq, out, c->stream);
-}
-
-int bn_g2_prepare_dev(bn_ctx* c, const bn_g2* d_q, size_t nq, bn_g2_prepared** out, void* stream) {
-    if (out) *out = nullptr;
-    CTX_GUARD(c);
-    RET_IF(g2_prepare_args(c, d_q, nq, out));
-    const hipStream_t s = pick(c, stream);
-    // (the workspace may grow in the fill: reserve() drains the previous users itself)
-    RET_IF(ws_acquire(c, s));
-    WsUse use{c, s};
-    return g2_prepare(c, d_q, true, nq, out, s);
-}
-
-size_t bn_g2_prepared_count(const bn_g2_prepared* h) { return h ? h->nq : 0; }
-
-// a live handle of this context (looked up, not dereferenced: another context's handle,
-// or a destroyed one, is refused)
-static bool prepared_live(const bn_ctx* c, const bn_g2_prepared* h) {
-    return h && std::find(c->prepared.begin(), c->prepared.end(), h) != c->prepared.end();
-}
-
-int bn_g2_prepared_destroy(bn_ctx* c, bn_g2_prepared* h) {
-    CTX_GUARD(c);
-    if (!prepared_live(c, h)) return fail(c, BN_ERR_INVALID_ARGUMENT, "not a live prepared handle of this context");
-    RET_IF(ws_drain(c));  // every call that reads the table has recorded ws_event behind its work
-    c->prepared.erase(std::find(c->prepared.begin(), c->prepared.end(), h));
-    (void)hipFree(h->table);
-    (void)hipFree(h->zero);
-    delete h;
-    return BN_OK;
-}
-
-// n pairings (fe) or Miller values of device arrays against the handle on stream s, every n
-// through k_pairing_prepared in launch sets of kChunk; the caller holds the lock
-static int prepared_dev_impl(bn_ctx* c, const bn_g1* d_p, const bn_g2_prepared* h, const uint32_t* d_qidx, size_t n,
-                             bn_gt* d_out, bool fe, hipStream_t s) {
-    if (fe) {
-        // the kernel returns the step program's last result as the Gt, as k_pairing_full
-        if (!c->fe_last_out) return fail(c, BN_ERR_INTERNAL, "step program does not end in its output");
-        RET_IF(reserve(c, n < kChunk ? n : kChunk));
-    }
-    RET_IF(ws_acquire(c, s));
-    WsUse use{c, s};
-    for (size_t off = 0; off < n; off += kChunk) {
-        const size_t m = (n - off) < kChunk ? (n - off) : kChunk;
-        launch_pairing_prepared(fe, d_p + off, h->table, h->zero, (uint32_t)h->nq, d_qidx ? d_qidx + off : nullptr, m,
-                                c->d_prog, c->fe_steps, c->slots, d_out + off, c->d_err, s);
-        HIPCHK(c, hipGetLastError());
-    }
-    return BN_OK;
-}
-static int prepared_args(bn_ctx* c, const void* p, const bn_g2_prepared* h, const void* out) {
-    if (!p || !out || !h) return fail(c, BN_ERR_INVALID_ARGUMENT, "null buffer");
-    if (!prepared_live(c, h)) return fail(c, BN_ERR_INVALID_ARGUMENT, "not a live prepared handle of this context");
-    return BN_OK;
-}
-// the host forms: indices checked first, then per chunk stage, copy, launch, read back,
-// synchronize (the device bits read per chunk, as bn_pairing_many's pageable form)
-static int prepared_host(bn_ctx* c, const bn_g1* p, const bn_g2_prepared* h, const uint32_t* qidx, size_t n,
-                         bn_gt* out, bool fe) {
-    if (qidx)
-        for (size_t i = 0; i < n; ++i)
-            if (qidx[i] >= h->nq) return fail(c, BN_ERR_INVALID_ARGUMENT, "prepared-point index out of range");
-    for (size_t off = 0; off < n; off += kChunk) {
-        const size_t m = (n - off) < kChunk ? (n - off) : kChunk;
-        const size_t o_idx = round256(m * sizeof(bn_g1));
-        const size_t o_out = o_idx + round256(m * sizeof(uint32_t));
-        RET_IF(stage(c, o_out + m * sizeof(bn_gt)));
-        uint8_t* base = (uint8_t*)c->stage;
-        bn_g1* dp = (bn_g1*)base;
-        uint32_t* didx = (uint32_t*)(base + o_idx);
-        bn_gt* dout = (bn_gt*)(base + o_out);
-        RET_IF(clear_err(c, c->stream));
-        HIPCHK(c, hipMemcpyAsync(dp, p + off, m * sizeof(bn_g1), hipMemcpyHostToDevice, c->stream));
-        if (qidx) HIPCHK(c, hipMemcpyAsync(didx, qidx + off, m * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-        RET_IF(prepared_dev_impl(c, dp, h, qidx ? didx : nullptr, m, dout, fe, c->stream));
-        HIPCHK(c, hipMemcpyAsync(out + off, dout, m * sizeof(bn_gt), hipMemcpyDeviceToHost, c->stream));
-        int bits = 0;
-        RET_IF(check_err(c, c->stream, &bits));
-        if (bits & (1 << BN_ERR_FE_ZERO)) return fail(c, BN_ERR_FE_ZERO, "miller loop cannot produce zero");
-    }
-    return BN_OK;
-}
-
-int bn_pairing_prepared_many(bn_ctx* c, const bn_g1* p, const bn_g2_prepared* h, const uint32_t* qidx, size_t n,
-                             bn_gt* out) {
-    CTX_GUARD_HOST(c);
-    if (n == 0) return BN_OK;
-    RET_IF(prepared_args(c, p, h, out));
-    const int rc = prepared_host(c, p, h, qidx, n, out, true);
-    (void)hipStreamSynchronize(c->stream);  // an early error may leave copies queued
-    return rc;
-}
-
-int bn_miller_loop_prepared_many(bn_ctx* c, const bn_g1* p, const bn_g2_prepared* h, const uint32_t* qidx, size_t n,
-                                 bn_gt* out) {
-    CTX_GUARD_HOST(c);
-    if (n == 0) return BN_OK;
-    RET_IF(prepared_args(c, p, h, out));
-    const int rc = prepared_host(c, p, h, qidx, n, out, false);
-    (void)hipStreamSynchronize(c->stream);
-    return rc;
-}
-
-int bn_pairing_prepared_many_dev(bn_ctx* c, const bn_g1* d_p, const bn_g2_prepared* h, const uint32_t* d_qidx,
-                                 size_t n, bn_gt* d_out, void* stream) {
-    CTX_GUARD(c);
-    if (n == 0) return BN_OK;
-    RET_IF(prepared_args(c, d_p, h, d_out));
-    return prepared_dev_impl(c, d_p, h, d_qidx, n, d_out, true, pick(c, stream));
-}
-
-// ---- products with prepared terms (bn_pairing_batch_prepared_many)
-// One launch set, products [j0, j1): nf fresh terms (the call's fresh terms f0 .. f0 + nf - 1,
-// which is where their points start in the compacted q) and np prepared ones; its words
-// start at off_at in prod_off_d (j1 - j0 + 1 set-relative offsets) and at map_at in
-// prod_map_d: the term map (nf + np words), the prepared slots' terms and table indices
-// (np each), the fresh slots' terms (nf).  Every product runs on the packed path (no alone
-// path), so the sets are products_plan's packed runs.
-struct PreparedSet {
-    size_t j0, j1, nf, np, f0, off_at, map_at;
-};
-static std::vector<PreparedSet> prepared_products_plan(const bn_ctx* c, const uint32_t* qidx, const size_t* off,
-                                                       size_t m) {
-    std::vector<PreparedSet> sets;
-    size_t f0 = 0, off_at = 0, map_at = 0;
-    for (size_t j = 0; j < m;) {
-        size_t e = j + 1;
-        while (e < m && e - j < kChunk && off[e + 1] - off[j] <= c->products_chunk) ++e;
-        size_t nf = 0;
-        for (size_t i = off[j]; i < off[e]; ++i) nf += qidx[i] == BN_QIDX_FRESH ? 1 : 0;
-        const size_t nt = off[e] - off[j];
-        sets.push_back({j, e, nf, nt - nf, f0, off_at, map_at});
-        f0 += nf;
-        off_at += e - j + 1;
-        map_at += 3 * nt;
-        j = e;
-    }
-    return sets;
-}
-// Refusals, before any point buffer is read (qidx and offsets are the host's control arrays)
-static int prepared_products_check(bn_ctx* c, const void* p, const void* q, const bn_g2_prepared* h,
-                                   const uint32_t* qidx, const size_t* off, size_t m, const void* out) {
-    if (!off) return fail(c, BN_ERR_INVALID_ARGUMENT, "null offsets");
-    if (off[0] != 0) return fail(c, BN_ERR_INVALID_ARGUMENT, "offsets[0] must be 0");
-    for (size_t j = 0; j < m; ++j)
-        if (off[j + 1] < off[j]) return fail(c, BN_ERR_INVALID_ARGUMENT, "offsets must not decrease");
-    if (!qidx || !out || !h) return fail(c, BN_ERR_INVALID_ARGUMENT, "null buffer");
-    if (!prepared_live(c, h)) return fail(c, BN_ERR_INVALID_ARGUMENT, "not a live prepared handle of this context");
-    if (off[m] && !p) return fail(c, BN_ERR_INVALID_ARGUMENT, "null buffer");
-    for (size_t j = 0; j < m; ++j)
-        if (off[j + 1] - off[j] > (size_t)kProductLaneMax)
-            return fail(c, BN_ERR_INVALID_ARGUMENT, "a product of more than 64 terms; use bn_pairing_batch");
-    size_t nf = 0;
-    for (size_t i = 0; i < off[m]; ++i) {
-        if (qidx[i] == BN_QIDX_FRESH) ++nf;
-        else if (qidx[i] >= h->nq) return fail(c, BN_ERR_INVALID_ARGUMENT, "prepared-point index out of range");
-    }
-    if (nf && !q) return fail(c, BN_ERR_INVALID_ARGUMENT, "null buffer");
-    return BN_OK;
-}
-static int grow_words(bn_ctx* c, uint32_t** h, uint32_t** d, size_t* cap, size_t words) {
-    if (words <= *cap) return BN_OK;
-    RET_IF(ws_drain(c));  // queued kernels may still read the old buffer
-    if (*h) HIPCHK(c, hipHostFree(*h));
-    if (*d) HIPCHK(c, hipFree(*d));
-    *h = nullptr; *d = nullptr; *cap = 0;
-    const size_t n = std::max<size_t>(words, 4096);
-    HIPCHK(c, hipHostMalloc(h, n * 4, hipHostMallocDefault));
-    HIPCHK(c, hipMalloc(d, n * 4));
-    *cap = n;
-    return BN_OK;
-}
-// The offsets and per-term words of every set -> prod_off_d / prod_map_d, two copies on s in
-// front of the call's kernels, under products_offsets_upload's discipline (one event for
-// both pinned sources).  compact_p: the host form stages a set's G1 points fresh first, then
-// prepared, so prepared slot k's term is nf + k; otherwise terms are the caller's, set-relative.
-static int prepared_products_upload(bn_ctx* c, const uint32_t* qidx, const size_t* off,
-                                    const std::vector<PreparedSet>& sets, bool compact_p, hipStream_t s) {
-    if (c->prod_off_pending) {
-        HIPCHK(c, hipEventSynchronize(c->prod_off_event));
-        c->prod_off_pending = false;
-    }
-    const PreparedSet& last = sets.back();
-    const size_t off_words = last.off_at + (last.j1 - last.j0 + 1);
-    const size_t map_words = last.map_at + 3 * (last.nf + last.np);
-    RET_IF(grow_words(c, &c->prod_off_h, &c->prod_off_d, &c->prod_off_cap, off_words));
-    RET_IF(grow_words(c, &c->prod_map_h, &c->prod_map_d, &c->prod_map_cap, map_words));
-    for (const PreparedSet& st : sets) {
-        const size_t lo = off[st.j0], nt = st.nf + st.np;
-        for (size_t j = st.j0; j <= st.j1; ++j) c->prod_off_h[st.off_at + (j - st.j0)] = (uint32_t)(off[j] - lo);
-        uint32_t* map = c->prod_map_h + st.map_at;
-        uint32_t* pterm = map + nt;
-        uint32_t* pidx = pterm + st.np;
-        uint32_t* fterm = pidx + st.np;
-        size_t kf = 0, kp = 0;
-        for (size_t t = 0; t < nt; ++t) {
-            const uint32_t qi = qidx[lo + t];
-            if (qi == BN_QIDX_FRESH) {
-                fterm[kf] = (uint32_t)t;
-                map[t] = (uint32_t)kf++;
-            } else {
-                pterm[kp] = (uint32_t)(compact_p ? st.nf + kp : t);
-                pidx[kp] = qi;
-                map[t] = kMapRegionB | (uint32_t)kp++;
-            }
-        }
-    }
-    HIPCHK(c, hipMemcpyAsync(c->prod_off_d, c->prod_off_h, off_words * 4, hipMemcpyHostToDevice, s));
-    if (map_words)
-        HIPCHK(c, hipMemcpyAsync(c->prod_map_d, c->prod_map_h, map_words * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipEventRecord(c->prod_off_event, s));
-    c->prod_off_pending = true;
-    return BN_OK;
-}
-static int prepared_products_reserve(bn_ctx* c, const std::vector<PreparedSet>& sets) {
-    size_t need = 1;
-    for (const PreparedSet& st : sets) need = std::max(need, std::max(st.nf + st.np, st.j1 - st.j0));
-    return reserve(c, need);
-}
-// one launch set: the nf fresh pairs at d_pf / d_qf through the producers into region A of
-// the workspace, the np prepared terms (G1 points d_pp[pterm[k]]) through k_prepared_expand
-// into region B behind it, the products' loop over both, the final exponentiation
-static int prepared_products_set_dev(bn_ctx* c, const PreparedSet& st, const bn_g1* d_pf, const bn_g2* d_qf,
-                                     const bn_g1* d_pp, const bn_g2_prepared* h, bn_gt* d_out, hipStream_t s) {
-    const size_t nf = st.nf, np = st.np, mc = st.j1 - st.j0;
-    if (nf + np > c->cap || mc > c->cap) return fail(c, BN_ERR_INTERNAL, "launch set exceeds the workspace");
-    const uint32_t* map = c->prod_map_d + st.map_at;
-    if (nf) RET_IF(prepare(c, d_pf, d_qf, nf, 0, s, 1, true));
-    if (np) {
-        launch_prepared_expand(d_pp, map + nf + np, map + nf + 2 * np, h->table, h->zero, (uint32_t)h->nq, np,
-                               c->coeffs + nf * (size_t)kCoeffFq * 9, c->flags + kPathLanes * nf, s);
-        HIPCHK(c, hipGetLastError());
-    }
-    const size_t lanes = kPathLanes * mc;
-    const unsigned block = products_block(c, lanes);
-    k_miller_products_mapped<<<(unsigned)((lanes + block - 1) / block), block, 0, s>>>(
-        c->coeffs, c->flags, nf, np, map, c->prod_off_d + st.off_at, mc, c->slots);
-    HIPCHK(c, hipGetLastError());
-    return run_fe(c, c->slots, mc, nullptr, d_out, nullptr, s);
-}
-
-int bn_pairing_batch_prepared_many_dev(bn_ctx* c, const bn_g1* d_p, const bn_g2* d_q, const bn_g2_prepared* h,
-                                       const uint32_t* qidx, const size_t* offsets, size_t m, bn_gt* d_out,
-                                       void* stream) {
-    CTX_GUARD(c);
-    if (m == 0) return BN_OK;
-    RET_IF(prepared_products_check(c, d_p, d_q, h, qidx, offsets, m, d_out));
-    const hipStream_t s = pick(c, stream);
-    const std::vector<PreparedSet> sets = prepared_products_plan(c, qidx, offsets, m);
-    RET_IF(prepared_products_reserve(c, sets));
-    size_t nfmax = 0;
-    for (const PreparedSet& st : sets) nfmax = std::max(nfmax, st.nf);
-    if (nfmax > c->prod_fresh_cap) {
-        RET_IF(ws_drain(c));
-        if (c->prod_fresh) HIPCHK(c, hipFree(c->prod_fresh));
-        c->prod_fresh = nullptr;
-        c->prod_fresh_cap = 0;
-        const size_t cap = std::max<size_t>(nfmax, 4096);
-        HIPCHK(c, hipMalloc(&c->prod_fresh, cap * sizeof(bn_g1)));
-        c->prod_fresh_cap = cap;
-    }
-    RET_IF(ws_acquire(c, s));
-    WsUse use{c, s};
-    RET_IF(prepared_products_upload(c, qidx, offsets, sets, false, s));
-    for (const PreparedSet& st : sets) {
-        const size_t lo = offsets[st.j0];
-        if (st.nf) {
-            launch_g1_gather(d_p + lo, c->prod_map_d + st.map_at + st.nf + 3 * st.np, st.nf, c->prod_fresh, s);
-            HIPCHK(c, hipGetLastError());
-        }
-        RET_IF(prepared_products_set_dev(c, st, c->prod_fresh, d_q + st.f0, d_p + lo, h, d_out + st.j0, s));
-    }
-    return BN_OK;
-}
-// The host form: every set staged in turn (its G1 points compacted, fresh first; its fresh
-// G2 points; its products' Gt), the device outcome read after each, BN_ERR_FE_ZERO reported
-// at the end with every row written.
-static int prepared_products_host(bn_ctx* c, const bn_g1* p, const bn_g2* q, const bn_g2_prepared* h,
-                                  const uint32_t* qidx, const size_t* off, size_t m, bn_gt* out) {
-    const std::vector<PreparedSet> sets = prepared_products_plan(c, qidx, off, m);
-    RET_IF(prepared_products_reserve(c, sets));
-    RET_IF(prepared_products_upload(c, qidx, off, sets, true, c->stream));
-    bool zero = false;
-    std::vector<bn_g1> hp;
-    for (const PreparedSet& st : sets) {
-        const size_t lo = off[st.j0], nt = st.nf + st.np, mc = st.j1 - st.j0;
-        RET_IF(clear_err(c, c->stream));
-        const size_t o_q = round256(nt * sizeof(bn_g1));
-        const size_t o_out = o_q + round256(st.nf * sizeof(bn_g2));
-        RET_IF(stage(c, o_out + mc * sizeof(bn_gt)));
-        uint8_t* base = (uint8_t*)c->stage;
-        bn_g1* dp = (bn_g1*)base;
-        bn_g2* dq = (bn_g2*)(base + o_q);
-        bn_gt* d = (bn_gt*)(base + o_out);
-        hp.resize(nt);  // (the previous set's copy has completed: check_err synchronizes)
-        size_t kf = 0, kp = st.nf;
-        for (size_t t = 0; t < nt; ++t) hp[qidx[lo + t] == BN_QIDX_FRESH ? kf++ : kp++] = p[lo + t];
-        if (nt) HIPCHK(c, hipMemcpyAsync(dp, hp.data(), nt * sizeof(bn_g1), hipMemcpyHostToDevice, c->stream));
-        if (st.nf)
-            HIPCHK(c, hipMemcpyAsync(dq, q + st.f0, st.nf * sizeof(bn_g2), hipMemcpyHostToDevice, c->stream));
-        RET_IF(prepared_products_set_dev(c, st, dp, dq, dp, h, d, c->stream));
-        HIPCHK(c, hipMemcpyAsync(out + st.j0, d, mc * sizeof(bn_gt), hipMemcpyDeviceToHost, c->stream));
-        int bits = 0;
-        RET_IF(check_err(c, c->stream, &bits));  // synchronizes: the stage and hp are reused
-        if (bits & (1 << BN_ERR_FE_ZERO)) zero = true;
-    }
-    if (zero) return fail(c, BN_ERR_FE_ZERO, "miller loop cannot produce zero");
-    return BN_OK;
-}
-int bn_pairing_batch_prepared_many(bn_ctx* c, const bn_g1* p, const bn_g2* q, const bn_g2_prepared* h,
-                                   const uint32_t* qidx, const size_t* offsets, size_t m, bn_gt* out) {
-    CTX_GUARD_HOST(c);
-    if (m == 0) return BN_OK;
-    RET_IF(prepared_products_check(c, p, q, h, qidx, offsets, m, out));
-    const int rc = prepared_products_host(c, p, q, h, qidx, offsets, m, out);
-    (void)hipStreamSynchronize(c->stream);  // an early error may leave copies queued
-    return rc;
+    return outcome(c, bits, kBitToAffine);
 }
 
 int bn_g1_mul_many_dev(bn_ctx* c, const bn_g1* d_p, const bn_fr* d_k, size_t n, bn_g1* d_out, void* stream) {
@@ -2160,296 +1420,12 @@ int bn_g2_mul_many(bn_ctx* c, const bn_g2* p, const bn_fr* k, size_t n, bn_g2* o
     return host_mul(c, p, k, n, out, g2_mul_launch);
 }
 
-}  // extern "C"
-
-// ---------------------------------------------------------------- multi-scalar multiplication
-// (kernels_msm.hip, kernels_msm_g2.hip).  The bucket path and the
-// small path return the same image: the group law is exact and the result is
-// normalized.  The host sequence is one template over the point type; MsmGroup<P>
-// names the group's kernels, settings and buffers.
-constexpr size_t kMsmMaxTerms = size_t(1) << 26;  // the entry index keeps bit 31 for the sign; keys and positions are 32-bit
-template <class P>
-struct MsmGroup;
-template <>
-struct MsmGroup<bn_g1> {
-    static constexpr size_t kLanes = 1;  // lanes per element of the group-law kernels
-    static constexpr auto k_count = k_msm_count;
-    static constexpr auto k_scatter = k_msm_scatter;
-    static constexpr auto k_accumulate = k_msm_accumulate;
-    static constexpr auto k_reduce = k_msm_reduce;
-    static constexpr auto k_horner = k_msm_horner;
-    static constexpr auto k_finish = k_msm_finish;
-    static constexpr auto k_op = k_g1_op;
-    static MsmGroupWs<bn_g1>& ws(bn_ctx* c) { return c->msm_g1; }
-    static void mul(const bn_g1* d_p, const bn_fr* d_k, size_t n, bn_g1* d_out, hipStream_t s) {
-        g1_mul_launch(d_p, d_k, n, d_out, s);
-    }
-    // The window width used when bn_set_msm_window is 0: the fastest width of the measured
-    // sweep (profiles/msm_sweep.jsonl, tools/msm_bench.py) at the nearest
-    // measured size, the steps at the geometric means between sizes whose best width
-    // differs.  Below 2^13 terms every width from 8 to 12 is within the run-to-run spread.
-    static int auto_window(size_t n) {
-        if (n < 6144) return 10;
-        if (n < 92682) return 12;    // 2^16.5
-        if (n < 370728) return 14;   // 2^18.5
-        if (n < 741455) return 15;   // 2^19.5
-        return 16;
-    }
-};
-template <>
-struct MsmGroup<bn_g2> {
-    static constexpr size_t kLanes = kPathLanes;
-    static constexpr auto k_count = k_msm_count_g2;
-    static constexpr auto k_scatter = k_msm_scatter_g2;
-    static constexpr auto k_accumulate = k_msm_accumulate_g2;
-    static constexpr auto k_reduce = k_msm_reduce_g2;
-    static constexpr auto k_horner = k_msm_horner_g2;
-    static constexpr auto k_finish = k_msm_finish_g2;
-    static constexpr auto k_op = k_g2_op;
-    static MsmGroupWs<bn_g2>& ws(bn_ctx* c) { return c->msm_g2; }
-    static void mul(const bn_g2* d_p, const bn_fr* d_k, size_t n, bn_g2* d_out, hipStream_t s) {
-        g2_mul_launch(d_p, d_k, n, d_out, s);
-    }
-    // G2's own table, read off its own sweep in the same way (profiles/msm_g2_sweep.jsonl,
-    // tools/msm_bench.py --group g2): 11 is the fastest width in the
-    // thousands of terms, 12 at 2^15 and 14 already at 2^16.  Below 2^15 terms the widths
-    // from 8 to 13 differ by less than the run-to-run spread (0.5 ms on a 2.3 ms floor).
-    static int auto_window(size_t n) {
-        if (n < 1449) return 10;     // 2^10.5
-        if (n < 23171) return 11;    // 2^14.5
-        if (n < 46341) return 12;    // 2^15.5
-        if (n < 370728) return 14;   // 2^18.5
-        if (n < 741455) return 15;   // 2^19.5
-        return 16;
-    }
-};
-struct MsmPlan {
-    bool small;
-    int c;
-    uint32_t nwin, nkeys, nseg;
-    size_t nent;  // n * W(c): the most entries
-};
-template <class P>
-static MsmPlan msm_plan(bn_ctx* c, size_t n) {
-    const MsmGroupWs<P>& g = MsmGroup<P>::ws(c);
-    MsmPlan m{};
-    m.small = n < g.min;
-    m.c = g.window ? g.window : MsmGroup<P>::auto_window(n);
-    m.nwin = (uint32_t)msm_windows(m.c);
-    m.nkeys = msm_num_keys(m.c);
-    m.nseg = (msm_buckets(m.c) + kMsmSegment - 1) / kMsmSegment;
-    m.nent = n * m.nwin;
-    return m;
-}
-template <class T>
-static int msm_grow(bn_ctx* c, T** buf, size_t* cap, size_t need) {
-    if (need <= *cap) return BN_OK;
-    if (*buf) {
-        RET_IF(ws_drain(c));
-        HIPCHK(c, hipFree(*buf));
-    }
-    *buf = nullptr;
-    *cap = 0;
-    HIPCHK(c, hipMalloc((void**)buf, need * sizeof(T)));
-    *cap = need;
-    return BN_OK;
-}
-template <class P>
-static int msm_reserve(bn_ctx* c, size_t n, const MsmPlan& m) {
-    MsmGroupWs<P>& g = MsmGroup<P>::ws(c);
-    if (m.small) return msm_grow(c, &g.tmp, &g.tmp_cap, n);
-    RET_IF(msm_grow(c, &c->msm_keys, &c->msm_keys_cap, 3 * (size_t)m.nkeys + 1));
-    RET_IF(msm_grow(c, &c->msm_sorted, &c->msm_sorted_cap, m.nent));
-    RET_IF(msm_grow(c, &g.buckets, &g.buckets_cap, (size_t)m.nkeys));
-    return msm_grow(c, &g.parts, &g.parts_cap, (size_t)m.nseg * m.nwin);
-}
-// buf[0] = sum of buf[0 .. m) by a halving addition tree in place (odd tail carried),
-// then *d_out = its returned image (finish) or the Jacobian sum as it stands
-template <class P>
-static int msm_tree_out(bn_ctx* c, P* buf, size_t m, size_t width, int finish, P* d_out, hipStream_t s) {
-    using G = MsmGroup<P>;
-    while (m > 1) {
-        const size_t h = (m + 1) / 2;
-        G::k_op<<<grid_for((m - h) * width), kBlock, 0, s>>>(kGroupAdd, buf, buf + h * width, (m - h) * width, buf, nullptr);
-        m = h;
-    }
-    if (width != 1) return BN_OK;
-    if (finish)
-        G::k_finish<<<1, 64, 0, s>>>(m ? buf : nullptr, d_out);
-    else if (m)
-        HIPCHK(c, hipMemcpyAsync(d_out, buf, sizeof(P), hipMemcpyDeviceToDevice, s));
-    else
-        G::k_finish<<<1, 64, 0, s>>>(nullptr, d_out);  // zero is its own Jacobian image
-    return BN_OK;
-}
-// the device sequence on stream s; the caller holds the lock and the workspace order.
-// The group-law kernels take G::kLanes lanes per element (kBlock is even: whole pairs).
-template <class P>
-static int msm_dev_impl(bn_ctx* c, const P* d_p, const bn_fr* d_k, size_t n, P* d_out, hipStream_t s, int finish) {
-    using G = MsmGroup<P>;
-    if (n == 0) {
-        G::k_finish<<<1, 64, 0, s>>>(nullptr, d_out);
-        HIPCHK(c, hipGetLastError());
-        return BN_OK;
-    }
-    const MsmPlan m = msm_plan<P>(c, n);
-    if (!m.small && m.nent > (size_t)0x7fffffff)
-        return fail(c, BN_ERR_INVALID_ARGUMENT, "n * windows exceeds the 32-bit entry positions at this window width");
-    RET_IF(msm_reserve<P>(c, n, m));
-    MsmGroupWs<P>& g = G::ws(c);
-    if (m.small) {
-        G::mul(d_p, d_k, n, g.tmp, s);
-        RET_IF(msm_tree_out(c, g.tmp, n, 1, finish, d_out, s));
-        HIPCHK(c, hipGetLastError());
-        return BN_OK;
-    }
-    uint32_t* counts = c->msm_keys;
-    uint32_t* cursors = counts + m.nkeys;
-    uint32_t* offsets = cursors + m.nkeys;
-    const uint32_t nent = (uint32_t)m.nent;
-    const size_t nparts = (size_t)m.nseg * m.nwin;
-    HIPCHK(c, hipMemsetAsync(counts, 0, (size_t)m.nkeys * 4, s));
-    G::k_count<<<grid_for(n), kBlock, 0, s>>>(d_p, d_k, n, m.c, m.nkeys, counts);
-    k_msm_scan<<<1, kMsmScanBlock, 0, s>>>(counts, m.nkeys, offsets, cursors);
-    G::k_scatter<<<grid_for(n), kBlock, 0, s>>>(d_p, d_k, n, m.c, m.nkeys, cursors, offsets, c->msm_sorted, nent);
-    G::k_accumulate<<<grid_for(G::kLanes * m.nkeys), kBlock, 0, s>>>(d_p, n, c->msm_sorted, offsets, m.nkeys, nent, g.buckets);
-    G::k_reduce<<<grid_for(G::kLanes * nparts), kBlock, 0, s>>>(g.buckets, m.c, m.nkeys, m.nseg, g.parts);
-    RET_IF(msm_tree_out<P>(c, g.parts, m.nseg, m.nwin, 0, nullptr, s));
-    G::k_horner<<<1, 64, 0, s>>>(g.parts, m.c, finish, d_out);
-    HIPCHK(c, hipGetLastError());
-    return BN_OK;
-}
-static int msm_check_args(bn_ctx* c, const void* p, const void* k, size_t n, const void* out) {
-    if (n > kMsmMaxTerms) return fail(c, BN_ERR_INVALID_ARGUMENT, "more than 2^26 terms");
-    if (!out || (n && (!p || !k))) return fail(c, BN_ERR_INVALID_ARGUMENT, "null buffer");
-    return BN_OK;
-}
-template <class P>
-static int msm_host(bn_ctx* c, const P* p, const bn_fr* k, size_t n, P* out, int finish) {
-    CTX_GUARD_HOST(c);
-    RET_IF(msm_check_args(c, p, k, n, out));
-    RET_IF(stage(c, (n + 1) * sizeof(P) + n * sizeof(bn_fr)));
-    P* dout = (P*)c->stage;
-    P* dp = dout + 1;
-    bn_fr* dk = (bn_fr*)(dp + n);
-    if (n) {
-        HIPCHK(c, hipMemcpyAsync(dp, p, n * sizeof(P), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(dk, k, n * sizeof(bn_fr), hipMemcpyHostToDevice, c->stream));
-    }
-    RET_IF(msm_dev_impl(c, dp, dk, n, dout, c->stream, finish));
-    HIPCHK(c, hipMemcpyAsync(out, dout, sizeof(P), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return BN_OK;
-}
-// *out = the returned image of the sum of the m host points a[0 .. m) (the partials of
-// a multi-device context, in device order)
-template <class P>
-static int msm_sum_host(bn_ctx* c, const P* a, size_t m, P* out) {
-    CTX_GUARD_HOST(c);
-    if (!out || (m && !a)) return fail(c, BN_ERR_INVALID_ARGUMENT, "null buffer");
-    MsmGroupWs<P>& g = MsmGroup<P>::ws(c);
-    RET_IF(msm_grow(c, &g.tmp, &g.tmp_cap, m + 1));
-    P* dout = g.tmp + m;
-    if (m) HIPCHK(c, hipMemcpyAsync(g.tmp, a, m * sizeof(P), hipMemcpyHostToDevice, c->stream));
-    RET_IF(msm_tree_out(c, g.tmp, m, 1, 1, dout, c->stream));
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(out, dout, sizeof(P), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return BN_OK;
-}
-template <class P>
-static int msm_dev(bn_ctx* c, const P* d_p, const bn_fr* d_k, size_t n, P* d_out, void* stream) {
-    CTX_GUARD(c);
-    RET_IF(msm_check_args(c, d_p, d_k, n, d_out));
-    hipStream_t s = pick(c, stream);
-    RET_IF(ws_acquire(c, s));
-    WsUse use{c, s};
-    return msm_dev_impl(c, d_p, d_k, n, d_out, s, 1);
-}
-// bn_msm_reserve / bn_g2_msm_reserve on a single-device context
-template <class P>
-static int msm_reserve_terms(bn_ctx* c, size_t n) {
-    CTX_GUARD(c);
-    if (n > kMsmMaxTerms) return fail(c, BN_ERR_INVALID_ARGUMENT, "more than 2^26 terms");
-    if (n == 0) return BN_OK;
-    const MsmPlan m = msm_plan<P>(c, n);
-    if (!m.small && m.nent > (size_t)0x7fffffff)
-        return fail(c, BN_ERR_INVALID_ARGUMENT, "n * windows exceeds the 32-bit entry positions at this window width");
-    return msm_reserve<P>(c, n, m);
-}
-extern "C" {
-
-int bn_internal_g1_msm_partial(bn_ctx* c, const bn_g1* p, const bn_fr* k, size_t n, bn_g1* out) {
-    return msm_host(c, p, k, n, out, 0);
-}
-int bn_internal_g1_sum(bn_ctx* c, const bn_g1* a, size_t m, bn_g1* out) { return msm_sum_host(c, a, m, out); }
-int bn_internal_g2_msm_partial(bn_ctx* c, const bn_g2* p, const bn_fr* k, size_t n, bn_g2* out) {
-    return msm_host(c, p, k, n, out, 0);
-}
-int bn_internal_g2_sum(bn_ctx* c, const bn_g2* a, size_t m, bn_g2* out) { return msm_sum_host(c, a, m, out); }
-int bn_g1_msm(bn_ctx* c, const bn_g1* p, const bn_fr* k, size_t n, bn_g1* out) {
-    if (c && !c->subs.empty()) return bn_multi_g1_msm(c, p, k, n, out);
-    return msm_host(c, p, k, n, out, 1);
-}
-int bn_g1_msm_dev(bn_ctx* c, const bn_g1* d_p, const bn_fr* d_k, size_t n, bn_g1* d_out, void* stream) {
-    return msm_dev(c, d_p, d_k, n, d_out, stream);
-}
-int bn_g2_msm(bn_ctx* c, const bn_g2* p, const bn_fr* k, size_t n, bn_g2* out) {
-    if (c && !c->subs.empty()) {
-        // the cap is on the whole sum, not on a shard
-        if (n > kMsmMaxTerms) return fail(c, BN_ERR_INVALID_ARGUMENT, "more than 2^26 terms");
-        return bn_multi_g2_msm(c, p, k, n, out);
-    }
-    return msm_host(c, p, k, n, out, 1);
-}
-int bn_g2_msm_dev(bn_ctx* c, const bn_g2* d_p, const bn_fr* d_k, size_t n, bn_g2* d_out, void* stream) {
-    return msm_dev(c, d_p, d_k, n, d_out, stream);
-}
-int bn_set_msm_window(bn_ctx* c, int bits) {
-    if (c && bits != 0 && !msm_window_ok(bits))
-        return fail(c, BN_ERR_INVALID_ARGUMENT, "window width outside 2 .. 16 (0: automatic)");
-    if (c && !c->subs.empty()) {
-        for (bn_ctx* d : c->subs) RET_IF(bn_set_msm_window(d, bits));
-        return BN_OK;
-    }
-    CTX_GUARD(c);
-    c->msm_g1.window = bits;
-    c->msm_g2.window = bits;
-    return BN_OK;
-}
-int bn_set_msm_min(bn_ctx* c, size_t n) {
-    if (c && !c->subs.empty()) {
-        for (bn_ctx* d : c->subs) RET_IF(bn_set_msm_min(d, n));
-        return BN_OK;
-    }
-    CTX_GUARD(c);
-    c->msm_g1.min = n;
-    c->msm_g2.min = n;
-    return BN_OK;
-}
-int bn_msm_reserve(bn_ctx* c, size_t n) {
-    if (c && !c->subs.empty()) {
-        for (bn_ctx* d : c->subs) RET_IF(bn_msm_reserve(d, n / c->subs.size() + 1));
-        return BN_OK;
-    }
-    return msm_reserve_terms<bn_g1>(c, n);
-}
-int bn_g2_msm_reserve(bn_ctx* c, size_t n) {
-    if (c && !c->subs.empty()) {
-        if (n > kMsmMaxTerms) return fail(c, BN_ERR_INVALID_ARGUMENT, "more than 2^26 terms");
-        for (bn_ctx* d : c->subs) RET_IF(bn_g2_msm_reserve(d, n / c->subs.size() + 1));
-        return BN_OK;
-    }
-    return msm_reserve_terms<bn_g2>(c, n);
-}
-
 int bn_fq12_op_many(bn_ctx* c, int op, const bn_gt* a, const bn_gt* b, size_t n, bn_gt* out) {
     CTX_GUARD_HOST(c);
     if (n == 0) return BN_OK;
     if (op < 0 || op > BN_FQ12_FROB3) return fail(c, BN_ERR_INVALID_ARGUMENT, "bad op");
     if (!a || !out || (op == BN_FQ12_MUL && !b)) return fail(c, BN_ERR_INVALID_ARGUMENT, "null buffer");
-    for (size_t off = 0; off < n; off += kChunk) {
-        const size_t m = (n - off) < kChunk ? (n - off) : kChunk;
+    for (auto [off, m] : chunks(n)) {
         RET_IF(reserve(c, m));
         RET_IF(stage(c, m * 3 * sizeof(bn_gt) + 4096));
         bn_gt* da = (bn_gt*)c->stage;
@@ -2609,8 +1585,7 @@ int bn_gt_pow_many_dev(bn_ctx* c, const bn_gt* d_a, const bn_fr* d_k, size_t n, 
     hipStream_t s = pick(c, stream);
     RET_IF(ws_acquire(c, s));
     WsUse use{c, s};
-    for (size_t off = 0; off < n; off += kChunk) {
-        const size_t m = (n - off) < kChunk ? (n - off) : kChunk;
+    for (auto [off, m] : chunks(n)) {
         k_gt_pow<<<grid_pair(kPathLanes * m), kPairBlock, 0, s>>>(d_a + off, d_k + off, m, d_out + off, c->slots);
         HIPCHK(c, hipGetLastError());
     }

@@ -1,0 +1,261 @@
+// capi_msm.hip -- host side of the C ABI's multi-scalar multiplication (bn_g1_msm,
+// bn_g2_msm; kernels_msm.hip, kernels_msm_g2.hip).  The bucket path
+// and the small path return the same image: the group law is exact and the result is
+// normalized.  The host sequence is one template over the point type; MsmGroup<P>
+// names the group's kernels, settings and buffers.
+#include "capi_internal.h"
+
+using namespace bn;
+
+constexpr size_t kMsmMaxTerms = size_t(1) << 26;  // the entry index keeps bit 31 for the sign; keys and positions are 32-bit
+template <class P>
+struct MsmGroup;
+template <>
+struct MsmGroup<bn_g1> {
+    static constexpr size_t kLanes = 1;  // lanes per element of the group-law kernels
+    static constexpr auto k_count = k_msm_count;
+    static constexpr auto k_scatter = k_msm_scatter;
+    static constexpr auto k_accumulate = k_msm_accumulate;
+    static constexpr auto k_reduce = k_msm_reduce;
+    static constexpr auto k_horner = k_msm_horner;
+    static constexpr auto k_finish = k_msm_finish;
+    static constexpr auto k_op = k_g1_op;
+    static MsmGroupWs<bn_g1>& ws(bn_ctx* c) { return c->msm_g1; }
+    static void mul(const bn_g1* d_p, const bn_fr* d_k, size_t n, bn_g1* d_out, hipStream_t s) {
+        g1_mul_launch(d_p, d_k, n, d_out, s);
+    }
+    // The window width used when bn_set_msm_window is 0: the fastest width of the measured
+    // sweep (profiles/msm_sweep.jsonl, tools/msm_bench.py) at the nearest
+    // measured size, the steps at the geometric means between sizes whose best width
+    // differs.  Below 2^13 terms every width from 8 to 12 is within the run-to-run spread.
+    static int auto_window(size_t n) {
+        if (n < 6144) return 10;
+        if (n < 92682) return 12;    // 2^16.5
+        if (n < 370728) return 14;   // 2^18.5
+        if (n < 741455) return 15;   // 2^19.5
+        return 16;
+    }
+};
+template <>
+struct MsmGroup<bn_g2> {
+    static constexpr size_t kLanes = kPathLanes;
+    static constexpr auto k_count = k_msm_count_g2;
+    static constexpr auto k_scatter = k_msm_scatter_g2;
+    static constexpr auto k_accumulate = k_msm_accumulate_g2;
+    static constexpr auto k_reduce = k_msm_reduce_g2;
+    static constexpr auto k_horner = k_msm_horner_g2;
+    static constexpr auto k_finish = k_msm_finish_g2;
+    static constexpr auto k_op = k_g2_op;
+    static MsmGroupWs<bn_g2>& ws(bn_ctx* c) { return c->msm_g2; }
+    static void mul(const bn_g2* d_p, const bn_fr* d_k, size_t n, bn_g2* d_out, hipStream_t s) {
+        g2_mul_launch(d_p, d_k, n, d_out, s);
+    }
+    // G2's own table, read off its own sweep in the same way (profiles/msm_g2_sweep.jsonl,
+    // tools/msm_bench.py --group g2): 11 is the fastest width in the
+    // thousands of terms, 12 at 2^15 and 14 already at 2^16.  Below 2^15 terms the widths
+    // from 8 to 13 differ by less than the run-to-run spread (0.5 ms on a 2.3 ms floor).
+    static int auto_window(size_t n) {
+        if (n < 1449) return 10;     // 2^10.5
+        if (n < 23171) return 11;    // 2^14.5
+        if (n < 46341) return 12;    // 2^15.5
+        if (n < 370728) return 14;   // 2^18.5
+        if (n < 741455) return 15;   // 2^19.5
+        return 16;
+    }
+};
+struct MsmPlan {
+    bool small;
+    int c;
+    uint32_t nwin, nkeys, nseg;
+    size_t nent;  // n * W(c): the most entries
+};
+template <class P>
+static MsmPlan msm_plan(bn_ctx* c, size_t n) {
+    const MsmGroupWs<P>& g = MsmGroup<P>::ws(c);
+    MsmPlan m{};
+    m.small = n < g.min;
+    m.c = g.window ? g.window : MsmGroup<P>::auto_window(n);
+    m.nwin = (uint32_t)msm_windows(m.c);
+    m.nkeys = msm_num_keys(m.c);
+    m.nseg = (msm_buckets(m.c) + kMsmSegment - 1) / kMsmSegment;
+    m.nent = n * m.nwin;
+    return m;
+}
+template <class P>
+static int msm_reserve(bn_ctx* c, size_t n, const MsmPlan& m) {
+    MsmGroupWs<P>& g = MsmGroup<P>::ws(c);
+    if (m.small) return grow_dev(c, &g.tmp, &g.tmp_cap, n);
+    RET_IF(grow_dev(c, &c->msm_keys, &c->msm_keys_cap, 3 * (size_t)m.nkeys + 1));
+    RET_IF(grow_dev(c, &c->msm_sorted, &c->msm_sorted_cap, m.nent));
+    RET_IF(grow_dev(c, &g.buckets, &g.buckets_cap, (size_t)m.nkeys));
+    return grow_dev(c, &g.parts, &g.parts_cap, (size_t)m.nseg * m.nwin);
+}
+// buf[0] = sum of buf[0 .. m) by a halving addition tree in place (odd tail carried),
+// then *d_out = its returned image (finish) or the Jacobian sum as it stands
+template <class P>
+static int msm_tree_out(bn_ctx* c, P* buf, size_t m, size_t width, int finish, P* d_out, hipStream_t s) {
+    using G = MsmGroup<P>;
+    while (m > 1) {
+        const size_t h = (m + 1) / 2;
+        G::k_op<<<grid_for((m - h) * width), kBlock, 0, s>>>(kGroupAdd, buf, buf + h * width, (m - h) * width, buf, nullptr);
+        m = h;
+    }
+    if (width != 1) return BN_OK;
+    if (finish)
+        G::k_finish<<<1, 64, 0, s>>>(m ? buf : nullptr, d_out);
+    else if (m)
+        HIPCHK(c, hipMemcpyAsync(d_out, buf, sizeof(P), hipMemcpyDeviceToDevice, s));
+    else
+        G::k_finish<<<1, 64, 0, s>>>(nullptr, d_out);  // zero is its own Jacobian image
+    return BN_OK;
+}
+// the device sequence on stream s; the caller holds the lock and the workspace order.
+// The group-law kernels take G::kLanes lanes per element (kBlock is even: whole pairs).
+template <class P>
+static int msm_dev_impl(bn_ctx* c, const P* d_p, const bn_fr* d_k, size_t n, P* d_out, hipStream_t s, int finish) {
+    using G = MsmGroup<P>;
+    if (n == 0) {
+        G::k_finish<<<1, 64, 0, s>>>(nullptr, d_out);
+        HIPCHK(c, hipGetLastError());
+        return BN_OK;
+    }
+    const MsmPlan m = msm_plan<P>(c, n);
+    if (!m.small && m.nent > (size_t)0x7fffffff)
+        return fail(c, BN_ERR_INVALID_ARGUMENT, "n * windows exceeds the 32-bit entry positions at this window width");
+    RET_IF(msm_reserve<P>(c, n, m));
+    MsmGroupWs<P>& g = G::ws(c);
+    if (m.small) {
+        G::mul(d_p, d_k, n, g.tmp, s);
+        RET_IF(msm_tree_out(c, g.tmp, n, 1, finish, d_out, s));
+        HIPCHK(c, hipGetLastError());
+        return BN_OK;
+    }
+    uint32_t* counts = c->msm_keys;
+    uint32_t* cursors = counts + m.nkeys;
+    uint32_t* offsets = cursors + m.nkeys;
+    const uint32_t nent = (uint32_t)m.nent;
+    const size_t nparts = (size_t)m.nseg * m.nwin;
+    HIPCHK(c, hipMemsetAsync(counts, 0, (size_t)m.nkeys * 4, s));
+    G::k_count<<<grid_for(n), kBlock, 0, s>>>(d_p, d_k, n, m.c, m.nkeys, counts);
+    k_msm_scan<<<1, kMsmScanBlock, 0, s>>>(counts, m.nkeys, offsets, cursors);
+    G::k_scatter<<<grid_for(n), kBlock, 0, s>>>(d_p, d_k, n, m.c, m.nkeys, cursors, offsets, c->msm_sorted, nent);
+    G::k_accumulate<<<grid_for(G::kLanes * m.nkeys), kBlock, 0, s>>>(d_p, n, c->msm_sorted, offsets, m.nkeys, nent, g.buckets);
+    G::k_reduce<<<grid_for(G::kLanes * nparts), kBlock, 0, s>>>(g.buckets, m.c, m.nkeys, m.nseg, g.parts);
+    RET_IF(msm_tree_out<P>(c, g.parts, m.nseg, m.nwin, 0, nullptr, s));
+    G::k_horner<<<1, 64, 0, s>>>(g.parts, m.c, finish, d_out);
+    HIPCHK(c, hipGetLastError());
+    return BN_OK;
+}
+static int msm_check_args(bn_ctx* c, const void* p, const void* k, size_t n, const void* out) {
+    if (n > kMsmMaxTerms) return fail(c, BN_ERR_INVALID_ARGUMENT, "more than 2^26 terms");
+    if (!out || (n && (!p || !k))) return fail(c, BN_ERR_INVALID_ARGUMENT, "null buffer");
+    return BN_OK;
+}
+template <class P>
+static int msm_host(bn_ctx* c, const P* p, const bn_fr* k, size_t n, P* out, int finish) {
+    CTX_GUARD_HOST(c);
+    RET_IF(msm_check_args(c, p, k, n, out));
+    void* at[3];  // the sum, the points, the scalars
+    RET_IF(stage_regions(c, {sizeof(P), n * sizeof(P), n * sizeof(bn_fr)}, at));
+    if (n) {
+        HIPCHK(c, hipMemcpyAsync(at[1], p, n * sizeof(P), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(at[2], k, n * sizeof(bn_fr), hipMemcpyHostToDevice, c->stream));
+    }
+    RET_IF(msm_dev_impl(c, (const P*)at[1], (const bn_fr*)at[2], n, (P*)at[0], c->stream, finish));
+    HIPCHK(c, hipMemcpyAsync(out, at[0], sizeof(P), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return BN_OK;
+}
+// *out = the returned image of the sum of the m host points a[0 .. m) (the partials of
+// a multi-device context, in device order)
+template <class P>
+static int msm_sum_host(bn_ctx* c, const P* a, size_t m, P* out) {
+    CTX_GUARD_HOST(c);
+    if (!out || (m && !a)) return fail(c, BN_ERR_INVALID_ARGUMENT, "null buffer");
+    MsmGroupWs<P>& g = MsmGroup<P>::ws(c);
+    RET_IF(grow_dev(c, &g.tmp, &g.tmp_cap, m + 1));
+    P* dout = g.tmp + m;
+    if (m) HIPCHK(c, hipMemcpyAsync(g.tmp, a, m * sizeof(P), hipMemcpyHostToDevice, c->stream));
+    RET_IF(msm_tree_out(c, g.tmp, m, 1, 1, dout, c->stream));
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(out, dout, sizeof(P), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return BN_OK;
+}
+template <class P>
+static int msm_dev(bn_ctx* c, const P* d_p, const bn_fr* d_k, size_t n, P* d_out, void* stream) {
+    CTX_GUARD(c);
+    RET_IF(msm_check_args(c, d_p, d_k, n, d_out));
+    hipStream_t s = pick(c, stream);
+    RET_IF(ws_acquire(c, s));
+    WsUse use{c, s};
+    return msm_dev_impl(c, d_p, d_k, n, d_out, s, 1);
+}
+// bn_msm_reserve / bn_g2_msm_reserve on a single-device context
+template <class P>
+static int msm_reserve_terms(bn_ctx* c, size_t n) {
+    CTX_GUARD(c);
+    if (n > kMsmMaxTerms) return fail(c, BN_ERR_INVALID_ARGUMENT, "more than 2^26 terms");
+    if (n == 0) return BN_OK;
+    const MsmPlan m = msm_plan<P>(c, n);
+    if (!m.small && m.nent > (size_t)0x7fffffff)
+        return fail(c, BN_ERR_INVALID_ARGUMENT, "n * windows exceeds the 32-bit entry positions at this window width");
+    return msm_reserve<P>(c, n, m);
+}
+extern "C" {
+
+int bn_internal_g1_msm_partial(bn_ctx* c, const bn_g1* p, const bn_fr* k, size_t n, bn_g1* out) {
+    return msm_host(c, p, k, n, out, 0);
+}
+int bn_internal_g1_sum(bn_ctx* c, const bn_g1* a, size_t m, bn_g1* out) { return msm_sum_host(c, a, m, out); }
+int bn_internal_g2_msm_partial(bn_ctx* c, const bn_g2* p, const bn_fr* k, size_t n, bn_g2* out) {
+    return msm_host(c, p, k, n, out, 0);
+}
+int bn_internal_g2_sum(bn_ctx* c, const bn_g2* a, size_t m, bn_g2* out) { return msm_sum_host(c, a, m, out); }
+int bn_g1_msm(bn_ctx* c, const bn_g1* p, const bn_fr* k, size_t n, bn_g1* out) {
+    if (is_multi(c)) return bn_multi_g1_msm(c, p, k, n, out);
+    return msm_host(c, p, k, n, out, 1);
+}
+int bn_g1_msm_dev(bn_ctx* c, const bn_g1* d_p, const bn_fr* d_k, size_t n, bn_g1* d_out, void* stream) {
+    return msm_dev(c, d_p, d_k, n, d_out, stream);
+}
+int bn_g2_msm(bn_ctx* c, const bn_g2* p, const bn_fr* k, size_t n, bn_g2* out) {
+    if (is_multi(c)) {
+        // the cap is on the whole sum, not on a shard
+        if (n > kMsmMaxTerms) return fail(c, BN_ERR_INVALID_ARGUMENT, "more than 2^26 terms");
+        return bn_multi_g2_msm(c, p, k, n, out);
+    }
+    return msm_host(c, p, k, n, out, 1);
+}
+int bn_g2_msm_dev(bn_ctx* c, const bn_g2* d_p, const bn_fr* d_k, size_t n, bn_g2* d_out, void* stream) {
+    return msm_dev(c, d_p, d_k, n, d_out, stream);
+}
+int bn_set_msm_window(bn_ctx* c, int bits) {
+    if (c && bits != 0 && !msm_window_ok(bits))
+        return fail(c, BN_ERR_INVALID_ARGUMENT, "window width outside 2 .. 16 (0: automatic)");
+    if (is_multi(c)) return for_each_sub(c, [&](bn_ctx* d) { return bn_set_msm_window(d, bits); });
+    CTX_GUARD(c);
+    c->msm_g1.window = bits;
+    c->msm_g2.window = bits;
+    return BN_OK;
+}
+int bn_set_msm_min(bn_ctx* c, size_t n) {
+    if (is_multi(c)) return for_each_sub(c, [&](bn_ctx* d) { return bn_set_msm_min(d, n); });
+    CTX_GUARD(c);
+    c->msm_g1.min = n;
+    c->msm_g2.min = n;
+    return BN_OK;
+}
+int bn_msm_reserve(bn_ctx* c, size_t n) {
+    if (is_multi(c)) return for_each_sub(c, [&](bn_ctx* d) { return bn_msm_reserve(d, n / c->subs.size() + 1); });
+    return msm_reserve_terms<bn_g1>(c, n);
+}
+int bn_g2_msm_reserve(bn_ctx* c, size_t n) {
+    if (is_multi(c)) {
+        if (n > kMsmMaxTerms) return fail(c, BN_ERR_INVALID_ARGUMENT, "more than 2^26 terms");
+        return for_each_sub(c, [&](bn_ctx* d) { return bn_g2_msm_reserve(d, n / c->subs.size() + 1); });
+    }
+    return msm_reserve_terms<bn_g2>(c, n);
+}
+
+}  // extern "C"

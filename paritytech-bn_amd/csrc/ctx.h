@@ -1,5 +1,5 @@
-// ctx.h -- the bn_ctx behind the C ABI (host side, shared by capi.hip and
-// capi_multi.hip).  Not a public header.
+// ctx.h -- the bn_ctx behind the C ABI (host side, shared by capi.hip, capi_products.hip,
+// capi_msm.hip and capi_multi.hip).  Not a public header.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -15,7 +15,7 @@
 // the small path's n products.
 template <class P>
 struct MsmGroupWs {
-    int window = 0;  // bits; 0: chosen from n (capi.hip msm_auto_window)
+    int window = 0;  // bits; 0: chosen from n (capi_msm.hip MsmGroup<P>::auto_window)
     size_t min = 0;  // batches below this many terms take the small path
     P* buckets = nullptr;
     P* parts = nullptr;
@@ -118,7 +118,7 @@ struct bn_ctx {
     size_t msm_keys_cap = 0, msm_sorted_cap = 0;
     MsmGroupWs<bn_g1> msm_g1;
     MsmGroupWs<bn_g2> msm_g2;
-    // bn_pairing_batch_many (capi.hip): calls with fewer than products_min products of at
+    // bn_pairing_batch_many (capi_products.hip): calls with fewer than products_min products of at
     // most kProductLaneMax terms run each on the single-product path; the packed path
     // takes at most products_chunk terms per launch set.  Its chunk-relative 32-bit
     // offsets go up through prod_off_h (pinned) into prod_off_d, one upload per call in
@@ -141,7 +141,7 @@ struct bn_ctx {
     size_t prod_map_cap = 0;  // words
     bn_g1* prod_fresh = nullptr;
     size_t prod_fresh_cap = 0;  // points
-    // the bn_g2_prepared handles this context made and has not destroyed yet (capi.hip).
+    // the bn_g2_prepared handles this context made and has not destroyed yet (capi_products.hip).
     // Their tables are their own memory, not part of the workspace; the calls that read
     // them order themselves through ws_event like every workspace user, which is what
     // bn_g2_prepared_destroy waits for.
@@ -170,7 +170,7 @@ BN_HIDDEN int bn_multi_g2_msm(bn_ctx* c, const bn_g2* p, const bn_fr* k, size_t 
 BN_HIDDEN int bn_multi_pairing_batch_many(bn_ctx* c, const bn_g1* p, const bn_g2* q, const size_t* offsets, size_t m,
                                           bn_gt* out);
 BN_HIDDEN int bn_multi_destroy(bn_ctx* c);
-// capi.hip internals used by capi_multi.hip
+// capi.hip / capi_msm.hip internals used by capi_multi.hip
 BN_HIDDEN int bn_internal_miller_product(bn_ctx* c, const bn_g1* p, const bn_g2* q, size_t n, int mode, bn_gt* result);
 BN_HIDDEN void bn_internal_gt_one(bn_gt* out);
 // *out = the Jacobian (un-normalized) sum of p[i] * k[i], i < n

@@ -1,5 +1,5 @@
 // kernels.h -- shared device helpers and the kernel declarations of the engine
-// (definitions in kernels_*.hip; launched from capi.hip).
+// (definitions in kernels_*.hip; launched from capi.hip, capi_products.hip and capi_msm.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -8,7 +8,7 @@
 //   k_msm_scatter     recoding again, each entry (term index, sign) to its bucket's run
 //   k_msm_accumulate  one lane per bucket: gathers its run's points and adds them
 //   k_msm_reduce      one lane per segment of kMsmSegment buckets: sum_j (j + 1) * B_j
-//   (k_g1_op add)     addition tree over each window's segments (capi.hip)
+//   (k_g1_op add)     addition tree over each window's segments (capi_msm.hip)
 //   k_msm_horner      one lane: Horner over the window sums, then normalize
 // Every computed index is bounded against its array in the kernel; a lane whose
 // index is out of range does nothing.

@@ -458,9 +458,9 @@ __global__ void BN_PATH_ATTR __launch_bounds__(kPairBlock) k_miller_seg(const ui
 // The coefficient loads of neighbouring lane pairs are strided by the product size, so
 // they are not coalesced.
 // Products of more than kProductLaneMax terms do not come here (the balance positions
-// hold t < 64; capi.hip routes them to the single-product path).
+// hold t < 64; products_plan.h routes them to the single-product path).
 // Launched with kPairBlock threads per block (kernels.h: issue balance) once the lane
-// pairs fill the GPU that way, with 256 or 128 below that (capi.hip products_block).
+// pairs fill the GPU that way, with 256 or 128 below that (capi_internal.h products_block).
 __global__ void BN_PATH_ATTR __launch_bounds__(kPairBlock) k_miller_products(const uint32_t* __restrict__ coeffs,
                                                                             const uint8_t* __restrict__ flags, size_t n,
                                                                             const uint32_t* __restrict__ off, size_t m,
@@ -509,7 +509,7 @@ __global__ void BN_PATH_ATTR __launch_bounds__(kPairBlock) k_miller_products(con
 // its region.  Everything else is k_miller_products: the wave-uniform pair loop to the
 // wave's largest product, the line one past a product's own count and for a flagged term,
 // the loads of such a lane pair from a clamped in-range term (whose map word is read), the
-// launch shape and the block size (capi.hip products_block).
+// launch shape and the block size (capi_internal.h products_block).
 __global__ void BN_PATH_ATTR __launch_bounds__(kPairBlock)
 k_miller_products_mapped(const uint32_t* __restrict__ coeffs, const uint8_t* __restrict__ flags, size_t nf, size_t np,
                          const uint32_t* __restrict__ map, const uint32_t* __restrict__ off, size_t m,

@@ -79,12 +79,16 @@ def test_g1_mul(ctx, pairs):
     edge_p = np.stack([z, p[0], p[1], p[2], p[3]])
     edge_k = O.canon_to_mont_array([5, 0, 1, O.R - 1, (1 << 253) + 12345], O.FR).reshape(5, 4)
     assert np.array_equal(ctx.g1_mul_many(edge_p, edge_k), O.g1_mul(edge_p, edge_k))
+    for n in (1, 3):  # staged regions that are padded to their alignment
+        assert np.array_equal(ctx.g1_mul_many(p[:n], K[:n]), O.g1_mul(p[:n], K[:n]))
 
 
 def test_g2_mul(ctx, pairs):
     _, q = pairs
     ks, K = O.random_scalars(64, seed=78)
     assert np.array_equal(ctx.g2_mul_many(q[:64], K), O.g2_mul(q[:64], K, NT))
+    for n in (1, 3):  # staged regions that are padded to their alignment
+        assert np.array_equal(ctx.g2_mul_many(q[:n], K[:n]), O.g2_mul(q[:n], K[:n]))
 
 
 def test_reference_kats(ctx, kats):
@@ -117,6 +121,11 @@ def test_miller_and_final_exp(ctx, pairs):
     assert np.array_equal(f, want_f)
     fe, ok = ctx.final_exponentiation_many(f)
     assert ok.all() and np.array_equal(fe, O.pairing_many(p[:64], q[:64], NT))
+    for n in (1, 3):  # staged regions that are padded to their alignment
+        fn = ctx.miller_loop_many(p[:n], q[:n])
+        assert np.array_equal(fn, want_f[:n])
+        fen, okn = ctx.final_exponentiation_many(fn)
+        assert okn.all() and np.array_equal(fen, fe[:n])
     # f == 0 -> None (fq12.rs:63-72)
     fe0, ok0 = ctx.final_exponentiation_many(np.zeros((2, 48), np.uint64))
     assert not ok0.any() and not fe0.any()
@@ -134,7 +143,7 @@ def test_zero_points(ctx, pairs):
     assert np.array_equal(ctx.pairing_many(p2, q2), O.pairing_many(p2, q2))
 
 
-@pytest.mark.parametrize("n", [1, 63, 65, 129, 255])
+@pytest.mark.parametrize("n", [1, 3, 63, 65, 129, 255])
 def test_pairing_many_ragged(ctx, pairs, n):
     """Batch sizes that leave a partial wave / workgroup, with zero points in the tail lanes."""
     p, q = pairs
@@ -149,7 +158,7 @@ def test_pairing_many_ragged(ctx, pairs, n):
     assert np.array_equal(ctx.pairing_batch(p2, q2), O.pairing_batch(p2, q2))
 
 
-@pytest.mark.parametrize("n", [0, 1, 5, 64])
+@pytest.mark.parametrize("n", [0, 1, 3, 5, 64])
 def test_pairing_batch(ctx, pairs, n):
     p, q = pairs
     p2, q2 = p[:n].copy(), q[:n].copy()
