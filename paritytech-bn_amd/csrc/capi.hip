@@ -236,11 +236,8 @@ constexpr int kRegionParts = 3;            // per-chunk partial products
 constexpr int kRegionResult = 4;           // the final product (element 0, stride 1)
 constexpr size_t kWideGroups = kBlock / 16;  // k_fq12_reduce_wide: 16-lane groups per block
 constexpr size_t kReduceBlocksMax = 512;      // one round of 256-thread blocks, two per CU (kernels_reduce.hip)
-// BN_REDUCE_LAST: a level whose sets all fit one block with chains of up to 8 factors
+// a level whose sets all fit one block with chains of up to 8 factors
 // finishes there (config 5: 80 + 24 + 19 -> 85 + 30 us, profiles/r5af_ab_reduce_last.txt)
-#ifndef BN_REDUCE_LAST
-#define BN_REDUCE_LAST 1
-#endif
 constexpr int kReduceLastMax = 8;  // the longest chain a finishing level may take
 
 // sets y < `sets` of n elements each at y * n
@@ -282,14 +279,12 @@ int product_wide(bn_ctx* c, const uint32_t* in, size_t in_stride, SetSpan span, 
         };
         int per_group = 2;
         while (per_group < 64 && blocks_for(per_group) > kReduceBlocksMax) per_group *= 2;
-#if BN_REDUCE_LAST
         // a level whose every set fits one block with chains of <= kReduceLastMax factors
         // finishes there instead of leaving a few blocks per set for one more launch
         size_t nmax = 0;
         for (int y = 0; y < sets; ++y) nmax = std::max<size_t>(nmax, span.n[y]);
         if (nmax > kWideGroups * (size_t)per_group && nmax <= kWideGroups * (size_t)kReduceLastMax)
             while (kWideGroups * (size_t)per_group < nmax) per_group *= 2;
-#endif
         const size_t per_block = kWideGroups * (size_t)per_group;
         size_t bmax = 0;
         span.blk[0] = 0;
@@ -538,19 +533,6 @@ uint32_t* parts_region(bn_ctx* c, size_t nchunks) {
 // into *d_out: k_horner_tree (the squarings of the segments side by side and a
 // product tree); BN254MI_HORNER_TREE=0 selects k_horner_wide (one group, Horner's
 // rule), kept for A/B
-// Build parameters (A/B builds, tools/build_variant.sh): BN_TAIL_DS=0 builds the tail
-// without the digit-sliced layout (kernels_tail.hip), BN_SEG_FE1=0 keeps the segments'
-// first chunks and squarings inside k_horner_tree2
-#ifndef BN_TAIL_DS
-#define BN_TAIL_DS 1
-#endif
-#ifndef BN_SEG_FE1
-#define BN_SEG_FE1 1
-#endif
-// BN_TAIL_M=0: the final exponentiation after k_seg_fe1 on one block (no multiplier block)
-#ifndef BN_TAIL_M
-#define BN_TAIL_M 1
-#endif
 // (g: the segment values, element s at stride S; default the result region)
 static int recombine_one(bn_ctx* c, const SegPlan& plan, int do_fe, bn_gt* d_out, hipStream_t s,
                          uint32_t* g = nullptr) {
@@ -561,19 +543,18 @@ static int recombine_one(bn_ctx* c, const SegPlan& plan, int do_fe, bn_gt* d_out
         const char* e = getenv("BN254MI_TAIL_FUSED");
         return !(e && atoi(e) == 0);
     }();
-    if (tree == 2 && BN_FE_DUO && BN_TAIL_DS && BN_SEG_FE1 && BN_TAIL_M && fused && do_fe && plan.S >= 1 &&
-        plan.S <= kMaxSeg) {
+    if (tree == 2 && fused && do_fe && plan.S >= 1) {
         // pairing_batch: the whole tail in one launch (kernels_tail.hip k_seg_tail)
         c->tail_epoch = c->tail_epoch + 1 < (1u << 29) ? c->tail_epoch + 1 : 1u;  // (epoch * 8 fits the role word)
         k_seg_tail<<<plan.S > 3 ? plan.S : 3, kTailBlock, 0, s>>>(g, plan, d_out, c->d_err,
                                                                   c->tail_ws, c->tail_epoch);
-    } else if (tree == 2 && BN_FE_DUO && plan.S <= kMaxSeg) {
+    } else if (tree == 2) {
         // pairing_batch: the segments' first chunks and squarings one block each
         // (k_seg_fe1), the zero flags and the squarer <-> multiplier channel of
         // k_horner_tree2's two blocks at the start of the reduction's ping-pong region
         // A (free once the reduction has written the result region)
         const uint32_t* zf = nullptr;
-        if (BN_TAIL_DS && BN_SEG_FE1 && do_fe && plan.S >= 1 && (size_t)kSlotWords * c->cap >= (size_t)kTailChanWords) {
+        if (do_fe && plan.S >= 1 && (size_t)kSlotWords * c->cap >= (size_t)kTailChanWords) {
             uint32_t* z = slot_region(c, kRegionA);
             k_seg_fe1<<<plan.S, kTailBlock, 0, s>>>(g, plan, z);
             HIPCHK(c, hipGetLastError());
@@ -585,8 +566,7 @@ static int recombine_one(bn_ctx* c, const SegPlan& plan, int do_fe, bn_gt* d_out
         // word k_seg_fe1 clears (kernels_tail.hip tail_claim): a multiplier that has not
         // started when the squarer gets there is not waited for -- the squarer runs
         // the chunk alone (the same value) and the late block returns.
-        k_horner_tree2<<<zf && BN_TAIL_M ? 2 : 1, kTailBlock, 0, s>>>(g, plan, do_fe, d_out, c->d_err,
-                                                          zf);
+        k_horner_tree2<<<zf ? 2 : 1, kTailBlock, 0, s>>>(g, plan, do_fe, d_out, c->d_err, zf);
     }
     else if (tree != 0)
         k_horner_tree<<<1, kBlock, 0, s>>>(g, plan, do_fe, d_out, c->d_err,

@@ -409,10 +409,7 @@ __device__ __noinline__ uint32_t ds_mul(uint32_t a, uint32_t b, bool conj_b) {
     }
     __syncthreads();
     uint64_t pp = 0, qq = 0;
-#ifndef BN_DS_MUL_UNROLL
-#define BN_DS_MUL_UNROLL 2
-#endif
-#pragma unroll BN_DS_MUL_UNROLL
+#pragma unroll 2
     for (int i = 0; i < 6; ++i) {
         const bool wrap = i > x.e;
         const int jj = wrap ? x.e - i + 6 : x.e - i;

@@ -117,29 +117,14 @@ BN_INLINE bool fq2_eq(const Fq2<A>& a, const Fq2<B>& b) {
     const uint32_t e = fq_eq(a.c, b.c) ? 1u : 0u;
     return (e & swap_pair(e)) != 0;
 }
-template <int B>
-BN_INLINE void fq2_fence(Fq2<B>& a) {
-    fq_fence(a.c);
-}
-// the fences around the two-lane products (below): 3 = inputs and results (rounds 2-4),
-// 1 = results only, 0 = none (default).  They kept the compiler from interleaving the
+// The two-lane products (below) run without compiler fences around them.  Rounds 2-4
+// fenced their inputs and results to keep the compiler from interleaving the
 // digit products of several Fq2 products; since every product is one asm statement
 // (BN_DOT2_ASM) there is nothing to interleave, and the "+v" input fences only made
 // the compiler copy every input it still needed (the fenced value counts as
 // rewritten): k_pairing_full 6.3 % fewer instructions, scratch 716 -> 584 B/lane,
 // 7.60-7.62 -> 7.47-7.49 ms (frac 0.491 -> 0.500), G2 * Fr 6.01-6.08 -> 5.82-5.86 ms
 // (profiles/r5q_ab_fence.txt)
-#ifndef BN_FQ2_FENCE
-#define BN_FQ2_FENCE 0
-#endif
-template <int B>
-BN_INLINE void fq2_fence_in(Fq2<B>& a) {
-    if constexpr ((BN_FQ2_FENCE & 2) != 0) fq2_fence(a);
-}
-template <int B>
-BN_INLINE void fq2_fence_out(Fq2<B>& a) {
-    if constexpr ((BN_FQ2_FENCE & 1) != 0) fq2_fence(a);
-}
 
 // K*p - x without a carry pass (digits < (sub_spread(L)+2)*2^29, value <= (B+1)*p)
 template <int K>
@@ -224,7 +209,7 @@ BN_INLINE auto fq_dot2(const Fq<X>& x, const Fq<Y>& y, const Fq<Z>& z, const Fq<
     return r;
 }
 
-// BN_DOT2_ADDEND (on by default): fq_dot2 with addends at weight R.  Columns 9..17 of
+// fq_dot2 with addends at weight R.  Columns 9..17 of
 // the chain -- the ones that leave as digits 0..8 -- also take digit d of each addend
 // c_j, times a small constant K_j that rides as the multiply-add's inline constant:
 //   r = REDC(x*y + z*w) + sum K_j * c_j   (r * R == x*y + z*w + R * sum K_j * c_j mod p).
@@ -233,10 +218,6 @@ BN_INLINE auto fq_dot2(const Fq<X>& x, const Fq<Y>& y, const Fq<Z>& z, const Fq<
 // cost one multiply-add per digit and leave normalized: next to the 2^58-sized
 // digit products a term K_j * c_j[d] < 2^36 is invisible in the 64-bit accumulator.
 // The value bound of every addend, times its multiplier, adds to the product's.
-// BN_DOT2_ADDEND=0 builds the callers' digit-wise forms (tools/build_variant.sh).
-#ifndef BN_DOT2_ADDEND
-#define BN_DOT2_ADDEND 1
-#endif
 // NA of the three addends are used (the others: K == 0, any operand)
 template <int NA, int K0, int K1, int K2, int X, int Y, int Z, int W, int C0, int C1, int C2>
 BN_INLINE auto fq_dot2_addn(const Fq<X>& x, const Fq<Y>& y, const Fq<Z>& z, const Fq<W>& w, const Fq<C0>& c0,
@@ -587,13 +568,7 @@ BN_INLINE auto fq2_cyc_u(const Fq2<A>& a, const Fq2<B>& b, const Fq2<T>& tmp, co
 template <int A, int B>
 BN_INLINE auto fq2_mul(const Fq2<A>& a_in, const Fq2<B>& b_in) {
     if constexpr (kv(A) > 40 || kv(B) > 40) return fq2_mul(pre<40>(a_in), pre<40>(b_in)); else {
-    Fq2<A> a = a_in;
-    Fq2<B> b = b_in;
-    fq2_fence_in(a);
-    fq2_fence_in(b);
-    auto r = fq2_mul_split(a, b);
-    fq2_fence_out(r);
-    return r;
+    return fq2_mul_split(a_in, b_in);
     }
 }
 template <class R, class S>
@@ -606,18 +581,8 @@ BN_INLINE auto fq2_mul2(const Fq2<A>& a_in, const Fq2<B>& b_in, const Fq2<C>& c_
     if constexpr (kv(A) > 40 || kv(B) > 40 || kv(C) > 40 || kv(D) > 40) {
         return fq2_mul2(pre<40>(a_in), pre<40>(b_in), pre<40>(c_in), pre<40>(d_in));
     } else {
-        Fq2<A> a = a_in;
-        Fq2<B> b = b_in;
-        Fq2<C> c = c_in;
-        Fq2<D> d = d_in;
-        fq2_fence_in(a);
-        fq2_fence_in(b);
-        fq2_fence_in(c);
-        fq2_fence_in(d);
-        auto r = fq2_mul_split(a, b);
-        auto q = fq2_mul_split(c, d);
-        fq2_fence_out(r);
-        fq2_fence_out(q);
+        auto r = fq2_mul_split(a_in, b_in);
+        auto q = fq2_mul_split(c_in, d_in);
         return Fq2Pair<decltype(r), decltype(q)>{r, q};
     }
 }
@@ -626,18 +591,14 @@ BN_INLINE auto fq2_mul2(const Fq2<A>& a_in, const Fq2<B>& b_in, const Fq2<C>& c_
 // lane 0: (a0 + K*p - a1) * (a0 + a1), lane 1: a1 * (a0 + a0).  x keeps digits
 // below 3*2^29 (no carry pass: fq_mul takes a 3 x 2 digit-bound product).
 template <int A>
-BN_INLINE auto fq2_sqr(const Fq2<A>& a_in) {
-    if constexpr (kv(A) > 40) return fq2_sqr(fq2_fold(a_in)); else {
-    Fq2<A> a = a_in;
-    fq2_fence_in(a);
+BN_INLINE auto fq2_sqr(const Fq2<A>& a) {
+    if constexpr (kv(A) > 40) return fq2_sqr(fq2_fold(a)); else {
     const bool odd = lane_odd();
     const Fq<kv(A)> own = fq_norm(a.c);
     const Fq<kv(A)> par = fq_partner(own);
     const auto x = fq_pick(odd, own, fq_sub(own, par));
     const auto y = fq_add(par, fq_select(odd, par, own));
-    auto r = wrap2(fq_mul(x, y));
-    fq2_fence_out(r);
-    return r;
+    return wrap2(fq_mul(x, y));
     }
 }
 // ---------------------------------------------------------------- line-step chains

@@ -15,18 +15,13 @@ namespace bn {
 constexpr int kBlock = 256;
 // The pairing-path kernels (kernels_pairing/fe/util.hip) run two lanes per
 // element (fq2_split.h: 2^16 pairings -> 2048 waves, two per SIMD); the host
-// launches kPathLanes threads per element.  Built with -DBN_PATH_SPLIT=0 they
-// run the one-lane layout (the round-1 form, kept for A/B measurements).
-constexpr int kPathLanes = BN_PATH_SPLIT ? 2 : 1;
+// launches kPathLanes threads per element.
+constexpr int kPathLanes = 2;
 // words of one Fq12 slot per lane of the translation unit's own layout
 constexpr int kSlotLaneWords = BN_SPLIT ? 54 : 108;
-#if BN_SPLIT
 // two waves per SIMD: the kernel must fit 256 registers (three or four waves: the
 // spills cost 20-40 %, profiles/r2u_ab_waves_per_simd.txt)
 #define BN_PATH_ATTR __attribute__((amdgpu_waves_per_eu(2, 2)))
-#else
-#define BN_PATH_ATTR
-#endif
 constexpr int kCoeffFq = BN_NUM_COEFFS * 6;  // Fq elements of line coefficients per pairing
 constexpr size_t kChunk = size_t(1) << 18;   // pairings per launch set (~5 GB workspace)
 constexpr int kSlotWords = 108;              // one Fq12: 12 Fq x 9 digits
@@ -64,6 +59,8 @@ __device__ __forceinline__ Fq2<B> ld_fq2(const uint32_t* base, size_t n, size_t 
     return {ld_fq<B>(base, n, i, j / 2)};
 }
 #else
+// one lane per element: no unit of the library keeps Fq2 / Fq12 slots or Gt images this way; the
+// layout comparisons tools/split_ubench.hip (-DBN_SPLIT=0) and tools/mul12_ubench.hip build these forms
 template <int B>
 __device__ __forceinline__ void st_fq2(uint32_t* base, size_t n, size_t i, int j, const Fq2<B>& x) {
     st_fq(base, n, i, j, x.c0);
@@ -108,7 +105,7 @@ __device__ __forceinline__ void st_fq_buf(__amdgpu_buffer_rsrc_t rs, int vo, siz
 #pragma unroll
     for (int l = 0; l < 9; ++l) __builtin_amdgcn_raw_buffer_store_b32(x.v[l], rs, vo, (int)(((size_t)j * 9 + l) * n * 4), 0);
 }
-#if BN_SPLIT
+#if BN_SPLIT  // (the step machine and Gt::pow are built on the two-lane layout only)
 template <int B>
 __device__ __forceinline__ void st_fq12_buf(uint32_t* base, size_t n, size_t i, const Fq12<B>& f) {
     const auto rs = slot_rsrc(base);
@@ -124,27 +121,6 @@ __device__ __forceinline__ Fq12<B> ld_fq12_buf(const uint32_t* base, size_t n, s
     auto q = [&](int k) { return Fq2<B>{ld_fq_buf<B>(rs, vo, n, k)}; };
     return {{q(0), q(1), q(2)}, {q(3), q(4), q(5)}};
 }
-#else
-template <int B>
-__device__ __forceinline__ void st_fq12_buf(uint32_t* base, size_t n, size_t i, const Fq12<B>& f) {
-    const auto rs = slot_rsrc(base);
-    const int vo = (int)(i * 4);
-    const Fq2<B>* c[6] = {&f.c0.c0, &f.c0.c1, &f.c0.c2, &f.c1.c0, &f.c1.c1, &f.c1.c2};
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-        st_fq_buf(rs, vo, n, 2 * k, c[k]->c0);
-        st_fq_buf(rs, vo, n, 2 * k + 1, c[k]->c1);
-    }
-}
-template <int B>
-__device__ __forceinline__ Fq12<B> ld_fq12_buf(const uint32_t* base, size_t n, size_t i) {
-    const auto rs = slot_rsrc(base);
-    const int vo = (int)(i * 4);
-    auto q = [&](int k) { return Fq2<B>{ld_fq_buf<B>(rs, vo, n, 2 * k), ld_fq_buf<B>(rs, vo, n, 2 * k + 1)}; };
-    return {{q(0), q(1), q(2)}, {q(3), q(4), q(5)}};
-}
-
-#endif  // BN_SPLIT
 
 // Per-lane slot selection (Gt::pow's window table): the descriptor is built
 // from the uniform workspace base and the lane's slot goes into the VGPR
@@ -153,17 +129,7 @@ __device__ __forceinline__ Fq12<B> ld_fq12_buf(const uint32_t* base, size_t n, s
 // waterfall loop whose per-lane pointer lives in VGPRs across partial-exec
 // regions; round 1's k_gt_pow faulted with an illegal address in that form
 // (DESIGN.md §3).  vo_bytes = (slot * kSlotWords * n + i) * 4 must stay below
-// 2^31 (checked by the host launcher).
-#if !BN_SPLIT
-template <int B>
-__device__ __forceinline__ Fq12<B> ld_fq12_buf_sel(const uint32_t* ws, size_t n, uint32_t vo_bytes) {
-    const auto rs = slot_rsrc(ws);
-    const int vo = (int)vo_bytes;
-    auto q = [&](int k) { return Fq2<B>{ld_fq_buf<B>(rs, vo, n, 2 * k), ld_fq_buf<B>(rs, vo, n, 2 * k + 1)}; };
-    return {{q(0), q(1), q(2)}, {q(3), q(4), q(5)}};
-}
-#else
-// two lanes per element: `n` counts lanes, the lane's own coordinates
+// 2^31 (checked by the host launcher).  `n` counts lanes.
 template <int B>
 __device__ __forceinline__ Fq12<B> ld_fq12_buf_sel(const uint32_t* ws, size_t n, uint32_t vo_bytes) {
     const auto rs = slot_rsrc(ws);
@@ -171,92 +137,10 @@ __device__ __forceinline__ Fq12<B> ld_fq12_buf_sel(const uint32_t* ws, size_t n,
     auto q = [&](int k) { return Fq2<B>{ld_fq_buf<B>(rs, vo, n, k)}; };
     return {{q(0), q(1), q(2)}, {q(3), q(4), q(5)}};
 }
-#endif
-
-template <int B>
-__device__ __forceinline__ Fq6<B> ld_fq6(const uint32_t* base, size_t n, size_t i, int h) {
-    return {ld_fq2<B>(base, n, i, 6 * h), ld_fq2<B>(base, n, i, 6 * h + 2), ld_fq2<B>(base, n, i, 6 * h + 4)};
-}
+#endif  // BN_SPLIT
 
 // No memory operation may move across this point (compiler barrier only).
 __device__ __forceinline__ void mem_fence() { asm volatile("" ::: "memory"); }
-
-// Fq6 product (fq6.rs:197-207, the same Karatsuba as fq6_mul) with operand b
-// supplied per Fq2 coordinate by g(j), fetched right before each product that
-// needs it (mem_fence keeps the loads from being hoisted), so b never has to be
-// held in registers.
-template <int A, class G>
-__device__ __forceinline__ auto fq6_mul_g(const Fq6<A>& a, G&& g) {
-    if constexpr (kv(A) > 20) {
-        return fq6_mul_g(fq6_fold(a), g);
-    } else {
-        mem_fence();
-        auto a_a = fq2_mul(a.c0, g(0));
-        mem_fence();
-        auto b_b = fq2_mul(a.c1, g(1));
-        mem_fence();
-        auto c_c = fq2_mul(a.c2, g(2));
-        mem_fence();
-        auto t0 = fq2_sub(fq2_sub(fq2_mul(fq2_add(a.c1, a.c2), fq2_add(g(1), g(2))), b_b), c_c);
-        mem_fence();
-        auto t1 = fq2_sub(fq2_sub(fq2_mul(fq2_add(a.c0, a.c1), fq2_add(g(0), g(1))), a_a), b_b);
-        mem_fence();
-        auto t2 = fq2_sub(fq2_mul(fq2_add(a.c0, a.c2), fq2_add(g(0), g(2))), a_a);
-        return mk6(fq2_add(fq2_mul_xi(t0), a_a), fq2_add(t1, fq2_mul_xi(c_c)), fq2_sub(fq2_add(t2, b_b), c_c));
-    }
-}
-
-#if !BN_SPLIT
-// a * b (fq12.rs:319-327 Karatsuba) with b read per Fq2 from `y`, the calling
-// lane's strided copy of an Fq12 (word w at y[w * stride]: an LDS image with
-// stride kBlock, or a lane-strided HBM slot with stride n); conj_b multiplies
-// by conj(b) instead (fq12.rs:126-128).  b is never held in registers whole.
-__device__ __forceinline__ Fq12<kF> mul12_strided(const Fq12<kF>& a, const uint32_t* y, size_t stride, bool conj_b) {
-    auto ld = [&](int j) {  // Fq2 coordinate j of b (0..2: b.c0, 3..5: b.c1)
-        Fq2<kF> r;
-#pragma unroll
-        for (int l = 0; l < 9; ++l) {
-            r.c0.v[l] = y[((2 * j) * 9 + l) * stride];
-            r.c1.v[l] = y[((2 * j + 1) * 9 + l) * stride];
-        }
-        return r;
-    };
-    auto g0 = [&](int j) { return ld(j); };
-    auto g1 = [&](int j) {
-        Fq2<kF> r = ld(3 + j);
-        if (conj_b) r = fq2_neg(r);
-        return r;
-    };
-    auto gs = [&](int j) { return fq2_add(g0(j), g1(j)); };
-    const auto aa = fq6_fold(fq6_mul_g(a.c0, g0));
-    const auto s = fq6_add(a.c0, a.c1);
-    const auto bb = fq6_fold(fq6_mul_g(a.c1, g1));
-    const auto t = fq6_mul_g(s, gs);
-    return narrow12<kF>(mk12(fq6_add(fq6_mul_by_nonresidue(bb), aa), fq6_sub(fq6_sub(t, aa), bb)));
-}
-__device__ __forceinline__ Fq12<kF> mul12_lds(const Fq12<kF>& a, const uint32_t* yl, bool conj_b) {
-    return mul12_strided(a, yl, kBlock, conj_b);
-}
-
-#endif
-
-// Asynchronous copy of a lane-strided Fq12 (108 words, stride n) from global
-// memory into the block's LDS image (stride kBlock) with buffer_load ... lds:
-// no VGPRs and no vector ALU (SGPR offsets, M0 = the wave's LDS base).  The
-// caller waits with lds_copy_wait() before reading.
-__device__ __forceinline__ void lds_copy_fq12(const uint32_t* src_block, size_t n, uint32_t* yl_block) {
-    // src_block = slot base + blockIdx.x * kBlock; yl_block = LDS image base
-    const __amdgpu_buffer_rsrc_t rs =
-        __builtin_amdgcn_make_buffer_rsrc((void*)src_block, 0, 0x7fffffff, 0x00020000);
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x & ~63u);
-    const int lane_off = (int)(threadIdx.x & 63u) * 4 + (int)wave * 4;
-#pragma unroll
-    for (int w = 0; w < kSlotWords; ++w)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(
-            rs, (__attribute__((address_space(3))) void*)(yl_block + w * kBlock + wave), 4, lane_off,
-            (int)((size_t)w * n * 4), 0, 0);
-}
-__device__ __forceinline__ void lds_copy_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 // ---------------------------------------------------------------- reference images
 __device__ __forceinline__ void ld_words(const bn_fq* src, uint32_t w[8]) {
@@ -330,7 +214,7 @@ __device__ __forceinline__ void st_gt_zero(bn_gt& g) {
 #pragma unroll
     for (int k = 0; k < 6; ++k) st_words(&g.c[2 * k + o], z);
 }
-#else
+#else  // (one lane per element: tools/split_ubench.hip -DBN_SPLIT=0, as st_fq2 above)
 template <int B>
 __device__ __forceinline__ void st_gt(bn_gt& g, const Fq12<B>& f) {
     // coefficient order c0.c0.c0, c0.c0.c1, c0.c1.c0, ... (fq12.rs:52-55); no array
@@ -570,18 +454,15 @@ __global__ void __launch_bounds__(kPairBlock) k_prepare(const bn_g1* __restrict_
 // the same outputs on kPrepareWideLanes lanes per pair (kernels_pairing.hip): four
 // lane pairs run each line step's independent products side by side.  scale = 1: the
 // lines as the Miller loop multiplies by them (ell_vw Py, ell_vv Px; the consumers of
-// coeffs expect that form in a BN_LINES_PRESCALED build), 0: the reference's
+// coeffs expect that form), 0: the reference's
 // coefficients (the G2Precomp export)
 constexpr int kPrepareWideLanes = 8;
-// BN_LINES_PRESCALED: the producers store each line as the Miller loop multiplies by it
+// The producers store each line as the Miller loop multiplies by it
 // (ell_0, ell_vw * Py, ell_vv * Px; mod.rs:589), so k_miller_seg / k_miller apply it
 // without scaling, and the latency kernel's producer writes it to its ring that way
 // (lines_wide.h PwEll: the eight-lane steps take the two P products in slots their
 // layers left duplicated); `scale` = 0 keeps the reference's G2Precomp coefficients
-// (the bn_g2_precompute export).  0: the consumers scale.
-#ifndef BN_LINES_PRESCALED
-#define BN_LINES_PRESCALED 1
-#endif
+// (the bn_g2_precompute export).
 __global__ void __launch_bounds__(kPairBlock) k_prepare_wide(const bn_g1* __restrict__ p, const bn_g2* __restrict__ q,
                                                          size_t n, uint32_t* __restrict__ coeffs,
                                                          uint32_t* __restrict__ paff, uint8_t* __restrict__ flags,
@@ -652,7 +533,7 @@ __global__ void __launch_bounds__(kBlock) k_fq12_reduce_wide(const uint32_t* __r
                                                              SetSpan sets, uint32_t* __restrict__ out,
                                                              size_t out_stride, size_t out_base, size_t out_set, int per_group);
 // kernels_tail.hip: k_horner_tree's recombination + final exponentiation of ONE
-// product, the final exponentiation's squarer on a pair of 16-lane groups (w12_cyc32)
+// product, the final exponentiation's last chunk digit-sliced on the whole block (fq12_ds.h)
 constexpr int kTailBlock = 256;
 __global__ void __launch_bounds__(kTailBlock) k_horner_tree2(const uint32_t* __restrict__ g, SegPlan plan, int do_fe,
                                                              bn_gt* __restrict__ out, int* __restrict__ err,
@@ -687,16 +568,14 @@ __global__ void __launch_bounds__(kTailBlock) k_fe_ds(const uint32_t* __restrict
 // kernels_wide.hip: the whole pairing of kLatPairs pairs per block in one launch
 // (a producer wave for the lines, consumer groups for the wide Miller loop + FE)
 constexpr int kLatPairs = 8;
-#ifndef BN_FE_DUO
-#define BN_FE_DUO 1  // the latency kernels' final exponentiation on two groups (fq12_wide.h)
-#endif
-// one producer wave, two consumer waves (+ with BN_FE_DUO a wave of multiplier groups)
-constexpr int kLatThreads = 64 + kLatPairs * 16 + (BN_FE_DUO ? 64 : 0);
+// one producer wave, two consumer waves and a wave of multiplier groups (the latency
+// kernels' final exponentiation runs on two groups, fq12_wide.h)
+constexpr int kLatThreads = 64 + kLatPairs * 16 + 64;
 // k_fe_wide / k_horner_wide: the two-group final exponentiation (8 elements per
 // block) while the blocks fit one round on the 256 CUs (the channel makes it one
 // block per CU); above, one group per element (16 per block)
 constexpr size_t kWideDuoMax = 2048;
-inline bool wide_duo(size_t n) { return BN_FE_DUO && n <= kWideDuoMax; }
+inline bool wide_duo(size_t n) { return n <= kWideDuoMax; }
 inline unsigned wide_blocks(size_t n) { return (unsigned)(wide_duo(n) ? (n + 7) / 8 : (n + 15) / 16); }
 __global__ void __launch_bounds__(kLatThreads) k_pairing_latency(const bn_g1* __restrict__ p,
                                                                  const bn_g2* __restrict__ q, size_t n,

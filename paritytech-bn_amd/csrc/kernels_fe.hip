@@ -1,6 +1,6 @@
 // kernels_fe.hip -- final exponentiation (fq12.rs:62-124, 249-266) as a step
 // program over lane-strided Fq12 slots (see kernels.h), plus the Gt output.
-// Pairing-path layout (BN_PATH_SPLIT: two lanes per element, fq2_split.h);
+// Pairing-path layout (two lanes per element, fq2_split.h);
 // `n` counts elements, the grid has kPathLanes threads per element.
 // fq_fold reads -q*p from an LDS table (fq.h; every kernel here calls
 // fold_table_init first): 2-3 % faster on this path, measured
@@ -8,13 +8,13 @@
 #define BN_FOLD_LDS 1
 #endif
 #include "fq.h"
-#define BN_SPLIT BN_PATH_SPLIT
+#define BN_SPLIT 1
 #include "kernels.h"
 #include "fe_vm.h"
 
 namespace bn {
 
-constexpr size_t kL = BN_SPLIT ? 2 : 1;  // lanes per element in this translation unit
+constexpr size_t kL = 2;  // lanes per element in this translation unit
 
 // Launched with kPairBlock threads per block (kernels.h: two-wave issue balance;
 // the program position is step * 256 + squarings done in the step).

@@ -1,6 +1,6 @@
 // kernels_gtpow.hip -- batched Gt::pow(Fr) (lib.rs:592-594 -> generic Fq12 pow,
-// fields/mod.rs:35-46), on the pairing path's two-lane layout (BN_PATH_SPLIT,
-// fq2_split.h: each lane holds one coordinate of every Fq2, so 2^16 powers are
+// fields/mod.rs:35-46), on the pairing path's two-lane layout
+// (fq2_split.h: each lane holds one coordinate of every Fq2, so 2^16 powers are
 // 2,048 waves, two per SIMD).
 //
 // The reference squares-and-multiplies over all 256 bits of U256::from(Fr)
@@ -37,12 +37,12 @@
 #include <type_traits>
 
 #include "fq.h"
-#define BN_SPLIT BN_PATH_SPLIT
+#define BN_SPLIT 1
 #include "kernels.h"
 
 namespace bn {
 
-constexpr size_t kL = BN_SPLIT ? 2 : 1;  // lanes per element in this translation unit
+constexpr size_t kL = 2;  // lanes per element in this translation unit
 
 // True when every element of the wave is a nonzero member of the cyclotomic
 // subgroup (order p^4 - p^2 + 1, where every pairing output lies):

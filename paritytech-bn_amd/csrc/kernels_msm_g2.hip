@@ -1,6 +1,6 @@
 // kernels_msm_g2.hip -- the group-law kernels of the G2 multi-scalar multiplication
 // (bn_g2_msm; the phases are kernels_msm.hip's, the bodies msm_group.h's) on the
-// pairing path's two-lane layout (BN_PATH_SPLIT, fq2_split.h): lanes 2j and 2j + 1
+// pairing path's two-lane layout (fq2_split.h): lanes 2j and 2j + 1
 // hold coordinates c0 and c1 of the points of element j.
 //   k_msm_accumulate_g2  one lane pair per (window, bucket) key
 //   k_msm_reduce_g2      one lane pair per (segment, window)
@@ -19,7 +19,7 @@
 #define BN_FOLD_LDS 1
 #endif
 #include "fq.h"
-#define BN_SPLIT BN_PATH_SPLIT
+#define BN_SPLIT 1
 #include "kernels.h"
 #include "msm_group.h"
 

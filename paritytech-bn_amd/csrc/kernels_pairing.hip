@@ -1,5 +1,5 @@
 // kernels_pairing.hip -- to_affine + G2 line precomputation (mod.rs:199-216, 701-727) and the
-// Miller loop (mod.rs:579-607).  Pairing-path layout (BN_PATH_SPLIT: two lanes
+// Miller loop (mod.rs:579-607).  Pairing-path layout (two lanes
 // per pairing, fq2_split.h; `n` counts pairings, the grid has kPathLanes
 // threads per pairing).  G1 values (P, its affine form) are held by both lanes.
 // fq_fold reads -q*p from an LDS table (fq.h; every kernel here calls
@@ -42,12 +42,9 @@
 #endif
 // k_pairing_full and the line producers of the calls that end in a final exponentiation
 // run the Miller loop on scaled coordinates (pairing.h scaled_inputs) instead of affine
-// ones: no to_affine inversion, the same Gt.  0 builds them on pair_to_affine as before.
-#ifndef BN_SCALED_INPUTS
-#define BN_SCALED_INPUTS 1
-#endif
+// ones: no to_affine inversion, the same Gt.
 #include "fq.h"
-#define BN_SPLIT BN_PATH_SPLIT
+#define BN_SPLIT 1
 #include "kernels.h"
 #include "lines_wide.h"
 #include "fe_vm.h"
@@ -65,7 +62,7 @@ __device__ __forceinline__ void prepare_pair(const bn_g1* __restrict__ p, const 
     const auto a = pair_inputs<Scaled>(p, q, i, l, flags, err, mode);
     st_fq(paff, nl, l, 0, a.px);
     st_fq(paff, nl, l, 1, a.py);
-    const bool sc = BN_LINES_PRESCALED && scale;
+    const bool sc = scale != 0;
     g2_precompute(a.qa, pair_coeff(a), [&](int k, const Ell& e) {
         balance_step(bal, (uint32_t)k);
         st_fq2(coeffs, nl, l, k * 6 + 0, e.ell_0);
@@ -101,10 +98,9 @@ __global__ void BN_PATH_ATTR __launch_bounds__(kPairBlock) k_prepare_scaled(cons
     const Balance bal = balance_init();
     const size_t l = lane_id(), i = l / kL, nl = kL * n;
     if (i >= n) return;
-    prepare_pair<BN_SCALED_INPUTS != 0>(p, q, n, coeffs, paff, flags, nullptr, 0, 1, bal, l, i, nl);
+    prepare_pair<true>(p, q, n, coeffs, paff, flags, nullptr, 0, 1, bal, l, i, nl);
 }
 
-#if BN_SPLIT
 // the same on eight lanes per pair (lines_wide.h)
 template <bool Scaled>
 __device__ __forceinline__ void prepare_pair_wide(const bn_g1* __restrict__ p, const bn_g2* __restrict__ q, size_t n,
@@ -124,7 +120,6 @@ __device__ __forceinline__ void prepare_pair_wide(const bn_g1* __restrict__ p, c
     G2Proj r = {qa.x, qa.y, widen<kPt>(fq2_one())};
     const auto qy_neg = fq2_neg(qa.y);
     int c = 0;
-#if BN_LINES_PRESCALED
     // slot 0 stores ell_0; with `scale` slot 2 stores ell_vw * Py and slot 3 ell_vv * Px
     // (their own products, lines_wide.h PwEll), else slot 0 the unscaled pair
     const bool sc = scale != 0;
@@ -163,32 +158,6 @@ __device__ __forceinline__ void prepare_pair_wide(const bn_g1* __restrict__ p, c
     q2.y = narrow<kPt>(fq2_neg(q2.y));
     emit(c++, pw_mixed_addition_step_p(r, q1, fq2_scale(q1.x, a.py), k, py_r, px_r));
     emit(c++, pw_mixed_addition_step_p(r, q2, fq2_scale(q2.x, a.py), k, py_r, px_r));
-#else
-    static_assert(!Scaled, "scaled inputs: only with BN_LINES_PRESCALED");
-    (void)scale;
-    auto emit = [&](int cc, const Ell& e) {
-        if (st) {
-            st_fq2(coeffs, nl, lt, cc * 6 + 0, e.ell_0);
-            st_fq2(coeffs, nl, lt, cc * 6 + 2, e.ell_vw);
-            st_fq2(coeffs, nl, lt, cc * 6 + 4, e.ell_vv);
-        }
-    };
-#pragma unroll 1
-    for (int d = 0; d < BN_NAF_DIGITS; ++d) {
-        balance_step(bal, (uint32_t)d);
-        emit(c++, pw_doubling_step(r, k));
-        if ((kNafNonzero >> d) & 1u) {
-            const bool minus = (kNafMinus >> d) & 1u;
-            const G2Aff<kPt> base = {qa.x, fq2_select(minus, widen<kPt>(qy_neg), qa.y)};
-            emit(c++, pw_mixed_addition_step(r, base, k));
-        }
-    }
-    G2Aff<kPt> q1 = mul_by_q(qa);
-    G2Aff<kPt> q2 = mul_by_q(q1);
-    q2.y = narrow<kPt>(fq2_neg(q2.y));
-    emit(c++, pw_mixed_addition_step(r, q1, k));
-    emit(c++, pw_mixed_addition_step(r, q2, k));
-#endif
 }
 // Launched with kPairBlock threads per block (kernels.h: issue balance).
 __global__ void BN_PATH_ATTR __launch_bounds__(kPairBlock) k_prepare_wide(const bn_g1* __restrict__ p,
@@ -214,10 +183,8 @@ __global__ void BN_PATH_ATTR __launch_bounds__(kPairBlock) k_prepare_wide_scaled
     const Balance bal = balance_init();
     const size_t l = lane_id(), i = l / kPW, nl = kL * n;
     if (i >= n) return;
-    prepare_pair_wide<BN_SCALED_INPUTS != 0 && BN_LINES_PRESCALED>(p, q, n, coeffs, paff, flags, nullptr, 0, 1, bal, l, i,
-                                                                   nl);
+    prepare_pair_wide<true>(p, q, n, coeffs, paff, flags, nullptr, 0, 1, bal, l, i, nl);
 }
-#endif
 
 // The coefficients k_prepare wrote for pair i -> the reference images of its
 // G2Precomp (mod.rs:566-577): 87 x {ell_0, ell_vw, ell_vv}, each a canonical Fq2
@@ -282,13 +249,8 @@ __global__ void BN_PATH_ATTR __launch_bounds__(kPairBlock) k_pairing_full(const 
     const Balance bal = balance_init();
     const size_t l = lane_id(), i = l / kL, nl = kL * n;
     if (i >= n) return;
-#if BN_SCALED_INPUTS
     const PairScaled a = pair_scaled(p, q, i, l, nullptr);
     Fq12<kF> f = miller_fused(a.qa, a.px, a.py, a.coeff, [&](int d) { balance_step(bal, (uint32_t)d); });
-#else
-    const PairAffine a = pair_to_affine(p, q, i, l, nullptr, err, 0);
-    Fq12<kF> f = miller_fused(a.qa, a.px, a.py, [&](int d) { balance_step(bal, (uint32_t)d); });
-#endif
     if (a.skip) f = widen<kF>(fq12_one());
     // f == 0: the reference's final_exponentiation returns None and pairing()
     // panics (fq12.rs:63-72) -> zero Gt and the error bit, as k_fe_out
@@ -316,14 +278,8 @@ __global__ void BN_PATH_ATTR __launch_bounds__(kBlock) k_miller(const uint32_t* 
         return Ell{ld_fq2<kLine>(coeffs, nl, l, k * 6 + 0), ld_fq2<kLine>(coeffs, nl, l, k * 6 + 2),
                    ld_fq2<kLine>(coeffs, nl, l, k * 6 + 4)};
     };
-#if BN_LINES_PRESCALED
-    (void)paff;
+    (void)paff;  // (the lines are stored as the loop multiplies by them: no P needed)
     Fq12<kF> f = miller_loop_scaled(line);
-#else
-    const Fq<2> px = ld_fq<2>(paff, nl, l, 0);
-    const Fq<2> py = ld_fq<2>(paff, nl, l, 1);
-    Fq12<kF> f = miller_loop(px, py, line);
-#endif
     if (flags[l]) f = widen<kF>(fq12_one());
     st_fq12(f_out, nl, l, f);
 }
@@ -344,9 +300,6 @@ __global__ void BN_PATH_ATTR __launch_bounds__(kBlock) k_miller(const uint32_t* 
 // Launched with kPairBlock threads per block (kernels.h: issue balance).
 #ifndef BN_SEG_STAMPS
 #define BN_SEG_STAMPS 0
-#endif
-#ifndef BN_SEG_LINE_BALANCE
-#define BN_SEG_LINE_BALANCE 1
 #endif
 #if BN_SEG_STAMPS
 // diagnostic build (tools/build_variant.sh segstamps -DBN_SEG_STAMPS=1, tools/seg_stamps.py):
@@ -379,25 +332,17 @@ __global__ void BN_PATH_ATTR __launch_bounds__(kPairBlock) k_miller_seg(const ui
     SEG_STAMP(3, (uint64_t)K);
     if (g >= G) return;
     const Ell one_line = {widen<kLine>(fq2_one()), widen<kLine>(fq2_zero()), widen<kLine>(fq2_zero())};
-    // line k of pair t of this group, with the pair's affine P
-    struct PairLine {
-        Ell e;
-        Fq<2> px, py;
-    };
+    // line k of pair t of this group (as the loop multiplies by it: no P needed)
+    (void)paff;
     auto pair_line = [&](size_t t, int k) {
         const size_t j = g + t * G;
         const bool live = j < n && !flags[j * kL + c];
         const size_t lt = (j < n ? j : 0) * kL + c;  // the pair's lane in the per-pair arrays
-        PairLine r;
         mem_fence();  // load right before use: K pairs' lines are never held at once
-        r.e = Ell{ld_fq2<kLine>(coeffs, nl, lt, k * 6 + 0), ld_fq2<kLine>(coeffs, nl, lt, k * 6 + 2),
-                  ld_fq2<kLine>(coeffs, nl, lt, k * 6 + 4)};
-#if !BN_LINES_PRESCALED  // (prescaled: the line as the loop multiplies by it, no P needed)
-        r.px = ld_fq<2>(paff, nl, lt, 0);
-        r.py = ld_fq<2>(paff, nl, lt, 1);
-#endif
-        if (!live) r.e = one_line;
-        return r;
+        Ell e = {ld_fq2<kLine>(coeffs, nl, lt, k * 6 + 0), ld_fq2<kLine>(coeffs, nl, lt, k * 6 + 2),
+                 ld_fq2<kLine>(coeffs, nl, lt, k * 6 + 4)};
+        if (!live) e = one_line;
+        return e;
     };
     // Digits lo..hi-1, then (last segment) the two closing lines as pseudo-digits
     // 64 and 65 without a squaring; per digit one squaring (none at lo: f starts
@@ -424,19 +369,12 @@ __global__ void BN_PATH_ATTR __launch_bounds__(kPairBlock) k_miller_seg(const ui
         for (int ps = 0; ps < passes; ++ps, ++idx) {
 #pragma unroll 1
             for (size_t t = 0; t < K; ++t) {
-                if (BN_SEG_LINE_BALANCE) balance_step(bal, dpos + 1u + ((uint32_t)ps << 6) + (uint32_t)t);
-                const PairLine pl = pair_line(t, idx);
-#if BN_LINES_PRESCALED
+                balance_step(bal, dpos + 1u + ((uint32_t)ps << 6) + (uint32_t)t);
+                const Ell e = pair_line(t, idx);
                 if (i == lo && ps == 0 && t == 0)
-                    f = line_from_one_scaled(pl.e);  // one * line (mod.rs:589 on f = one)
+                    f = line_from_one_scaled(e);  // one * line (mod.rs:589 on f = one)
                 else
-                    f = apply_line_scaled(f, pl.e);
-#else
-                if (i == lo && ps == 0 && t == 0)
-                    f = line_from_one(pl.e, pl.px, pl.py);  // one * line (mod.rs:589 on f = one)
-                else
-                    f = apply_line(f, pl.e, pl.px, pl.py);
-#endif
+                    f = apply_line_scaled(f, e);
             }
         }
     }
@@ -465,7 +403,6 @@ __global__ void BN_PATH_ATTR __launch_bounds__(kPairBlock) k_miller_products(con
                                                                             const uint8_t* __restrict__ flags, size_t n,
                                                                             const uint32_t* __restrict__ off, size_t m,
                                                                             uint32_t* __restrict__ out) {
-    static_assert(BN_LINES_PRESCALED, "k_miller_products takes the lines as the loop multiplies by them");
     fold_table_init();
     const Balance bal = balance_init();
     const size_t l = lane_id(), j = l / kL, c = l % kL, nl = kL * n;
@@ -514,7 +451,6 @@ __global__ void BN_PATH_ATTR __launch_bounds__(kPairBlock)
 k_miller_products_mapped(const uint32_t* __restrict__ coeffs, const uint8_t* __restrict__ flags, size_t nf, size_t np,
                          const uint32_t* __restrict__ map, const uint32_t* __restrict__ off, size_t m,
                          uint32_t* __restrict__ out) {
-    static_assert(BN_LINES_PRESCALED, "k_miller_products_mapped takes the lines as the loop multiplies by them");
     fold_table_init();
     const Balance bal = balance_init();
     const size_t l = lane_id(), j = l / kL, c = l % kL, n = nf + np;

@@ -1,6 +1,6 @@
 // kernels_prepared.hip -- pairings against prepared G2 points (bn_g2_prepared; G2Precomp,
 // mod.rs:566-607): the table's fill and the throughput kernel that reads it.
-// Pairing-path layout (BN_PATH_SPLIT: two lanes per pairing, fq2_split.h; `n` counts
+// Pairing-path layout (two lanes per pairing, fq2_split.h; `n` counts
 // pairings, the grid has kPathLanes threads per pairing).  G1 values are held by both lanes.
 // Built as kernels_pairing.hip is: the same BN_FOLD_LDS / BN_FQ6_LAZY / BN_CYC_LIN, so the
 // Fq12 product, square and cyclotomic square of the final exponentiation here are the
@@ -20,7 +20,7 @@
 #endif
 #endif
 #include "fq.h"
-#define BN_SPLIT BN_PATH_SPLIT
+#define BN_SPLIT 1
 #include "kernels.h"
 #include "lines_wide.h"
 #include "fe_vm.h"

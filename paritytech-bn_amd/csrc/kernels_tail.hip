@@ -2,53 +2,30 @@
 // of ONE product (pairing_batch / miller_loop_batch, mod.rs:609-640, 904-926;
 // fq12.rs:62-110), the tail of config 5: k_horner_tree (kernels_wide.hip)'s
 // recombination on the 16-lane groups, then the final exponentiation's last chunk
-// on the whole block in the digit-sliced layout (BN_TAIL_DS, fq12_ds.h: one digit
+// on the whole block in the digit-sliced layout (fq12_ds.h: one digit
 // per lane, ~1.7x shorter squarings and ~1.5x shorter products than the 16-lane
-// ones on the chain, tools/ds_check).  BN_TAIL_DS=0 builds the round-5 form: the
-// squarer S on a PAIR of 16-lane groups of one wave (w12_cyc32: the helper
-// computes the xi * P products beside the main group's P), channel ch < 4: S =
-// groups 2ch, 2ch + 1 (waves 0-1), M = group 8 + ch (wave 2).  Values are
-// k_horner_tree's.
-#ifndef BN_TAIL_DS
-#define BN_TAIL_DS 1
-#endif
-// k_seg_fe1's first chunk with the Fq12 inversion's products spread over a group's
-// lane pairs (w12_fe_first_par); 0: w12_fe_first on one group (A/B)
-#ifndef BN_FE1_PAR
-#define BN_FE1_PAR 1
-#endif
+// ones on the chain, tools/ds_check).  Values are k_horner_tree's.
 #ifndef BN_TAIL_LATE_M
 #define BN_TAIL_LATE_M 0
 #endif
 #define BN_FOLD_LDS 1
 #define BN_WIDE_ARRS 4
-#define BN_S_CYC w12_cyc32
 #include "fq.h"
 #define BN_SPLIT 1
 #include "fq12_wide.h"
-#if BN_TAIL_DS
 #include "fq12_ds.h"
-#endif
-#ifndef TAIL_STAMP  // (fq12_ds.h defines the diagnostic stamps; BN_TAIL_DS=0 builds have none)
-#define BN_TAIL_STAMPS 0
-#define TAIL_STAMP(i) ((void)0)
-#endif
 
 namespace bn {
 
 constexpr int kTailThreads = BN_WIDE_THREADS;
 static_assert(kTailThreads == kTailBlock, "the launch (kernels.h kTailBlock) and the LDS layout agree");
 static_assert(kWGroups == 16, "four waves of four groups");
-constexpr int kTailDuo = 4;  // final-exponentiation channels: S pairs in waves 0-1, M in wave 2
-#if BN_TAIL_DS
 static_assert(kDsThreads == kTailThreads, "the digit-sliced element takes the whole block");
-#else
-__shared__ uint32_t g_tail_ch[kTailDuo * kDuoWords];
-#endif
-__shared__ uint32_t g_tail_cnt[kTailDuo * 4];
+// (nothing reads g_tail_cnt any more: k_horner_tree2's reset of it goes with the next change to
+// that kernel's code, since dropping it changes the kernel's instructions and LDS size)
+__shared__ uint32_t g_tail_cnt[16];
 __shared__ uint32_t g_tail_zero;
 
-#if BN_TAIL_DS
 // ---------------------------------------------------------------- the first chunk, in parallel
 // fq12.rs:62-73 of a nonzero f: c = conj(f) * f^-1 = conj(f)^2 * N^-1 with N = f conj(f)
 // = c0^2 - v c1^2 in Fq6 (fq12.rs:305-313: f^-1 = conj(f) N^-1), then frob^2(c) * c.
@@ -171,9 +148,7 @@ __device__ __noinline__ Fq<2> w12_fe_first_par(Fq<2> f) {
     }
     return r;
 }
-#endif
 
-#if BN_TAIL_DS
 // pairing_batch with several segments: block s takes segment s's value g_s (element
 // s of the split-layout array g, stride S), runs the final exponentiation's first
 // chunk on it (w12_fe_first, fq12.rs:62-73: a power map, so E1(prod g_s^(2^e_s)) =
@@ -225,11 +200,7 @@ __global__ void __launch_bounds__(kTailThreads) k_seg_fe1(uint32_t* __restrict__
         if (threadIdx.x == 0) zf[s] = zero ? 1u : 0u;
     }
     if (BN_TAIL_STAMPS && s == 0) TAIL_STAMP(16);
-#if BN_FE1_PAR
     x = w12_fe_first_par(x);  // group 0 gets the first chunk
-#else
-    if (threadIdx.x < (unsigned)kWLanes) x = w12_fe_first(x);
-#endif
     if (BN_TAIL_STAMPS && s == 0) TAIL_STAMP(17);
     ds_init();
     uint32_t d = ds_from_w12(x);
@@ -431,7 +402,6 @@ __global__ void __launch_bounds__(kTailThreads) k_fe_ds(const uint32_t* __restri
     ds_init();
     tail_squarer(ds_from_w12(x), pw + kRoleWord, ch, epoch, err, &out[i], w, ok ? ok + i : nullptr);
 }
-#endif
 
 // g: the S segment values (element s of a split-layout array of stride S);
 // segment s's value is raised to 2^(len_(s+1) + ... + len_(S-1)), the values are
@@ -445,8 +415,8 @@ __global__ void __launch_bounds__(kTailThreads) k_horner_tree2(const uint32_t* _
                                                                const uint32_t* __restrict__ zf) {
     if (BN_TAIL_STAMPS) TAIL_STAMP(blockIdx.x == 0 ? 0 : 24);
     if (threadIdx.x == 0) g_tail_zero = 0;
-    if (threadIdx.x < kTailDuo * 4) g_tail_cnt[threadIdx.x] = 0;
-    __syncthreads();  // the resets are seen before any group can use them
+    if (threadIdx.x < 16) g_tail_cnt[threadIdx.x] = 0;
+    __syncthreads();  // the reset is seen before any group can set the flag
     fold_table_init();
     const WL w = wl();
     const int grp = (int)threadIdx.x / kWLanes;
@@ -458,7 +428,6 @@ __global__ void __launch_bounds__(kTailThreads) k_horner_tree2(const uint32_t* _
         e0 += plan.hi[t] - plan.lo[t];
         if (t > grp) e += plan.hi[t] - plan.lo[t];
     }
-#if BN_TAIL_DS
     if (do_fe && zf && blockIdx.x == 1) {  // the multiplier block of the final exponentiation
 #if BN_TAIL_LATE_M  // test build (`make chanfail`): M starts ~2 ms late, so the squarer must go on alone
         for (int t = 0; t < 40000; ++t) __builtin_amdgcn_s_sleep(1);
@@ -473,7 +442,6 @@ __global__ void __launch_bounds__(kTailThreads) k_horner_tree2(const uint32_t* _
         if (BN_TAIL_STAMPS) TAIL_STAMP(26);
         return;
     }
-#endif
     if (do_fe && zf) {
         if (threadIdx.x < (unsigned)plan.S && zf[threadIdx.x]) g_tail_zero = 1;
         e0 = 0;  // k_seg_fe1 did the first chunk and the squarings
@@ -513,7 +481,6 @@ __global__ void __launch_bounds__(kTailThreads) k_horner_tree2(const uint32_t* _
     x = w_get<2>(slot(0), w.l);
     __syncthreads();  // slot 0 is group 0's operand area again from here on
     uint32_t words[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#if BN_TAIL_DS
     if (do_fe) {
         const bool zero = g_tail_zero != 0;
         if (zero && err && threadIdx.x == 0) err_or(err, BN_ERR_FE_ZERO);
@@ -539,25 +506,6 @@ __global__ void __launch_bounds__(kTailThreads) k_horner_tree2(const uint32_t* _
         fq_store_ref(x, words);
     }
     if (threadIdx.x < 12) st_words(&out[0].c[w_gt_index(w)], words);
-#else
-    if (do_fe) {
-        if (grp >= 3 * kTailDuo) return;  // wave 3
-        const bool m = grp >= 2 * kTailDuo;
-        const int ch = m ? grp - 2 * kTailDuo : grp >> 1;
-        WDuo d = {g_tail_ch + ch * kDuoWords, g_tail_cnt + 4 * ch, 0, 0, err};
-        if (m) {
-            w12_final_exp_m(d);
-            return;
-        }
-        const bool zero = g_tail_zero != 0;
-        if (zero && err && w.l == 0 && grp == 0) err_or(err, BN_ERR_FE_ZERO);
-        const Fq<2> r = w12_fe_last_s(x, d);
-        if (!zero) fq_store_ref(r, words);
-    } else {
-        fq_store_ref(x, words);
-    }
-    if (w.l < 12 && grp == 0) st_words(&out[0].c[w_gt_index(w)], words);
-#endif
 }
 
 }  // namespace bn

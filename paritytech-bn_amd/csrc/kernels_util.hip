@@ -1,13 +1,13 @@
 // kernels_util.hip -- Gt image <-> lane-strided conversion.
-// Pairing-path layout (BN_PATH_SPLIT: two lanes per element, kernels.h); n,
+// Pairing-path layout (two lanes per element, kernels.h); n,
 // m, half and stride count elements, the grid has kPathLanes threads each.
 #include "fq.h"
-#define BN_SPLIT BN_PATH_SPLIT
+#define BN_SPLIT 1
 #include "kernels.h"
 
 namespace bn {
 
-constexpr size_t kL = BN_SPLIT ? 2 : 1;  // lanes per element in this translation unit
+constexpr size_t kL = 2;  // lanes per element in this translation unit
 
 // Gt images <-> lane-strided internal Fq12
 __global__ void BN_PATH_ATTR __launch_bounds__(kBlock) k_gt_load(const bn_gt* __restrict__ g, size_t n,

@@ -17,7 +17,7 @@ namespace bn {
 __device__ __forceinline__ size_t w_elem() { return lane_id() / kWLanes; }
 
 // Element and role of this group in the final-exponentiation kernels: with
-// BN_FE_DUO a block holds kWGroups / 2 elements, each with its squarer group in
+// `duo` a block holds kWGroups / 2 elements, each with its squarer group in
 // waves 0-1 and its multiplier group in waves 2-3 (fq12_wide.h), and channel
 // `slot` of the block; else one element per group, every group a squarer.
 struct WRole {
@@ -27,66 +27,44 @@ struct WRole {
 };
 constexpr int kDuoPerBlock = kWGroups / 2;
 __device__ __forceinline__ WRole w_role(bool duo) {
-#if BN_FE_DUO
     if (duo) {
         const int g = (int)threadIdx.x / kWLanes;
         return {(size_t)blockIdx.x * kDuoPerBlock + (size_t)(g % kDuoPerBlock), g < kDuoPerBlock, true, g % kDuoPerBlock};
     }
-#endif
-    (void)duo;
     return {w_elem(), true, false, 0};
 }
-#if BN_FE_DUO
 __shared__ uint32_t g_wduo_ch[kDuoPerBlock * kDuoWords];  // 36 KB
 __shared__ uint32_t g_wduo_cnt[kDuoPerBlock * 4];
-#endif
 // zero the block's channel counters (every thread of the block calls it)
 __device__ __forceinline__ void w_duo_init() {
-#if BN_FE_DUO
     if (threadIdx.x < kDuoPerBlock * 4) g_wduo_cnt[threadIdx.x] = 0;
     __syncthreads();
-#endif
 }
 // the final exponentiation on S (with its M running w12_final_exp_m), or on
 // the group alone
 __device__ __forceinline__ Fq<2> w_final_exp(const WRole& r, const Fq<2>& x, int* err) {
-#if BN_FE_DUO
     if (r.duo) {
         WDuo d = {g_wduo_ch + r.slot * kDuoWords, g_wduo_cnt + 4 * r.slot, 0, 0, err};
         return w12_final_exp_s(x, d);
     }
-#endif
-    (void)r;
-    (void)err;
     return w12_final_exp(x);
 }
 // the last chunk only, of s = w12_fe_first(x) (k_horner_tree)
 __device__ __forceinline__ Fq<2> w_fe_last(const WRole& r, const Fq<2>& s, int* err) {
-#if BN_FE_DUO
     if (r.duo) {
         WDuo d = {g_wduo_ch + r.slot * kDuoWords, g_wduo_cnt + 4 * r.slot, 0, 0, err};
         return w12_fe_last_s(s, d);
     }
-#endif
-    (void)r;
-    (void)err;
     return w12_fe_last(s);
 }
 // M's part; true if this group is M (and has done it)
 __device__ __forceinline__ bool w_final_exp_m(const WRole& r, bool run, int* err) {
-#if BN_FE_DUO
     if (r.sq) return false;
     if (run) {
         WDuo d = {g_wduo_ch + r.slot * kDuoWords, g_wduo_cnt + 4 * r.slot, 0, 0, err};
         w12_final_exp_m(d);
     }
     return true;
-#else
-    (void)r;
-    (void)run;
-    (void)err;
-    return false;
-#endif
 }
 
 // out[e] = final_exponentiation(f[e]) for e < n, f lane-strided (split layout,
@@ -199,7 +177,7 @@ __global__ void __launch_bounds__(kBlock) k_horner_wide(const uint32_t* __restri
 // on one, every group runs group 0's number of squarings and keeps its own
 // count's result, every group computes each tree level's product and keeps it
 // where the level needs it, and the last chunk then runs on every group pair --
-// S groups 0-7 with M groups 8-15 (BN_FE_DUO) -- on copies of group 0's value;
+// S groups 0-7 with M groups 8-15 (`duo`) -- on copies of group 0's value;
 // group 0 stores the result.
 __shared__ uint32_t g_hor_zero;
 __global__ void __launch_bounds__(kBlock) k_horner_tree(const uint32_t* __restrict__ g, SegPlan plan, int do_fe,

@@ -22,7 +22,7 @@ namespace bn {
 // ---------------------------------------------------------------- k_pairing_latency
 // pairing() of a few pairs in ONE launch, for latency (bn_pairing_many_dev
 // batches of at most kLatencyMaxDefault pairs, capi.hip).  A block holds
-// kLatPairs pairs and three waves (four with BN_FE_DUO):
+// kLatPairs pairs and four waves:
 //  - wave 0, the producer: to_affine and the 87 line coefficients of each pair
 //    on eight lanes (lines_wide.h, as k_prepare_wide), each line scaled by P
 //    (ell_vw * Py, ell_vv * Px: mod.rs:589) and put into the pair's LDS ring;
@@ -30,8 +30,8 @@ namespace bn {
 //    on the wide layout (fq12_wide.h) right behind the producer -- per digit
 //    the generic square and the sparse product by each line as it arrives
 //    (mod.rs:579-607's order, so the Miller value is the reference's) -- then
-//    the final exponentiation (w12_final_exp), and stores the Gt image;
-//  - BN_FE_DUO: the consumer is the squarer of the two-group final
+//    the final exponentiation, and stores the Gt image;
+//  - the consumer is the squarer of the two-group final
 //    exponentiation (fq12_wide.h w12_final_exp_s); the multiplier groups are
 //    wave 0 once its lines are out (pairs 0-3) and wave 3 (pairs 4-7).
 // The loop needs no segments and no Horner recombination, and the three
@@ -44,7 +44,7 @@ namespace bn {
 // a wait that runs out of its cap sets BN_ERR_INTERNAL (the call then fails).
 // (the ring itself, g_lat_ring, is declared in fq12_wide.h beside w12_mul_line)
 __shared__ uint32_t g_lat_prod[kLatPairs], g_lat_cons[kLatPairs], g_lat_skip[kLatPairs];
-__shared__ uint32_t g_lat_duo[kLatPairs * 4];  // BN_FE_DUO: the counters of each pair's channel
+__shared__ uint32_t g_lat_duo[kLatPairs * 4];  // the counters of each pair's final-exponentiation channel
 static_assert(kDuoWords <= kLatRing * kLatLineWords, "the FE channel reuses the pair's line ring");
 constexpr uint32_t kLatSpinCap = kSpinCap;  // fq12_wide.h: ~4 s of s_sleep 1, never reached while both sides run
 
@@ -64,7 +64,6 @@ __device__ uint64_t g_lat_stamps[8];
 #define LAT_STAMP(cond, k) ((void)0)
 #endif
 
-#if BN_FE_DUO
 // the multiplier group of pair j (fq12_wide.h, two-group final exponentiation);
 // its channel is the pair's line ring, free once the Miller loop has read every
 // line -- before S hands over anything
@@ -75,7 +74,6 @@ __device__ __forceinline__ void lat_multiplier(int j, size_t base, size_t n, con
     WDuo duo = {g_lat_ring + j * kLatRing * kLatLineWords, g_lat_duo + 4 * j, 0, 0, err};
     w12_final_exp_m(duo);
 }
-#endif
 
 // f_out != null (pairing_batch / miller_loop_batch): the Miller values go to
 // f_out (split layout, lane-strided, stride n; a zero-point pair's is one) for the
@@ -133,7 +131,6 @@ __global__ void __launch_bounds__(kLatThreads) BN_LAT_KERNEL_ATTR BN_LAT_KERNEL_
         G2Proj r = {a.qa.x, a.qa.y, widen<kPt>(fq2_one())};
         const auto qy_neg = fq2_neg(a.qa.y);
         int line = 0;
-#if BN_LINES_PRESCALED
         // the P products from the steps' free slots (lines_wide.h PwEll): slot 0 writes
         // ell_0, slot 2 ell_vw * Py (x4), slot 3 ell_vv * Px (x2), each from its own lanes
         // (one select and one ring write per lane at a per-slot offset, not a write per
@@ -162,48 +159,14 @@ __global__ void __launch_bounds__(kLatThreads) BN_LAT_KERNEL_ATTR BN_LAT_KERNEL_
         q2.y = narrow<kPt>(fq2_neg(q2.y));
         emit(line++, pw_mixed_addition_step_p(r, q1, fq2_scale(q1.x, a.py), k, py_r, px_r));
         emit(line++, pw_mixed_addition_step_p(r, q2, fq2_scale(q2.x, a.py), k, py_r, px_r));
-#else
-        auto emit = [&](int ln_i, const Ell& e) {
-            // slots 0, 2 scale ell_vw by Py, slots 1, 3 ell_vv by Px (one product
-            // per lane instead of two); slot 0 takes x2 from slot 1
-            const bool odd_slot = (k & 1) != 0;
-            const auto y = narrow<kLine>(fq2_scale(fq2_select(odd_slot, e.ell_vv, e.ell_vw), fq_select(odd_slot, a.px, a.py)));
-            const auto x2 = pw_from(y, 1);
-            ring_wait(ln_i);
-            if (st) {
-                ring_put(ln_i, 0, e.ell_0);
-                ring_put(ln_i, 1, y);
-                ring_put(ln_i, 2, x2);
-            }
-            announce(ln_i);
-        };
-#pragma unroll 1
-        for (int d = 0; d < BN_NAF_DIGITS; ++d) {
-            emit(line++, pw_doubling_step(r, k));
-            if ((kNafNonzero >> d) & 1u) {
-                const bool minus = (kNafMinus >> d) & 1u;
-                const G2Aff<kPt> bq = {a.qa.x, fq2_select(minus, widen<kPt>(qy_neg), a.qa.y)};
-                emit(line++, pw_mixed_addition_step(r, bq, k));
-            }
-        }
-        G2Aff<kPt> q1 = mul_by_q(a.qa);
-        G2Aff<kPt> q2 = mul_by_q(q1);
-        q2.y = narrow<kPt>(fq2_neg(q2.y));
-        emit(line++, pw_mixed_addition_step(r, q1, k));
-        emit(line++, pw_mixed_addition_step(r, q2, k));
-#endif
         LAT_STAMP(threadIdx.x == 0, 2);  // producer: last line out
-#if BN_FE_DUO
         lat_multiplier((int)threadIdx.x / kWLanes, base, n, f_out, err);
-#endif
         return;
     }
-#if BN_FE_DUO
     if (threadIdx.x >= 64 + kLatPairs * kWLanes) {  // wave 3: the multipliers of pairs 4-7
         lat_multiplier(kLatPairs / 2 + ((int)threadIdx.x - 64 - kLatPairs * kWLanes) / kWLanes, base, n, f_out, err);
         return;
     }
-#endif
     // ---- consumer groups: pair j on a 16-lane group of waves 1-2
     const int j = ((int)threadIdx.x - 64) / kWLanes;
     // idle groups repeat the block's last pair (the producer fills their rings
@@ -263,12 +226,8 @@ __global__ void __launch_bounds__(kLatThreads) BN_LAT_KERNEL_ATTR BN_LAT_KERNEL_
     }
     const bool zero = w12_is_zero(x);
     if (zero && err && w.l == 0 && live) err_or(err, BN_ERR_FE_ZERO);
-#if BN_FE_DUO
     WDuo duo = {g_lat_ring + j * kLatRing * kLatLineWords, g_lat_duo + 4 * j, 0, 0, err};
     const Fq<2> res = w12_final_exp_s(x, duo);
-#else
-    const Fq<2> res = w12_final_exp(x);
-#endif
     LAT_STAMP(threadIdx.x == 64, 5);  // consumer: final exponentiation done
     uint32_t words[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (!zero) fq_store_ref(res, words);

@@ -8,7 +8,7 @@
 
 namespace bn {
 
-constexpr size_t kL = BN_SPLIT ? 2 : 1;  // lanes per pairing in the including translation unit
+constexpr size_t kL = 2;  // lanes per pairing in the including translation unit
 
 // ---------------------------------------------------------------- pairing kernels
 // to_affine of both points of pair i (mod.rs:199-216; the z == 1 shortcut yields
@@ -31,7 +31,6 @@ __device__ __forceinline__ PairAffine pair_to_affine(const bn_g1* __restrict__ p
     const bool p_zero = words_zero(w);
     const bool p_one = words_one(w);
     const Fq<2> pz = fq_load_ref(w);
-#if BN_SPLIT
     uint32_t wz[8];
     ld_words(lane_odd() ? &q[i].z.c1 : &q[i].z.c0, wz);  // this lane's coordinate of z
     const uint32_t own_zero = words_zero(wz) ? 1u : 0u;
@@ -41,15 +40,6 @@ __device__ __forceinline__ PairAffine pair_to_affine(const bn_g1* __restrict__ p
     const Fq2<2> qz = {fq_load_ref(wz)};
     const auto qz_sq = fq_sqr(qz.c);
     const auto nq = fq_add(qz_sq, fq_partner(qz_sq));  // N(qz) = z0^2 + z1^2, the same on both lanes
-#else
-    uint32_t w0[8], w1[8];
-    ld_words(&q[i].z.c0, w0);
-    ld_words(&q[i].z.c1, w1);
-    const bool q_zero = words_zero(w0) && words_zero(w1);
-    const bool q_one = words_one(w0) && words_zero(w1);
-    const Fq2<2> qz = {fq_load_ref(w0), fq_load_ref(w1)};
-    const auto nq = fq_add(fq_sqr(qz.c0), fq_sqr(qz.c1));
-#endif
     if ((p_zero || q_zero) && mode == 1 && (l % kL) == 0) err_or(err, BN_ERR_TO_AFFINE);
     if (flags) flags[l] = (p_zero || q_zero) ? 1 : 0;
 
@@ -75,12 +65,8 @@ __device__ __forceinline__ PairAffine pair_to_affine(const bn_g1* __restrict__ p
     a.skip = p_zero || q_zero;
     a.px = fq_mul(ld_ref(p[i].x), pzinv2);
     a.py = fq_mul(ld_ref(p[i].y), fq_mul(pzinv2, pzinv));
-#if BN_SPLIT
     const auto zn = fq_mul(qz.c, ninv);
     const auto qzinv = wrap2(fq_select(lane_odd(), fq_neg(zn), zn));  // conj(qz) * ninv
-#else
-    const auto qzinv = mk2(fq_mul(qz.c0, ninv), fq_neg(fq_mul(qz.c1, ninv)));
-#endif
     auto qzinv2 = fq2_sqr(qzinv);
     a.qa = {narrow<kPt>(fq2_mul(ld_ref2(q[i].x), qzinv2)), narrow<kPt>(fq2_mul(ld_ref2(q[i].y), fq2_mul(qzinv2, qzinv)))};
     return a;
@@ -103,7 +89,6 @@ __device__ __forceinline__ PairScaled pair_scaled(const bn_g1* __restrict__ p, c
     ld_words(&p[i].z, w);
     const bool p_zero = words_zero(w);
     const Fq<2> pz = fq_load_ref(w);
-#if BN_SPLIT
     uint32_t wz[8];
     ld_words(lane_odd() ? &q[i].z.c1 : &q[i].z.c0, wz);  // this lane's coordinate of z
     const uint32_t own_zero = words_zero(wz) ? 1u : 0u;
@@ -111,14 +96,6 @@ __device__ __forceinline__ PairScaled pair_scaled(const bn_g1* __restrict__ p, c
     const Fq2<2> qz = {fq_load_ref(wz)};
     const auto qz_sq = fq_sqr(qz.c);
     const auto nq = fq_add(qz_sq, fq_partner(qz_sq));  // N(qz), the same on both lanes
-#else
-    uint32_t w0[8], w1[8];
-    ld_words(&q[i].z.c0, w0);
-    ld_words(&q[i].z.c1, w1);
-    const bool q_zero = words_zero(w0) && words_zero(w1);
-    const Fq2<2> qz = {fq_load_ref(w0), fq_load_ref(w1)};
-    const auto nq = fq_add(fq_sqr(qz.c0), fq_sqr(qz.c1));
-#endif
     if (flags) flags[l] = (p_zero || q_zero) ? 1 : 0;
     const ScaledPair s = scaled_inputs(ld_ref(p[i].x), ld_ref(p[i].y), pz, ld_ref2(q[i].x), ld_ref2(q[i].y), qz, nq);
     return {s.px, s.py, s.qa, s.coeff, p_zero || q_zero};
@@ -139,7 +116,6 @@ __device__ __forceinline__ auto pair_inputs(const bn_g1* __restrict__ p, const b
 __device__ __forceinline__ auto pair_coeff(const PairAffine&) { return doubling_coeff(); }
 __device__ __forceinline__ G2Coeff pair_coeff(const PairScaled& a) { return a.coeff; }
 
-#if BN_SPLIT
 // ---------------------------------------------------------------- k_prepare_wide
 // The same to_affine + 87 line coefficients for small batches, on EIGHT lanes
 // per pair: four lane pairs ("slots") run each line step's independent Fq2
@@ -195,55 +171,11 @@ __device__ __forceinline__ auto pw_mul(int k, const X0& x0_in, const Y0& y0_in, 
     return fq2_mul(pw_pick(k, widen<JX>(x0), widen<JX>(x1), widen<JX>(x2), widen<JX>(x3)),
                    pw_pick(k, widen<JY>(y0), widen<JY>(y1), widen<JY>(y2), widen<JY>(y3)));
 }
-// doubling_step (curve.h) in three layers
-__device__ __forceinline__ Ell pw_doubling_step(G2Proj& s, int k) {
-    const auto l1 = pw_mul(k, s.x, s.y, s.y, s.y, s.z, s.z, s.x, s.x);  // x*y, y^2, z^2, x^2
-    const auto a = fq2_half(pw_from(l1, 0));
-    const auto b = pw_from(l1, 1);
-    const auto c = pw_from(l1, 2);
-    const auto j = pw_from(l1, 3);
-    const auto d = fq2_add(fq2_add(c, c), c);
-    const auto yz = fq2_add(s.y, s.z);
-    const auto bc = g2_coeff_b();
-    const auto l2 = pw_mul(k, bc, d, yz, yz, bc, d, yz, yz);  // e = b' * 3c, (y + z)^2
-    const auto e = pw_from(l2, 0);
-    const auto h = fq2_sub(pw_from(l2, 1), fq2_add(b, c));
-    const auto f = fq2_add(fq2_add(e, e), e);
-    const auto g = fq2_half(fq2_add(b, f));
-    const auto i = fq2_sub(e, b);
-    const auto l3 = pw_mul(k, a, fq2_sub(b, f), g, g, e, e, b, h);  // x', g^2, e^2, z'
-    const auto e_sq = pw_from(l3, 2);
-    s.x = narrow<kPt>(pw_from(l3, 0));
-    s.y = narrow<kPt>(fq2_sub(pw_from(l3, 1), fq2_add(fq2_add(e_sq, e_sq), e_sq)));
-    s.z = narrow<kPt>(pw_from(l3, 3));
-    return {narrow<kLine>(fq2_mul_xi(i)), narrow<kLine>(fq2_neg(h)), narrow<kLine>(fq2_add(fq2_add(j, j), j))};
-}
-// mixed_addition_step (curve.h) in four layers
-template <int BB>
-__device__ __forceinline__ Ell pw_mixed_addition_step(G2Proj& s, const G2Aff<BB>& base, int k) {
-    const auto l1 = pw_mul(k, s.z, base.x, s.z, base.y, s.z, base.x, s.z, base.y);  // z*bx, z*by
-    const auto d = fq2_sub(s.x, pw_from(l1, 0));
-    const auto e = fq2_sub(s.y, pw_from(l1, 1));
-    const auto l2 = pw_mul(k, d, d, e, e, e, base.x, d, base.y);  // f = d^2, g = e^2, e*bx, d*by
-    const auto f = pw_from(l2, 0);
-    const auto g = pw_from(l2, 1);
-    const auto l0 = fq2_mul_xi(fq2_sub(pw_from(l2, 2), pw_from(l2, 3)));
-    const auto l3 = pw_mul(k, d, f, s.x, f, s.z, g, s.z, g);  // h = d*f, i = x*f, z*g
-    const auto h = pw_from(l3, 0);
-    const auto i = pw_from(l3, 1);
-    const auto jj = fq2_sub(fq2_add(pw_from(l3, 2), h), fq2_add(i, i));
-    const auto l4 = pw_mul(k, d, jj, e, fq2_sub(i, jj), h, s.y, s.z, h);  // nx, e*(i - j), h*y, nz
-    s.x = narrow<kPt>(pw_from(l4, 0));
-    s.y = narrow<kPt>(fq2_sub(pw_from(l4, 1), pw_from(l4, 2)));
-    s.z = narrow<kPt>(pw_from(l4, 3));
-    return {narrow<kLine>(l0), narrow<kLine>(d), narrow<kLine>(fq2_neg(e))};
-}
-
 // ---------------------------------------------------------------- P-scaled lines from the free slots
 // The Miller loop multiplies by ell_0 + (ell_vw Py) w^3 + (ell_vv Px) w^4 (mod.rs:589).
-// The doubling step's middle layer above runs two distinct products on four slots and
+// Laid out on four slots, the doubling step's middle layer has two distinct products and
 // the addition's first and third layers three, so the two P products fit into slots
-// that were duplicates: the scaled coefficients cost the producer no extra layer, and
+// that would hold duplicates: the scaled coefficients cost the producer no extra layer, and
 // the consumer (k_miller_seg, k_miller, the latency kernel's groups) no longer scales
 // each line (two Fq products of its ~4,700 VALU per line).  Slot 2 ends up holding
 // ell_vw * Py and slot 3 ell_vv * Px (each in its own lanes: stored from there, no
@@ -301,7 +233,7 @@ __device__ __forceinline__ PwEll pw_doubling_step_p(G2Proj& s, int k, const Fq2<
 }
 // mixed_addition_step (curve.h) in four layers with the P products:
 // L1: z bx, z by, x Py, z (bx Py)  (d Py = x Py - z bx Py);  L2: d^2, e^2, e bx, d by;
-// L3: d f, x f, z g, e Px;  L4: as pw_mixed_addition_step.  bxpy = base.x * Py (per base)
+// L3: d f, x f, z g, e Px;  L4: nx, e (i - j), h y, nz.  bxpy = base.x * Py (per base)
 template <int BB, int XB, int PY, int PX>
 __device__ __forceinline__ PwEll pw_mixed_addition_step_p(G2Proj& s, const G2Aff<BB>& base, const Fq2<XB>& bxpy,
                                                           int k, const Fq2<PY>& py_r, const Fq2<PX>& px_r) {
@@ -327,8 +259,5 @@ __device__ __forceinline__ PwEll pw_mixed_addition_step_p(G2Proj& s, const G2Aff
     r.vv_px = narrow<kLine>(fq2_neg(l3));         // slot 3: -e Px
     return r;
 }
-
-
-#endif  // BN_SPLIT
 
 }  // namespace bn

@@ -108,7 +108,7 @@ BN_INLINE Fq12<kF> apply_line(const Fq12<B>& f, const Ell& c, const Fq<PB>& px, 
 }
 
 // the same with the line already scaled by P (e.ell_vw = ell_vw * Py, e.ell_vv = ell_vv * Px:
-// what the producers store with BN_LINES_PRESCALED, lines_wide.h PwEll)
+// what the producers store, lines_wide.h PwEll)
 template <int B>
 BN_INLINE Fq12<kF> apply_line_scaled(const Fq12<B>& f, const Ell& e) {
 #if BN_SPLIT

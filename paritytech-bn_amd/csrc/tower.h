@@ -681,14 +681,11 @@ BN_INLINE LineOpsT<kv(X), kv(X) + 1> line_ops_of(const Fq2<X>& v_in) {
     return {fq_select(odd, pv, v), fq_norm(fq_pick(odd, v, fq_neg_lazy(pv)))};
 #endif
 }
-// BN_DOT6_ASM: the sum as one v_mad_u64_u32 chain (dot2_asm.inc BN_ASM_DOT6) instead of
-// 17 64-bit column accumulators: k_miller_seg's loop spilled 27 dwords and reloaded 44
+// On the device the sum is one v_mad_u64_u32 chain (dot2_asm.inc BN_ASM_DOT6) instead of
+// 17 64-bit column accumulators (the host builds' form): k_miller_seg's loop spilled 27 dwords and reloaded 44
 // per line with the accumulators (scratch 320 -> 72 B per lane), config 5 1.84-1.90 ->
 // 1.76-1.80 ms and its PMC traffic 1.62 -> 0.80 GB per product, k_pairing_full unchanged
 // (profiles/r5w_ab_dot6.txt)
-#ifndef BN_DOT6_ASM
-#define BN_DOT6_ASM 1
-#endif
 // This lane's coordinate of a * va + b * vb + c * vc over Fq2, reduced once:
 //   REDC(sum over the three of own(u) * v.y + partner(u) * v.w),   pu = fq_partner(u).
 // Contract: every operand has normalized digits, so a column holds at most 54 digit
@@ -707,7 +704,7 @@ BN_INLINE auto fq_dot6p(const Fq<A>& a, const Fq<A>& pa, const LineOpsT<YA, WA>&
     constexpr int BO = 1 + (int)(S * 5908 / 1000000 + 1);
     static_assert(BO <= kMaxBound, "fq_dot6: the value must stay below 2^261");
     static_assert(S > 54 || BO == 2, "fq_dot6: the sparse line product's contract leaves below 2 p");
-#if BN_DOT6_ASM && BN_DOT2_ASM && defined(__HIP_DEVICE_COMPILE__)
+#if BN_DOT2_ASM && defined(__HIP_DEVICE_COMPILE__)
     Fq<BO> r;
     asm(BN_ASM_DOT6 : BN_ASM_OUT9(r.v)
         : BN_ASM_IN9(a.v), BN_ASM_IN9(va.y.v), BN_ASM_IN9(pa.v), BN_ASM_IN9(va.w.v), BN_ASM_IN9(b.v),
@@ -974,19 +971,11 @@ BN_INLINE auto fq12_mul_by_024(const Fq12<F>& f, const Fq2<X>& ell_0, const Fq2<
 }
 
 // fq12.rs:198-247 -- Granger-Scott cyclotomic squaring (the reference's formula)
-// BN_CYC_LAZY: t0, t2, t4 and xi*t5 leave with a carry pass instead of a fold (their
+// t0, t2, t4 and xi*t5 leave with a carry pass instead of a fold (their
 // digits normalized, the value bound carried on to the outputs' folds): 65 VALU fewer
 // per square with the asm column sums, k_pairing_full 7.47-7.48 -> 7.37-7.38 ms,
 // Gt::pow -1.2 % (profiles/r5u_ab_cyc_lazy.txt).  Every fold stays under the bound
 // check (fq.h fold_fetch; tools/fold_check.py).
-#ifndef BN_CYC_LAZY
-#define BN_CYC_LAZY 1
-#endif
-#if BN_CYC_LAZY
-#define BN_CYC_T(x) fq2_norm(x)
-#else
-#define BN_CYC_T(x) fq2_fold(x)
-#endif
 template <int A>
 BN_INLINE auto fq12_cyclotomic_sqr(const Fq12<A>& a) {
     const auto& z0 = a.c0.c0;
@@ -995,7 +984,7 @@ BN_INLINE auto fq12_cyclotomic_sqr(const Fq12<A>& a) {
     const auto& z2 = a.c1.c0;
     const auto& z1 = a.c1.c1;
     const auto& z5 = a.c1.c2;
-#if BN_SPLIT && BN_DOT2_ADDEND
+#if BN_SPLIT
     // On the addend chains (fq2_split.h): the even outputs n = 3t - 2z = 3(t - z) + z
     // with t - z straight from the product's chain (fq2_cyc_u) -- no xi * tmp pass,
     // K*p spreads or carry pass for t, and 3u + z keeps its digits below 4 * 2^29,
@@ -1027,23 +1016,23 @@ BN_INLINE auto fq12_cyclotomic_sqr(const Fq12<A>& a) {
 #if BN_CYC_LIN & 4
     auto n2 = wrap2(fq_lin<54, 6, 2>(tmp45.c, fq_neg_lazy(xt45), z2.c));
 #else
-    auto x5 = BN_CYC_T(fq2_dbl(fq2_mul_xi(tmp45)));  // xi * t5
+    auto x5 = fq2_norm(fq2_dbl(fq2_mul_xi(tmp45)));  // xi * t5
     auto n2 = fq2_add(fq2_dbl(fq2_add(x5, z2)), x5);
 #endif
 #else
     auto tmp01 = fq2_mul(z0, z1);
-    auto t0 = BN_CYC_T(fq2_sub(fq2_sub(fq2_mul(fq2_add(z0, z1), fq2_add(fq2_mul_xi(z1), z0)), tmp01), fq2_mul_xi(tmp01)));
+    auto t0 = fq2_norm(fq2_sub(fq2_sub(fq2_mul(fq2_add(z0, z1), fq2_add(fq2_mul_xi(z1), z0)), tmp01), fq2_mul_xi(tmp01)));
     auto t1 = fq2_dbl(tmp01);
     auto tmp23 = fq2_mul(z2, z3);
-    auto t2 = BN_CYC_T(fq2_sub(fq2_sub(fq2_mul(fq2_add(z2, z3), fq2_add(fq2_mul_xi(z3), z2)), tmp23), fq2_mul_xi(tmp23)));
+    auto t2 = fq2_norm(fq2_sub(fq2_sub(fq2_mul(fq2_add(z2, z3), fq2_add(fq2_mul_xi(z3), z2)), tmp23), fq2_mul_xi(tmp23)));
     auto t3 = fq2_dbl(tmp23);
     auto tmp45 = fq2_mul(z4, z5);
     auto xi45 = fq2_mul_xi(tmp45);  // also gives xi * t5 = 2 * xi * tmp45 below
-    auto t4 = BN_CYC_T(fq2_sub(fq2_sub(fq2_mul(fq2_add(z4, z5), fq2_add(fq2_mul_xi(z5), z4)), tmp45), xi45));
+    auto t4 = fq2_norm(fq2_sub(fq2_sub(fq2_mul(fq2_add(z4, z5), fq2_add(fq2_mul_xi(z5), z4)), tmp45), xi45));
 
     auto n0 = fq2_add(fq2_dbl(fq2_sub(t0, z0)), t0);
     auto n1 = fq2_add(fq2_dbl(fq2_add(t1, z1)), t1);
-    auto x5 = BN_CYC_T(fq2_dbl(xi45));  // xi * t5
+    auto x5 = fq2_norm(fq2_dbl(xi45));  // xi * t5
     auto n2 = fq2_add(fq2_dbl(fq2_add(x5, z2)), x5);
     auto n3 = fq2_add(fq2_dbl(fq2_sub(t4, z3)), t4);
     auto n4 = fq2_add(fq2_dbl(fq2_sub(t2, z4)), t2);

@@ -144,9 +144,9 @@ def main():
     dst = os.path.join(here, "..", "paritytech-bn_amd", "csrc", "dot2_asm.inc")
     lines = ["// dot2_asm.inc -- GENERATED by tools/gen_dot2_asm.py (do not edit): the single-chain",
              "// column sums of fq_dot2 / fq_mul / fq_sqr (fq2_split.h, fq.h BN_DOT2_ASM) and of the",
-             "// six-product sum of the sparse line product (pairing.h, BN_DOT6_ASM); DOT2A<n>: dot2",
+             "// six-product sum of the sparse line product (tower.h fq_dot6p); DOT2A<n>: dot2",
              "// with n addend vectors at weight R, LIN<n>: the normalized sum of n small multiples",
-             "// (fq2_split.h fq_dot2_add, fq_lin; BN_DOT2_ADDEND); MULA<n>: mul with n addend vectors,",
+             "// (fq2_split.h fq_dot2_add, fq_lin); MULA<n>: mul with n addend vectors,",
              "// DOT4[A<n>]: the four-product sum (fq2_split.h fq_mul_add, fq_dot4; curve.h BN_LINE_CHAIN).",
              "#pragma once"]
     for kind in KINDS:
