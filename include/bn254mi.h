@@ -295,6 +295,60 @@ int bn_set_msm_min(bn_ctx* ctx, size_t n);
  * it is separate from the pairing workspace and not counted by bn_workspace_bytes */
 int bn_msm_reserve(bn_ctx* ctx, size_t n);
 
+/* ---- G1 MSMs over prepared bases (window tables, no doubling) ----
+ * Many small MSMs over the SAME few G1 bases: a Groth16 verifier's vk_x = IC[0] + sum input_i IC[i]
+ * per proof, many commitments over one basis, batched fixed-base G1 * Fr (k = 1).  A bn_g1_prepared
+ * handle holds, on the device, for every base b and every window w of the signed c-bit recoding
+ * (W(c) = 254 / c + 1 windows, as bn_g1_msm), the affine points (j + 1) 2^(c w) bases[b] for
+ * j < 2^(c-1): 64 bytes each, and one zero flag per base.  An MSM is then k W(c) table lookups added
+ * up, with no doubling.
+ *   c: the window width, 2 .. 16; 0 takes the default, 10 (832 KiB per base;
+ *   bn_g1_prepared_window reports the width used).  Wider is faster and costs twice the memory
+ *   and the prepare time per bit.  k >= 1, and k W(c) 2^(c-1) entries must not exceed 2^31 - 1 (indices are 32-bit).
+ *   bn_g1_prepared_table_bytes(k, c) is host arithmetic (no device needed): the device bytes of that
+ *   table, 0 for arguments bn_g1_bases_prepare refuses.
+ *   Refused with BN_ERR_INVALID_ARGUMENT before anything is read, *out untouched: a NULL bases or
+ *   out, a k or c outside those limits, a multi-device context (a device context from bn_ctx_device
+ *   works).
+ *   bases[b] may be any Jacobian image (z != one; z == 0 with arbitrary x, y: such a base
+ *   contributes nothing); points are assumed to be on the curve, as everywhere in the group API.
+ *   The handle belongs to the context that made it, exactly as a bn_g2_prepared: any other context
+ *   refuses it; bn_g1_prepared_destroy waits for the work that reads it, then frees it;
+ *   bn_ctx_destroy frees the handles still alive.  The table is the handle's own memory, not
+ *   counted by bn_workspace_bytes.
+ * The _dev form takes device bases and enqueues on `stream` without synchronizing (it allocates
+ * the table first). */
+typedef struct bn_g1_prepared bn_g1_prepared;
+size_t bn_g1_prepared_table_bytes(size_t k, int c);
+int bn_g1_bases_prepare(bn_ctx* ctx, const bn_g1* bases, size_t k, int c, bn_g1_prepared** out);
+int bn_g1_bases_prepare_dev(bn_ctx* ctx, const bn_g1* d_bases, size_t k, int c, bn_g1_prepared** out, void* stream);
+size_t bn_g1_prepared_count(const bn_g1_prepared* prepared);
+int bn_g1_prepared_window(const bn_g1_prepared* prepared);
+int bn_g1_prepared_destroy(bn_ctx* ctx, bn_g1_prepared* prepared);
+/* out[j * out_stride] = (sum over b < k of bases[b] * k[j * k + b]).normalize() for j < m: `k` is an
+ * m x k row-major matrix of Fr images (k = the handle's count), and every output is the image
+ * bn_g1_msm(bases, row j) returns, bit for bit: (x, y, one), and (0, one, 0) for a zero sum.
+ *   out_stride counts points and must be >= 1; the points between the strided outputs are not
+ *   written (stride 4 writes vk_x straight into the interleaved p array of
+ *   bn_pairing_batch_prepared_many_dev for Groth16).
+ *   m == 0 returns BN_OK and touches nothing.  Refused with BN_ERR_INVALID_ARGUMENT: a NULL k or out
+ *   with m > 0; a NULL handle, one of another context or a destroyed one; out_stride == 0; a
+ *   multi-device context; m above 2^26.  No outcome depends on the data: the _dev form has no
+ *   status to report.
+ * L lanes per output each add their share of the lookups; the partial sums (96 bytes per lane,
+ * at most 2^20 lanes at a time: more outputs run in sets) live in the G1 MSM workspace, grown on
+ * first use or by bn_msm_reserve(n) for calls of up to n = m L lanes.  The _dev form enqueues on
+ * `stream` without synchronizing; it may allocate (and then waits for earlier work) on first use at
+ * a larger size. */
+int bn_g1_msm_prepared_many(bn_ctx* ctx, const bn_g1_prepared* prepared, const bn_fr* k, size_t m, bn_g1* out,
+                            size_t out_stride);
+int bn_g1_msm_prepared_many_dev(bn_ctx* ctx, const bn_g1_prepared* prepared, const bn_fr* d_k, size_t m,
+                                bn_g1* d_out, size_t out_stride, void* stream);
+/* lanes per output of the lookup kernel: a power of two from 1 to 64, or 0 (default) = chosen from
+ * m and k.  Anything else is refused with BN_ERR_INVALID_ARGUMENT.  Results are identical for every
+ * value. */
+int bn_set_msm_prepared_lanes(bn_ctx* ctx, int lanes);
+
 /* ---- G2 multi-scalar multiplication (bucket method on the two-lane layout) ---- */
 
 /* The same contract over G2: *out = (sum over i < n of p[i] * k[i]).normalize(), the image (x, y, one)

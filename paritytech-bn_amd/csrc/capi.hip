@@ -944,7 +944,7 @@ static void ctx_teardown(bn_ctx* c) {
     for (void* p : {(void*)c->coeffs, (void*)c->paff, (void*)c->slots, (void*)c->flags, (void*)c->d_err,
                     (void*)c->d_prog, c->stage, (void*)c->tail_ws, (void*)c->fe_ds_ws, (void*)c->msm_keys,
                     (void*)c->msm_sorted, (void*)c->msm_g1.buckets, (void*)c->msm_g1.parts, (void*)c->msm_g1.tmp,
-                    (void*)c->msm_g2.buckets, (void*)c->msm_g2.parts, (void*)c->msm_g2.tmp})
+                    (void*)c->msm_g2.buckets, (void*)c->msm_g2.parts, (void*)c->msm_g2.tmp, (void*)c->msm_g1.fixed})
         if (p) (void)hipFree(p);
     for (bn_g2_prepared* h : c->prepared) {  // the handles still alive (the streams are drained)
         if (h->table) (void)hipFree(h->table);
@@ -952,6 +952,12 @@ static void ctx_teardown(bn_ctx* c) {
         delete h;
     }
     c->prepared.clear();
+    for (bn_g1_prepared* h : c->g1_prepared) {
+        if (h->table) (void)hipFree(h->table);
+        if (h->zero) (void)hipFree(h->zero);
+        delete h;
+    }
+    c->g1_prepared.clear();
     for (auto& ev : c->ev_marks)
         for (auto e : ev) c->ev_pool.push_back(e);
     for (auto e : c->ev_pool)

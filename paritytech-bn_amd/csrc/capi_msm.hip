@@ -2,12 +2,19 @@
 // bn_g2_msm; kernels_msm.hip, kernels_msm_g2.hip).  The bucket path
 // and the small path return the same image: the group law is exact and the result is
 // normalized.  The host sequence is one template over the point type; MsmGroup<P>
-// names the group's kernels, settings and buffers.
+// names the group's kernels, settings and buffers.  Behind it, the bn_g1_prepared handles
+// and bn_g1_msm_prepared_many (kernels_msm_fixed.hip; §8c).
+#include <type_traits>
+
 #include "capi_internal.h"
+#include "msm_fixed.h"
 
 using namespace bn;
 
 constexpr size_t kMsmMaxTerms = size_t(1) << 26;  // the entry index keeps bit 31 for the sign; keys and positions are 32-bit
+// Lanes (partial sums of 96 bytes) per launch set of bn_g1_msm_prepared_many: a call of more
+// runs its outputs in sets of this many lanes through the same buffer.
+constexpr size_t kFixedSetLanes = size_t(1) << 20;
 template <class P>
 struct MsmGroup;
 template <>
@@ -90,16 +97,23 @@ static int msm_reserve(bn_ctx* c, size_t n, const MsmPlan& m) {
     RET_IF(grow_dev(c, &g.buckets, &g.buckets_cap, (size_t)m.nkeys));
     return grow_dev(c, &g.parts, &g.parts_cap, (size_t)m.nseg * m.nwin);
 }
-// buf[0] = sum of buf[0 .. m) by a halving addition tree in place (odd tail carried),
-// then *d_out = its returned image (finish) or the Jacobian sum as it stands
+// buf[0 .. width) = sum of the m rows of `width` points at buf by a halving addition tree in
+// place (odd tail carried)
+template <class P>
+static void msm_tree(P* buf, size_t m, size_t width, hipStream_t s) {
+    while (m > 1) {
+        const size_t h = (m + 1) / 2;
+        MsmGroup<P>::k_op<<<grid_for((m - h) * width), kBlock, 0, s>>>(kGroupAdd, buf, buf + h * width, (m - h) * width, buf, nullptr);
+        m = h;
+    }
+}
+// the tree, then for width 1 *d_out = the sum's returned image (finish) or the Jacobian sum
+// as it stands
 template <class P>
 static int msm_tree_out(bn_ctx* c, P* buf, size_t m, size_t width, int finish, P* d_out, hipStream_t s) {
     using G = MsmGroup<P>;
-    while (m > 1) {
-        const size_t h = (m + 1) / 2;
-        G::k_op<<<grid_for((m - h) * width), kBlock, 0, s>>>(kGroupAdd, buf, buf + h * width, (m - h) * width, buf, nullptr);
-        m = h;
-    }
+    msm_tree(buf, m, width, s);
+    m = m ? 1 : 0;
     if (width != 1) return BN_OK;
     if (finish)
         G::k_finish<<<1, 64, 0, s>>>(m ? buf : nullptr, d_out);
@@ -200,9 +214,154 @@ static int msm_reserve_terms(bn_ctx* c, size_t n) {
     const MsmPlan m = msm_plan<P>(c, n);
     if (!m.small && m.nent > (size_t)0x7fffffff)
         return fail(c, BN_ERR_INVALID_ARGUMENT, "n * windows exceeds the 32-bit entry positions at this window width");
-    return msm_reserve<P>(c, n, m);
+    RET_IF(msm_reserve<P>(c, n, m));
+    // and the partial sums of the prepared-bases MSM for calls of up to n lanes (G1 only)
+    if constexpr (std::is_same<P, bn_g1>::value)
+        return grow_dev(c, &c->msm_g1.fixed, &c->msm_g1.fixed_cap, std::min(n, kFixedSetLanes));
+    return BN_OK;
 }
+
+// ---------------------------------------------------------------- prepared bases
+// a live handle of this context (looked up, not dereferenced)
+static bool g1_prepared_live(const bn_ctx* c, const bn_g1_prepared* h) {
+    return h && std::find(c->g1_prepared.begin(), c->g1_prepared.end(), h) != c->g1_prepared.end();
+}
+// refused before anything is read: a NULL bases or out, a width outside 2 .. 16 (0: the
+// default), a k that is 0 or whose table exceeds the 32-bit entry indices
+static int g1_prepare_args(bn_ctx* c, const void* bases, size_t k, int cw, bn_g1_prepared** out) {
+    if (!bases || !out) return fail(c, BN_ERR_INVALID_ARGUMENT, "null buffer");
+    if (cw != 0 && !msm_window_ok(cw)) return fail(c, BN_ERR_INVALID_ARGUMENT, "window width outside 2 .. 16 (0: default)");
+    if (!msm_fixed_entries(k, cw))
+        return fail(c, BN_ERR_INVALID_ARGUMENT, "k is 0 or k * windows * 2^(c-1) exceeds the 32-bit entry indices");
+    return BN_OK;
+}
+// Fills a new handle on stream s from the k bases (host memory, or device memory when dev).
+// The caller holds the lock and has ordered s after the workspace's previous user (the host
+// form stages the bases).
+static int g1_prepare_fill(bn_ctx* c, bn_g1_prepared* h, const bn_g1* bases, bool dev, hipStream_t s) {
+    HIPCHK(c, hipMalloc(&h->table, (size_t)h->nent * 2 * sizeof(bn_fq)));
+    HIPCHK(c, hipMalloc(&h->zero, h->k));
+    const bn_g1* d = bases;
+    if (!dev) {
+        void* at[1];
+        RET_IF(stage_regions(c, {h->k * sizeof(bn_g1)}, at));
+        HIPCHK(c, hipMemcpyAsync(at[0], bases, h->k * sizeof(bn_g1), hipMemcpyHostToDevice, s));
+        d = (const bn_g1*)at[0];
+    }
+    k_g1_table_build<<<grid_for(h->k * (size_t)msm_windows(h->c)), kBlock, 0, s>>>(d, (uint32_t)h->k, h->c, h->table,
+                                                                                   h->zero, h->nent);
+    HIPCHK(c, hipGetLastError());
+    return BN_OK;
+}
+static int g1_prepare(bn_ctx* c, const bn_g1* bases, bool dev, size_t k, int cw, bn_g1_prepared** out, hipStream_t s) {
+    bn_g1_prepared* h = new bn_g1_prepared();
+    h->k = k;
+    h->c = cw ? cw : kMsmFixedWindow;
+    h->nent = (uint32_t)msm_fixed_entries(k, h->c);
+    int rc = g1_prepare_fill(c, h, bases, dev, s);
+    if (rc == BN_OK && !dev && hipStreamSynchronize(s) != hipSuccess) rc = fail(c, BN_ERR_HIP, "hipStreamSynchronize");
+    if (rc != BN_OK) {
+        (void)hipStreamSynchronize(s);  // nothing queued may still write the table
+        if (h->table) (void)hipFree(h->table);
+        if (h->zero) (void)hipFree(h->zero);
+        delete h;
+        return rc;
+    }
+    c->g1_prepared.push_back(h);
+    *out = h;
+    return BN_OK;
+}
+static int msm_prepared_args(bn_ctx* c, const bn_g1_prepared* h, const void* k, size_t m, const void* out,
+                             size_t out_stride) {
+    if (!g1_prepared_live(c, h)) return fail(c, BN_ERR_INVALID_ARGUMENT, "not a live prepared handle of this context");
+    if (out_stride == 0) return fail(c, BN_ERR_INVALID_ARGUMENT, "out_stride is 0");
+    if (m > kMsmMaxTerms) return fail(c, BN_ERR_INVALID_ARGUMENT, "more than 2^26 outputs");
+    if (m && (!k || !out)) return fail(c, BN_ERR_INVALID_ARGUMENT, "null buffer");
+    return BN_OK;
+}
+// the device sequence on stream s, in sets of kFixedSetLanes lanes: the lookups, the tree
+// over each output's lanes, the finish; the caller holds the lock and the workspace order
+static int msm_prepared_dev_impl(bn_ctx* c, const bn_g1_prepared* h, const bn_fr* d_k, size_t m, bn_g1* d_out,
+                                 size_t out_stride, hipStream_t s) {
+    MsmGroupWs<bn_g1>& g = c->msm_g1;
+    const uint32_t L = g.fixed_lanes ? (uint32_t)g.fixed_lanes : msm_fixed_auto_lanes(m, h->k, h->c);
+    const size_t set = std::max<size_t>(1, kFixedSetLanes / L);
+    RET_IF(grow_dev(c, &g.fixed, &g.fixed_cap, std::min(m, set) * L));
+    for (size_t off = 0; off < m; off += set) {
+        const size_t mc = std::min(m - off, set);
+        k_g1_msm_fixed<<<grid_for(mc * L), kBlock, 0, s>>>(h->table, h->zero, h->nent, (uint32_t)h->k, h->c,
+                                                           d_k + off * h->k, mc, L, g.fixed);
+        msm_tree(g.fixed, L, mc, s);
+        k_g1_msm_fixed_finish<<<grid_for(mc), kBlock, 0, s>>>(g.fixed, mc, d_out + off * out_stride, out_stride);
+    }
+    HIPCHK(c, hipGetLastError());
+    return BN_OK;
+}
+
 extern "C" {
+
+size_t bn_g1_prepared_table_bytes(size_t k, int cw) {
+    const uint64_t nent = (cw == 0 || msm_window_ok(cw)) ? msm_fixed_entries(k, cw) : 0;
+    return nent ? (size_t)(nent * 2 * sizeof(bn_fq) + k) : 0;
+}
+int bn_g1_bases_prepare(bn_ctx* c, const bn_g1* bases, size_t k, int cw, bn_g1_prepared** out) {
+    CTX_GUARD(c);
+    RET_IF(g1_prepare_args(c, bases, k, cw, out));
+    RET_IF(ws_acquire(c, c->stream));
+    WsUse use{c, c->stream};
+    return g1_prepare(c, bases, false, k, cw, out, c->stream);
+}
+int bn_g1_bases_prepare_dev(bn_ctx* c, const bn_g1* d_bases, size_t k, int cw, bn_g1_prepared** out, void* stream) {
+    CTX_GUARD(c);
+    RET_IF(g1_prepare_args(c, d_bases, k, cw, out));
+    const hipStream_t s = pick(c, stream);
+    RET_IF(ws_acquire(c, s));
+    WsUse use{c, s};
+    return g1_prepare(c, d_bases, true, k, cw, out, s);
+}
+size_t bn_g1_prepared_count(const bn_g1_prepared* h) { return h ? h->k : 0; }
+int bn_g1_prepared_window(const bn_g1_prepared* h) { return h ? h->c : 0; }
+int bn_g1_prepared_destroy(bn_ctx* c, bn_g1_prepared* h) {
+    CTX_GUARD(c);
+    if (!g1_prepared_live(c, h)) return fail(c, BN_ERR_INVALID_ARGUMENT, "not a live prepared handle of this context");
+    RET_IF(ws_drain(c));  // every call that reads the table has recorded ws_event behind its work
+    c->g1_prepared.erase(std::find(c->g1_prepared.begin(), c->g1_prepared.end(), h));
+    (void)hipFree(h->table);
+    (void)hipFree(h->zero);
+    delete h;
+    return BN_OK;
+}
+int bn_g1_msm_prepared_many(bn_ctx* c, const bn_g1_prepared* h, const bn_fr* k, size_t m, bn_g1* out, size_t out_stride) {
+    CTX_GUARD_HOST(c);
+    RET_IF(msm_prepared_args(c, h, k, m, out, out_stride));
+    if (m == 0) return BN_OK;
+    void* at[2];  // the sums, the scalars
+    RET_IF(stage_regions(c, {m * sizeof(bn_g1), m * h->k * sizeof(bn_fr)}, at));
+    HIPCHK(c, hipMemcpyAsync(at[1], k, m * h->k * sizeof(bn_fr), hipMemcpyHostToDevice, c->stream));
+    RET_IF(msm_prepared_dev_impl(c, h, (const bn_fr*)at[1], m, (bn_g1*)at[0], 1, c->stream));
+    HIPCHK(c, hipMemcpy2DAsync(out, out_stride * sizeof(bn_g1), at[0], sizeof(bn_g1), sizeof(bn_g1), m,
+                               hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return BN_OK;
+}
+int bn_g1_msm_prepared_many_dev(bn_ctx* c, const bn_g1_prepared* h, const bn_fr* d_k, size_t m, bn_g1* d_out,
+                                size_t out_stride, void* stream) {
+    CTX_GUARD(c);
+    RET_IF(msm_prepared_args(c, h, d_k, m, d_out, out_stride));
+    if (m == 0) return BN_OK;
+    hipStream_t s = pick(c, stream);
+    RET_IF(ws_acquire(c, s));
+    WsUse use{c, s};
+    return msm_prepared_dev_impl(c, h, d_k, m, d_out, out_stride, s);
+}
+int bn_set_msm_prepared_lanes(bn_ctx* c, int lanes) {
+    if (c && lanes != 0 && !msm_fixed_lanes_ok(lanes))
+        return fail(c, BN_ERR_INVALID_ARGUMENT, "lanes per output must be 0 (automatic) or a power of two from 1 to 64");
+    if (is_multi(c)) return for_each_sub(c, [&](bn_ctx* d) { return bn_set_msm_prepared_lanes(d, lanes); });
+    CTX_GUARD(c);
+    c->msm_g1.fixed_lanes = lanes;
+    return BN_OK;
+}
 
 int bn_internal_g1_msm_partial(bn_ctx* c, const bn_g1* p, const bn_fr* k, size_t n, bn_g1* out) {
     return msm_host(c, p, k, n, out, 0);

@@ -12,7 +12,8 @@
 
 // One group's settings and point buffers of the multi-scalar multiplication (P = bn_g1
 // or bn_g2): buckets the bucket sums, parts the segment and window partial sums, tmp
-// the small path's n products.
+// the small path's n products; fixed the lanes' partial sums of the prepared-bases MSM
+// (bn_g1_msm_prepared_many, G1 only so far).
 template <class P>
 struct MsmGroupWs {
     int window = 0;  // bits; 0: chosen from n (capi_msm.hip MsmGroup<P>::auto_window)
@@ -21,6 +22,9 @@ struct MsmGroupWs {
     P* parts = nullptr;
     P* tmp = nullptr;
     size_t buckets_cap = 0, parts_cap = 0, tmp_cap = 0;
+    int fixed_lanes = 0;  // lanes per output of the lookup kernel; 0: chosen from m and k (msm_fixed.h)
+    P* fixed = nullptr;
+    size_t fixed_cap = 0;
 };
 
 // bn_g2_prepare's handle: the 87 line coefficients of each of nq affine G2 points
@@ -31,6 +35,17 @@ struct bn_g2_prepared {
     size_t nq = 0;
     uint32_t* table = nullptr;
     uint8_t* zero = nullptr;  // zero[j] != 0: q[j] was G2::zero(), its table row is never used
+};
+
+// bn_g1_bases_prepare's handle: the window table of k G1 bases at width c (msm_fixed.h:
+// nent affine entries of two bn_fq each) and a zero flag per base, device-resident, owned
+// like a bn_g2_prepared by the single-device context whose `g1_prepared` list holds it.
+struct bn_g1_prepared {
+    size_t k = 0;
+    int c = 0;
+    uint32_t nent = 0;
+    bn_fq* table = nullptr;
+    uint8_t* zero = nullptr;  // zero[b] != 0: bases[b] had z == 0, its entries are never added
 };
 
 struct bn_ctx {
@@ -146,6 +161,8 @@ struct bn_ctx {
     // them order themselves through ws_event like every workspace user, which is what
     // bn_g2_prepared_destroy waits for.
     std::vector<bn_g2_prepared*> prepared;
+    // the same for the bn_g1_prepared handles (capi_msm.hip)
+    std::vector<bn_g1_prepared*> g1_prepared;
     // multi-device context (bn_ctx_create_multi): one single-device sub-context
     // per listed device; `device` is -1 and the fields above are unused
     std::vector<bn_ctx*> subs;

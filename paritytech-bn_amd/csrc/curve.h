@@ -178,6 +178,45 @@ BN_INLINE Jac<F> jac_add(const Jac<F>& s, const Jac<F>& o) {
     return jac_add(s, o, jac_is_zero(o));
 }
 
+// s + (ax, ay, one): jac_add_pre for an affine, nonzero second operand whose sign the caller
+// has applied to ay (msm_fixed.h adds table entries this way).  z2 = one drops the four
+// products by its powers and z3 = 2 z1 h: 8 products and 3 squarings.  The same point as
+// jac_add, not the same Jacobian image.  The shortcuts of jac_add: s zero gives the entry,
+// s equal to the entry goes to jac_double, and s equal to minus the entry has h == 0 with
+// s2 != s1, so z3 == 0: a zero point.
+template <template <int> class F, int BX, int BY>
+BN_INLINE Jac<F> jac_add_mixed(const Jac<F>& s, const F<BX>& ax, const F<BY>& ay) {
+    const bool s_zero = jac_is_zero(s);
+    auto z1_squared = F_sqr(s.z);
+    auto u2 = F_mul(ax, z1_squared);
+    auto z1_cubed = F_mul(s.z, z1_squared);
+    auto s2 = F_mul(ay, z1_cubed);
+    auto h = F_sub(u2, s.x);
+    auto s2_minus_s1 = F_sub(s2, s.y);
+    const bool h_zero = F_is_zero(h);
+    bool same = false;
+    if (BN_ANY(h_zero)) same = h_zero && F_is_zero(s2_minus_s1);  // rare: wave-uniform guard
+    auto i = F_sqr(F_add(h, h));
+    auto j = F_mul(h, i);
+    auto r = F_add(s2_minus_s1, s2_minus_s1);
+    auto v = F_mul(s.x, i);
+    auto s1_j = F_mul(s.y, j);
+    auto x3 = F_fold(F_sub(F_sub(F_sqr(r), j), F_add(v, v)));
+    auto y3 = F_sub(F_mul(r, F_sub(v, x3)), F_add(s1_j, s1_j));
+    auto z1_h = F_mul(s.z, h);
+    Jac<F> out = {narrow<kPt>(x3), narrow<kPt>(y3), narrow<kPt>(F_add(z1_h, z1_h))};
+    if (BN_ANY(same && !s_zero)) {  // rare: wave-uniform guard
+        const Jac<F> d = jac_double(s);
+        const bool take = same && !s_zero;
+        out = {F_select(take, d.x, out.x), F_select(take, d.y, out.y), F_select(take, d.z, out.z)};
+    }
+    if (BN_ANY(s_zero)) {
+        const Jac<F> e = {narrow<kPt>(ax), narrow<kPt>(ay), F_widen<kPt>(F_one<F>())};
+        out = {F_select(s_zero, e.x, out.x), F_select(s_zero, e.y, out.y), F_select(s_zero, e.z, out.z)};
+    }
+    return out;
+}
+
 // mod.rs:336-350 (zero unchanged, else (x, -y, z)), at the storage bound
 template <template <int> class F>
 BN_INLINE Jac<F> jac_neg(const Jac<F>& a) {

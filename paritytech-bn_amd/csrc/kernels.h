@@ -616,6 +616,12 @@ __global__ void __launch_bounds__(kBlock) k_msm_accumulate_g2(const bn_g2* __res
 __global__ void __launch_bounds__(kBlock) k_msm_reduce_g2(const bn_g2* __restrict__ buckets, int c, uint32_t nkeys, uint32_t nseg, bn_g2* __restrict__ parts);
 __global__ void __launch_bounds__(64) k_msm_horner_g2(const bn_g2* __restrict__ win, int c, int finish, bn_g2* __restrict__ out);
 __global__ void __launch_bounds__(64) k_msm_finish_g2(const bn_g2* in, bn_g2* out);
+// kernels_msm_fixed.hip (msm_fixed.h): MSMs over prepared bases.  table: nent entries of two
+// bn_fq (x, y); zero: one flag per base; parts: m * L points, lane major
+__global__ void __launch_bounds__(kBlock) k_g1_table_build(const bn_g1* __restrict__ bases, uint32_t k, int c, bn_fq* __restrict__ table, uint8_t* __restrict__ zero, uint32_t nent);
+__global__ void __launch_bounds__(kBlock) k_g1_msm_fixed(const bn_fq* __restrict__ table, const uint8_t* __restrict__ zero, uint32_t nent, uint32_t k, int c,
+                                                         const bn_fr* __restrict__ scalars, size_t m, uint32_t L, bn_g1* __restrict__ parts);
+__global__ void __launch_bounds__(kBlock) k_g1_msm_fixed_finish(const bn_g1* __restrict__ sums, size_t m, bn_g1* __restrict__ out, size_t stride);
 __global__ void __launch_bounds__(kPairBlock) k_gt_pow(const bn_gt* __restrict__ a, const bn_fr* __restrict__ k, size_t n,
                                                    bn_gt* __restrict__ out, uint32_t* __restrict__ ws);
 // kernels_codec.hip (codec.h): encodings, square roots, validation, decompression

@@ -24,7 +24,8 @@ multi-scalar multiplications g1_msm / g2_msm = sum of points[i] * scalars[i]) th
 the engine exists for, and pairings against fixed G2 points prepared once (G2Prepared,
 pairing_prepared_many, miller_loop_prepared_many: the reference's G2Precomp held on the
 device; pairing_batch_prepared_many: many products whose terms mix fresh and prepared
-points).  Values keep the reference's memory images (canonical
+points), and many small MSMs over fixed G1 bases prepared once (G1Prepared,
+g1_msm_prepared_many).  Values keep the reference's memory images (canonical
 Montgomery, little-endian u64 limbs), so a Gt compares equal exactly when the
 reference's derived PartialEq would.  Every computation runs on the GPU; there
 is no CPU fallback.
@@ -555,6 +556,81 @@ def pairing_batch_prepared_many(products, prepared):
     p = np.stack([a.img for a, _ in flat]) if flat else np.zeros((0, 12), np.uint64)
     q = np.stack([b.img for b in fresh]) if fresh else np.zeros((0, 24), np.uint64)
     return [Gt(row) for row in prepared._ctx.pairing_batch_prepared_many(p, q, h, qidx, offsets)]
+
+
+class G1Prepared:
+    """Window tables of fixed G1 bases held on the device (bn_g1_bases_prepare): what a
+    verifier builds once from its verifying key's IC points, or a committer from its basis,
+    and then runs many small MSMs over (g1_msm_prepared_many).  Built from a sequence of G1
+    (or a (k, 12) image array) of at least one base; zero bases are allowed.  `window` is
+    the table's width in bits, 2 .. 16 (0: the engine's default); len() is the number of
+    bases.  Release it with close(), a `with` block, or by dropping it; it belongs to the
+    engine context it was built on (the process-wide one unless `ctx` is given)."""
+
+    def __init__(self, bases, window=0, ctx=None):
+        self._h = None
+        b = _images(bases, 12)
+        if b.shape[0] < 1:
+            raise ValueError("G1Prepared takes at least one base")
+        if window != 0 and not 2 <= window <= 16:
+            raise ValueError("G1Prepared window must be 0 or 2 .. 16, not %r" % (window,))
+        self._ctx = ctx if ctx is not None else context()
+        self._n = b.shape[0]
+        self._h = self._ctx.g1_bases_prepare(b, window)
+        self.window = self._ctx.g1_prepared_window(self._h)
+
+    def __len__(self):
+        return self._n
+
+    @property
+    def closed(self):
+        return self._h is None
+
+    def _handle(self):
+        if self._h is None:
+            raise ValueError("this G1Prepared is closed")
+        return self._h
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        # (a context closed first has freed its handles itself)
+        if h is not None and getattr(self._ctx, "handle", None):
+            self._ctx.g1_prepared_destroy(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def g1_msm_prepared_many(prepared, rows):
+    """[sum_b prepared[b] * row[b] for row in rows] as normalized G1 in one engine call
+    (bn_g1_msm_prepared_many), each the same G1 as g1_msm over the bases and that row.  rows:
+    a sequence of sequences of Fr, one scalar per base, or an (m, k, 4) image array.  A row
+    whose length is not len(prepared) and a closed G1Prepared raise ValueError before any
+    device call; no rows give []."""
+    h = prepared._handle()
+    k = len(prepared)
+    if isinstance(rows, np.ndarray):
+        s = np.ascontiguousarray(rows, dtype=np.uint64)
+        if s.ndim != 3 or s.shape[1:] != (k, 4):
+            raise ValueError("g1_msm_prepared_many: scalars of shape %s are not rows of %d Fr" % (s.shape, k))
+    else:
+        rows = [list(r) for r in rows]
+        for r in rows:
+            if len(r) != k:
+                raise ValueError("g1_msm_prepared_many: a row of %d scalars for %d bases" % (len(r), k))
+        s = _images([x for r in rows for x in r], 4).reshape(len(rows), k, 4)
+    if s.shape[0] == 0:
+        return []
+    return [G1(row) for row in prepared._ctx.g1_msm_prepared_many(h, s)]
 
 
 def g2_affine_new_many(x, y):

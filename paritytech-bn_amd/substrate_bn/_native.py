@@ -39,6 +39,9 @@ EXPORTS = [
     "bn_set_latency_max", "bn_dev_status", "bn_set_fq12_op_unit",
     "bn_g1_msm", "bn_g1_msm_dev", "bn_set_msm_window", "bn_set_msm_min", "bn_msm_reserve",
     "bn_g2_msm", "bn_g2_msm_dev", "bn_g2_msm_reserve",
+    "bn_g1_prepared_table_bytes", "bn_g1_bases_prepare", "bn_g1_bases_prepare_dev", "bn_g1_prepared_count",
+    "bn_g1_prepared_window", "bn_g1_prepared_destroy", "bn_g1_msm_prepared_many", "bn_g1_msm_prepared_many_dev",
+    "bn_set_msm_prepared_lanes",
     "bn_pairing_batch_many", "bn_pairing_batch_many_dev", "bn_set_products_min", "bn_set_products_chunk",
     "bn_g2_prepare", "bn_g2_prepare_dev", "bn_g2_prepared_count", "bn_g2_prepared_destroy",
     "bn_pairing_prepared_many", "bn_pairing_prepared_many_dev", "bn_miller_loop_prepared_many",
@@ -135,6 +138,15 @@ def load():
         "bn_g2_msm": ([vp, vp, vp, sz, vp], i),
         "bn_g2_msm_dev": ([vp, vp, vp, sz, vp, vp], i),
         "bn_g2_msm_reserve": ([vp, sz], i),
+        "bn_g1_prepared_table_bytes": ([sz, i], sz),
+        "bn_g1_bases_prepare": ([vp, vp, sz, i, ctypes.POINTER(vp)], i),
+        "bn_g1_bases_prepare_dev": ([vp, vp, sz, i, ctypes.POINTER(vp), vp], i),
+        "bn_g1_prepared_count": ([vp], sz),
+        "bn_g1_prepared_window": ([vp], i),
+        "bn_g1_prepared_destroy": ([vp, vp], i),
+        "bn_g1_msm_prepared_many": ([vp, vp, vp, sz, vp, sz], i),
+        "bn_g1_msm_prepared_many_dev": ([vp, vp, vp, sz, vp, sz, vp], i),
+        "bn_set_msm_prepared_lanes": ([vp, i], i),
         "bn_pairing_batch_many": ([vp, vp, vp, vp, sz, vp], i),
         "bn_pairing_batch_many_dev": ([vp, vp, vp, vp, sz, vp, vp], i),
         "bn_set_products_min": ([vp, sz], i),
@@ -522,6 +534,61 @@ class Context:
         self._check(self._L.bn_g2_msm(self._h, _ptr(p), _ptr(k), n, _ptr(out)))
         return out
 
+    # ---- MSMs over prepared G1 bases (bn_g1_prepared)
+    def g1_bases_prepare(self, bases, c=0):
+        """bn_g1_bases_prepare: a handle (int) holding the window table of the rows of `bases`
+        at width c (0: the default) on the device; release it with g1_prepared_destroy
+        (substrate_bn.G1Prepared does)."""
+        b = _arr(bases, 12)
+        h = ctypes.c_void_p()
+        self._check(self._L.bn_g1_bases_prepare(self._h, _ptr(b), b.shape[0], c, ctypes.byref(h)))
+        return h.value
+
+    def g1_bases_prepare_dev(self, d_bases, k, c=0, stream=None):
+        h = ctypes.c_void_p()
+        self._check(self._L.bn_g1_bases_prepare_dev(self._h, d_bases, k, c, ctypes.byref(h), stream))
+        return h.value
+
+    def g1_prepared_count(self, handle):
+        return int(self._L.bn_g1_prepared_count(handle))
+
+    def g1_prepared_window(self, handle):
+        return int(self._L.bn_g1_prepared_window(handle))
+
+    def g1_prepared_destroy(self, handle):
+        self._check(self._L.bn_g1_prepared_destroy(self._h, handle))
+
+    def g1_msm_prepared_many(self, handle, scalars, out_stride=1):
+        """bn_g1_msm_prepared_many: scalars is an (m, k) matrix of Fr images -- (m, k, 4) words,
+        or (m, 4) when the handle has one base -- and row j of the (m, 12) result is the
+        normalized image of sum_b bases[b] * scalars[j, b].  With out_stride > 1 the result
+        is the (m * out_stride, 12) strided buffer itself: row j * out_stride holds output j and
+        the other rows stay zero.  A matrix whose width is not the handle's count and an
+        out_stride below 1 raise ValueError before any native call."""
+        k = self.g1_prepared_count(handle)
+        s = np.ascontiguousarray(scalars, dtype=np.uint64)
+        if out_stride < 1:
+            raise ValueError("out_stride must be at least 1, not %d" % out_stride)
+        if s.ndim == 3 and s.shape[1:] == (k, 4):
+            m = s.shape[0]
+        elif s.ndim == 2 and k == 1 and s.shape[1] == 4:
+            m = s.shape[0]
+        else:
+            raise ValueError("scalars of shape %s are not rows of %d Fr images" % (s.shape, k))
+        out = np.zeros((m * out_stride, 12), np.uint64)
+        self._check(self._L.bn_g1_msm_prepared_many(self._h, handle, _ptr(s), m, _ptr(out), out_stride))
+        return out
+
+    def g1_msm_prepared_many_dev(self, handle, d_k, m, d_out, out_stride=1, stream=None):
+        if out_stride < 1:
+            raise ValueError("out_stride must be at least 1, not %d" % out_stride)
+        self._check(self._L.bn_g1_msm_prepared_many_dev(self._h, handle, d_k, m, d_out, out_stride, stream))
+
+    def set_msm_prepared_lanes(self, lanes):
+        """Lanes per output of the prepared-bases lookup kernel: a power of two from 1 to 64;
+        0: chosen from m and k."""
+        self._check(self._L.bn_set_msm_prepared_lanes(self._h, lanes))
+
     def fq12_op_many(self, op, a, b=None):
         a = _arr(a, 48)
         bb = _arr(b, 48) if b is not None else None
@@ -718,3 +785,9 @@ class Context:
 
 def workspace_bytes(n):
     return load().bn_workspace_bytes(n)
+
+
+def g1_prepared_table_bytes(k, c=0):
+    """bn_g1_prepared_table_bytes: device bytes of the table of k bases at width c (0: the
+    default); 0 for arguments the prepare call refuses.  Host arithmetic, no device."""
+    return load().bn_g1_prepared_table_bytes(k, c)
