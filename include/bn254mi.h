@@ -349,6 +349,56 @@ int bn_g1_msm_prepared_many_dev(bn_ctx* ctx, const bn_g1_prepared* prepared, con
  * value. */
 int bn_set_msm_prepared_lanes(bn_ctx* ctx, int lanes);
 
+/* ---- many small G1 MSMs over FRESH bases in one call (shared doublings) ----
+ * The front half of a batch of PLONK / KZG verifications: one or two MSMs of 2 to about 30 terms
+ * per proof over the proof's own commitments, which differ in every proof, so no table can be
+ * prepared ahead.  One call computes m of them:
+ *   out[j * out_stride] = (sum over offsets[j] <= i < offsets[j+1] of p[i] * k[i]).normalize(), j < m,
+ * every output bit for bit the 96 bytes the single MSM returns on the same slice: (x, y, one), and
+ * (0, one, 0) for a zero sum or an empty segment.  The group law is exact and the normalized image
+ * unique: every setting below, and both paths, give the same bytes.
+ *   p[i] may be any Jacobian image (z != one; z == 0 with arbitrary x, y: such a term contributes
+ *   nothing), k[i] any Fr image, as for the single MSM.  offsets is HOST memory in both forms:
+ *   m + 1 entries, non-decreasing, offsets[0] == 0, n = offsets[m].  out_stride counts points and
+ *   must be >= 1; the points between the strided outputs are not written (stride 1 or 2 writes the
+ *   sums straight into the p array of bn_pairing_batch_prepared_many_dev).
+ *   Refused with BN_ERR_INVALID_ARGUMENT before any buffer is read, out untouched: malformed
+ *   offsets; a NULL offsets or out with m > 0; a NULL p or k with n > 0; out_stride == 0; n or m
+ *   above 2^26; a multi-device context (a device context from bn_ctx_device works).  m == 0 returns
+ *   BN_OK and touches nothing.  No outcome depends on the data: the _dev form has no status to report.
+ * Packed path (Straus): per launch set, one lane per term writes the term's signed c-bit digits (one
+ * byte each: c <= 8) and its 2^(c-1) Jacobian multiples; one lane per UNIT -- a contiguous run of at
+ * most T terms of one segment -- walks the windows from the top, doubling c times per window and adding
+ * one signed multiple per term, so the terms of a unit share the 254 doublings; one lane per segment
+ * adds its units' partial sums (at most 64) and normalizes.  A segment of more than 64 T terms takes
+ * units of ceil(len / 64) terms.  A segment longer than the max setting is not packed: it runs alone
+ * on the single MSM's path into its own output, on the same stream.
+ * The digits, multiples and partial sums of one launch set live in a workspace of their own, grown on
+ * first use or by bn_g1_msm_many_reserve, ordered like the shared one and not counted by
+ * bn_workspace_bytes.  The _dev form enqueues on `stream` without synchronizing; it reads offsets
+ * before it returns, may wait for the previous call's upload of its plan words (not for its
+ * kernels), and may allocate (and then waits for earlier work) on first use at a larger size. */
+int bn_g1_msm_many(bn_ctx* ctx, const bn_g1* p, const bn_fr* k, const size_t* offsets, size_t m, bn_g1* out,
+                   size_t out_stride);
+int bn_g1_msm_many_dev(bn_ctx* ctx, const bn_g1* d_p, const bn_fr* d_k, const size_t* offsets, size_t m,
+                       bn_g1* d_out, size_t out_stride, void* stream);
+/* the packed path's settings; each refuses a value outside its range with BN_ERR_INVALID_ARGUMENT and
+ * none changes a result.  window: c, 2 .. 8, 0 = default (4).  unit: T, 1 .. 64, 0 = chosen per launch
+ * set (the smallest that keeps the set at 2^16 lanes, at most 16: T = 1 up to 2^16 terms).  max:
+ * segments of more terms run alone; at most 4096, 0 = default (1024, except that a call with 16 or more
+ * such segments packs those of up to 4096 terms too: together they fill the card, while a few of them
+ * run faster alone).  chunk: the most terms of a launch
+ * set (sets are cut at segment boundaries; a single segment may exceed it), at most 2^26; 0 = default
+ * (2^20, and at most 1 GiB of digits and multiples, so windows above 4 shrink the set; a set of 2^20
+ * terms at c = 4 holds 832 MiB of them, allocated only by calls of that size). */
+int bn_set_msm_many_window(bn_ctx* ctx, int c);
+int bn_set_msm_many_unit(bn_ctx* ctx, int terms);
+int bn_set_msm_many_max(bn_ctx* ctx, size_t terms);
+int bn_set_msm_many_chunk(bn_ctx* ctx, size_t terms);
+/* pre-size that workspace for calls of up to `terms` terms in up to `segments` segments at the current
+ * settings (else grown on first use) */
+int bn_g1_msm_many_reserve(bn_ctx* ctx, size_t terms, size_t segments);
+
 /* ---- G2 multi-scalar multiplication (bucket method on the two-lane layout) ---- */
 
 /* The same contract over G2: *out = (sum over i < n of p[i] * k[i]).normalize(), the image (x, y, one)

@@ -936,6 +936,10 @@ static void ctx_teardown(bn_ctx* c) {
     if (c->prod_map_h) (void)hipHostFree(c->prod_map_h);
     if (c->prod_map_d) (void)hipFree(c->prod_map_d);
     if (c->prod_fresh) (void)hipFree(c->prod_fresh);
+    if (c->many_words_event) (void)hipEventDestroy(c->many_words_event);
+    if (c->many_words_h) (void)hipHostFree(c->many_words_h);
+    for (void* p : {(void*)c->many_words_d, (void*)c->many_digits, (void*)c->many_table, (void*)c->many_parts})
+        if (p) (void)hipFree(p);
     for (hipEvent_t e : {c->ev_in[0], c->ev_in[1], c->ev_comp[0], c->ev_comp[1], c->ev_out[0], c->ev_out[1]})
         if (e) (void)hipEventDestroy(e);
     if (c->pin) (void)hipHostFree(c->pin);

@@ -3,11 +3,14 @@
 // and the small path return the same image: the group law is exact and the result is
 // normalized.  The host sequence is one template over the point type; MsmGroup<P>
 // names the group's kernels, settings and buffers.  Behind it, the bn_g1_prepared handles
-// and bn_g1_msm_prepared_many (kernels_msm_fixed.hip; §8c).
+// and bn_g1_msm_prepared_many (kernels_msm_fixed.hip; §8c), and bn_g1_msm_many
+// (kernels_msm_many.hip, msm_many_plan.h; §8d).
 #include <type_traits>
 
 #include "capi_internal.h"
 #include "msm_fixed.h"
+#include "msm_many.h"
+#include "msm_many_plan.h"
 
 using namespace bn;
 
@@ -298,6 +301,100 @@ static int msm_prepared_dev_impl(bn_ctx* c, const bn_g1_prepared* h, const bn_fr
     return BN_OK;
 }
 
+// ---------------------------------------------------------------- many MSMs over fresh bases
+// The settings a 0 stands for, read off profiles/msm_many_sweep.jsonl: width
+// 4; the automatic T of a launch set is the smallest that keeps the set at 2^16 lanes (one
+// wave on every SIMD: below that the card idles, above it a shorter chain gains less than the
+// shared doublings), at most 16; a set takes at most 2^20 terms, and at most 1 GiB of digits
+// and multiples, so windows above 4 shrink it (a forced chunk is taken as it is); segments
+// above 1,024 terms run alone on bn_g1_msm's path (1.9 ms each) unless the call has 16 or more
+// of them, which together fill the card on the packed path (a forced max always holds).
+constexpr int kManyWindow = 4;
+constexpr size_t kManyLanes = size_t(1) << 16;
+constexpr uint32_t kManyUnitAutoMax = 16;
+constexpr size_t kManySetTerms = size_t(1) << 20;
+constexpr size_t kManySetBytes = size_t(1) << 30;
+constexpr size_t kManyMaxDefault = 1024;
+constexpr size_t kManyPackLongFrom = 16;
+
+static int many_window(const bn_ctx* c) { return c->many_window ? c->many_window : kManyWindow; }
+static MsmManyLimits many_limits(const bn_ctx* c) {
+    const int cw = many_window(c);
+    const size_t per_term = (sizeof(bn_g1) << (cw - 1)) + (size_t)msm_windows(cw);
+    const size_t chunk = c->many_chunk ? c->many_chunk : std::min(kManySetTerms, kManySetBytes / per_term);
+    return {(uint32_t)c->many_unit, c->many_max ? c->many_max : kManyMaxDefault, chunk, kManyLanes, kManyUnitAutoMax,
+            c->many_max ? SIZE_MAX : kManyPackLongFrom};
+}
+// the buffers of a launch set of up to nt terms and nu units at the context's width, and
+// the words of a call
+static int many_grow(bn_ctx* c, size_t nt, size_t nu, size_t words) {
+    const int cw = many_window(c);
+    RET_IF(grow_dev(c, &c->many_digits, &c->many_digits_cap, (size_t)msm_many_digits(nt, cw)));
+    RET_IF(grow_dev(c, &c->many_table, &c->many_table_cap, (size_t)msm_many_entries(nt, cw)));
+    RET_IF(grow_dev(c, &c->many_parts, &c->many_parts_cap, nu));
+    if (words && c->many_words_pending) {  // the pinned source may be replaced
+        HIPCHK(c, hipEventSynchronize(c->many_words_event));
+        c->many_words_pending = false;
+    }
+    return grow_pinned_pair(c, &c->many_words_h, &c->many_words_d, &c->many_words_cap, words);
+}
+// Refusals, before any point buffer is read (offsets is the host's control array).  m is
+// not 0.
+static int many_args(bn_ctx* c, const void* p, const void* k, const size_t* off, size_t m, const void* out) {
+    if (const char* why = msm_many_offsets_refusal(off, m)) return fail(c, BN_ERR_INVALID_ARGUMENT, why);
+    if (!out || (off[m] && (!p || !k))) return fail(c, BN_ERR_INVALID_ARGUMENT, "null buffer");
+    return BN_OK;
+}
+// The words of every launch set of the call -> many_words_d in one copy on s in front of the
+// call's kernels.  The pinned source is rewritten by the next call, which first waits for
+// this copy (not for the kernels behind it).
+static int many_upload(bn_ctx* c, const MsmManyPlan& plan, const size_t* off, hipStream_t s) {
+    if (!plan.words) return BN_OK;
+    if (!c->many_words_event) HIPCHK(c, hipEventCreateWithFlags(&c->many_words_event, hipEventDisableTiming));
+    if (c->many_words_pending) {
+        HIPCHK(c, hipEventSynchronize(c->many_words_event));
+        c->many_words_pending = false;
+    }
+    msm_many_fill(plan, off, c->many_words_h);
+    HIPCHK(c, hipMemcpyAsync(c->many_words_d, c->many_words_h, plan.words * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipEventRecord(c->many_words_event, s));
+    c->many_words_pending = true;
+    return BN_OK;
+}
+// the device sequence on stream s: every packed item as one launch set through the shared
+// buffers, every other segment through bn_g1_msm's path into its own output; the caller holds
+// the lock and the workspace order
+static int many_dev_impl(bn_ctx* c, const bn_g1* d_p, const bn_fr* d_k, const size_t* off, size_t m, bn_g1* d_out,
+                         size_t out_stride, hipStream_t s) {
+    const int cw = many_window(c);
+    const MsmManyPlan plan = msm_many_plan(many_limits(c), off, m);
+    if (plan.set_terms > 0xffffffffull || plan.set_units > 0xffffffffull)
+        return fail(c, BN_ERR_INTERNAL, "launch set exceeds its 32-bit offsets");
+    if (!c->many_words_event) HIPCHK(c, hipEventCreateWithFlags(&c->many_words_event, hipEventDisableTiming));
+    RET_IF(many_grow(c, plan.set_terms, plan.set_units, plan.words));
+    RET_IF(many_upload(c, plan, off, s));
+    for (const MsmManyItem& it : plan.items) {
+        const size_t lo = off[it.j0], nt = off[it.j1] - lo, mc = it.j1 - it.j0;
+        if (!it.packed) {
+            RET_IF(msm_dev_impl(c, d_p + lo, d_k + lo, nt, d_out + it.j0 * out_stride, s, 1));
+            continue;
+        }
+        if (nt > c->many_table_cap >> (cw - 1) || it.units > c->many_parts_cap)
+            return fail(c, BN_ERR_INTERNAL, "launch set exceeds the workspace");
+        const uint32_t* unit_off = c->many_words_d + it.words_at;
+        if (nt) {
+            k_g1_msm_many_table<<<grid_for(nt), kBlock, 0, s>>>(d_p + lo, d_k + lo, (uint32_t)nt, cw, c->many_digits,
+                                                                c->many_table);
+            k_g1_msm_many_unit<<<grid_for(it.units), kBlock, 0, s>>>(c->many_digits, c->many_table, (uint32_t)nt, cw,
+                                                                     unit_off, (uint32_t)it.units, c->many_parts);
+        }
+        k_g1_msm_many_finish<<<grid_for(mc), kBlock, 0, s>>>(c->many_parts, (uint32_t)it.units, unit_off + it.units + 1,
+                                                             mc, d_out + it.j0 * out_stride, out_stride);
+        HIPCHK(c, hipGetLastError());
+    }
+    return BN_OK;
+}
+
 extern "C" {
 
 size_t bn_g1_prepared_table_bytes(size_t k, int cw) {
@@ -353,6 +450,81 @@ int bn_g1_msm_prepared_many_dev(bn_ctx* c, const bn_g1_prepared* h, const bn_fr*
     RET_IF(ws_acquire(c, s));
     WsUse use{c, s};
     return msm_prepared_dev_impl(c, h, d_k, m, d_out, out_stride, s);
+}
+int bn_g1_msm_many(bn_ctx* c, const bn_g1* p, const bn_fr* k, const size_t* offsets, size_t m, bn_g1* out,
+                   size_t out_stride) {
+    CTX_GUARD_HOST(c);
+    if (out_stride == 0) return fail(c, BN_ERR_INVALID_ARGUMENT, "out_stride is 0");
+    if (m == 0) return BN_OK;
+    RET_IF(many_args(c, p, k, offsets, m, out));
+    const size_t n = offsets[m];
+    void* at[3];  // the sums, the points, the scalars
+    RET_IF(stage_regions(c, {m * sizeof(bn_g1), n * sizeof(bn_g1), n * sizeof(bn_fr)}, at));
+    int rc = [&]() -> int {
+        if (n) {
+            HIPCHK(c, hipMemcpyAsync(at[1], p, n * sizeof(bn_g1), hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(at[2], k, n * sizeof(bn_fr), hipMemcpyHostToDevice, c->stream));
+        }
+        RET_IF(many_dev_impl(c, (const bn_g1*)at[1], (const bn_fr*)at[2], offsets, m, (bn_g1*)at[0], 1, c->stream));
+        HIPCHK(c, hipMemcpy2DAsync(out, out_stride * sizeof(bn_g1), at[0], sizeof(bn_g1), sizeof(bn_g1), m,
+                                   hipMemcpyDeviceToHost, c->stream));
+        return BN_OK;
+    }();
+    if (hipStreamSynchronize(c->stream) != hipSuccess && rc == BN_OK) rc = fail(c, BN_ERR_HIP, "hipStreamSynchronize");
+    return rc;
+}
+int bn_g1_msm_many_dev(bn_ctx* c, const bn_g1* d_p, const bn_fr* d_k, const size_t* offsets, size_t m, bn_g1* d_out,
+                       size_t out_stride, void* stream) {
+    CTX_GUARD(c);
+    if (out_stride == 0) return fail(c, BN_ERR_INVALID_ARGUMENT, "out_stride is 0");
+    if (m == 0) return BN_OK;
+    RET_IF(many_args(c, d_p, d_k, offsets, m, d_out));
+    hipStream_t s = pick(c, stream);
+    RET_IF(ws_acquire(c, s));
+    WsUse use{c, s};
+    return many_dev_impl(c, d_p, d_k, offsets, m, d_out, out_stride, s);
+}
+int bn_set_msm_many_window(bn_ctx* c, int bits) {
+    if (c && bits != 0 && !msm_many_window_ok(bits))
+        return fail(c, BN_ERR_INVALID_ARGUMENT, "window width outside 2 .. 8 (0: default)");
+    if (is_multi(c)) return for_each_sub(c, [&](bn_ctx* d) { return bn_set_msm_many_window(d, bits); });
+    CTX_GUARD(c);
+    c->many_window = bits;
+    return BN_OK;
+}
+int bn_set_msm_many_unit(bn_ctx* c, int terms) {
+    if (c && (terms < 0 || terms > (int)kMsmManyMaxUnitTerms))
+        return fail(c, BN_ERR_INVALID_ARGUMENT, "terms per unit outside 1 .. 64 (0: automatic)");
+    if (is_multi(c)) return for_each_sub(c, [&](bn_ctx* d) { return bn_set_msm_many_unit(d, terms); });
+    CTX_GUARD(c);
+    c->many_unit = terms;
+    return BN_OK;
+}
+int bn_set_msm_many_max(bn_ctx* c, size_t terms) {
+    if (c && terms > kMsmManyMaxSegment)
+        return fail(c, BN_ERR_INVALID_ARGUMENT, "at most 4096 terms per packed segment (0: default)");
+    if (is_multi(c)) return for_each_sub(c, [&](bn_ctx* d) { return bn_set_msm_many_max(d, terms); });
+    CTX_GUARD(c);
+    c->many_max = terms;
+    return BN_OK;
+}
+int bn_set_msm_many_chunk(bn_ctx* c, size_t terms) {
+    if (c && terms > kMsmManyMaxTerms)
+        return fail(c, BN_ERR_INVALID_ARGUMENT, "at most 2^26 terms per launch set (0: default)");
+    if (is_multi(c)) return for_each_sub(c, [&](bn_ctx* d) { return bn_set_msm_many_chunk(d, terms); });
+    CTX_GUARD(c);
+    c->many_chunk = terms;
+    return BN_OK;
+}
+int bn_g1_msm_many_reserve(bn_ctx* c, size_t terms, size_t segments) {
+    CTX_GUARD(c);
+    if (terms > kMsmManyMaxTerms || segments > kMsmManyMaxTerms)
+        return fail(c, BN_ERR_INVALID_ARGUMENT, "more than 2^26 terms or segments");
+    // a set holds at most the chunk's terms, or one segment of at most `max`; a unit has at
+    // least one term; a call's words are its units, its segments and two per set
+    const MsmManyLimits lim = many_limits(c);
+    const size_t st = std::min(terms, std::max(lim.chunk, kMsmManyMaxSegment));
+    return many_grow(c, st, st, terms + 3 * segments + 2);
 }
 int bn_set_msm_prepared_lanes(bn_ctx* c, int lanes) {
     if (c && lanes != 0 && !msm_fixed_lanes_ok(lanes))

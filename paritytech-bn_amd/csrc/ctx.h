@@ -163,6 +163,24 @@ struct bn_ctx {
     std::vector<bn_g2_prepared*> prepared;
     // the same for the bn_g1_prepared handles (capi_msm.hip)
     std::vector<bn_g1_prepared*> g1_prepared;
+    // bn_g1_msm_many (capi_msm.hip, kernels_msm_many.hip).  Settings: 0 takes
+    // the default (capi_msm.hip).  Its workspace is its own, like the MSM's: the digit bytes,
+    // the multiples and the units' partial sums of one launch set, grown on first use or by
+    // bn_g1_msm_many_reserve and ordered by ws_event; and the plan's words of every set of a
+    // call (msm_many_plan.h), which go up through many_words_h (pinned) in one upload in front
+    // of the call's kernels -- many_words_event marks that upload done, and the next call
+    // waits for it before it rewrites many_words_h.
+    int many_window = 0, many_unit = 0;
+    size_t many_max = 0, many_chunk = 0;
+    uint8_t* many_digits = nullptr;
+    bn_g1* many_table = nullptr;
+    bn_g1* many_parts = nullptr;
+    size_t many_digits_cap = 0, many_table_cap = 0, many_parts_cap = 0;
+    uint32_t* many_words_h = nullptr;
+    uint32_t* many_words_d = nullptr;
+    size_t many_words_cap = 0;  // words
+    hipEvent_t many_words_event = nullptr;  // created on first use
+    bool many_words_pending = false;
     // multi-device context (bn_ctx_create_multi): one single-device sub-context
     // per listed device; `device` is -1 and the fields above are unused
     std::vector<bn_ctx*> subs;

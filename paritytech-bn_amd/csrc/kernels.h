@@ -622,6 +622,14 @@ __global__ void __launch_bounds__(kBlock) k_g1_table_build(const bn_g1* __restri
 __global__ void __launch_bounds__(kBlock) k_g1_msm_fixed(const bn_fq* __restrict__ table, const uint8_t* __restrict__ zero, uint32_t nent, uint32_t k, int c,
                                                          const bn_fr* __restrict__ scalars, size_t m, uint32_t L, bn_g1* __restrict__ parts);
 __global__ void __launch_bounds__(kBlock) k_g1_msm_fixed_finish(const bn_g1* __restrict__ sums, size_t m, bn_g1* __restrict__ out, size_t stride);
+// kernels_msm_many.hip (msm_many.h): many small MSMs over fresh bases.  Per launch set of nt terms:
+// digits W(c) * nt bytes, table nt << (c - 1) points, parts one point per unit
+__global__ void __launch_bounds__(kBlock) k_g1_msm_many_table(const bn_g1* __restrict__ p, const bn_fr* __restrict__ k, uint32_t nt, int c, uint8_t* __restrict__ digits,
+                                                              bn_g1* __restrict__ table);
+__global__ void __launch_bounds__(kBlock) k_g1_msm_many_unit(const uint8_t* __restrict__ digits, const bn_g1* __restrict__ table, uint32_t nt, int c,
+                                                             const uint32_t* __restrict__ unit_off, uint32_t nunits, bn_g1* __restrict__ parts);
+__global__ void __launch_bounds__(kBlock) k_g1_msm_many_finish(const bn_g1* __restrict__ parts, uint32_t nunits, const uint32_t* __restrict__ seg_unit, size_t m,
+                                                               bn_g1* __restrict__ out, size_t stride);
 __global__ void __launch_bounds__(kPairBlock) k_gt_pow(const bn_gt* __restrict__ a, const bn_fr* __restrict__ k, size_t n,
                                                    bn_gt* __restrict__ out, uint32_t* __restrict__ ws);
 // kernels_codec.hip (codec.h): encodings, square roots, validation, decompression

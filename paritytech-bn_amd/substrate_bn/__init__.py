@@ -442,6 +442,27 @@ def g1_msm(points, scalars):
     return G1(context().g1_msm(p, k))
 
 
+def g1_msm_many(msms, ctx=None):
+    """[g1_msm(points, scalars) for points, scalars in msms] in one engine call
+    (bn_g1_msm_many): many small MSMs over fresh bases, as a batch of PLONK / KZG verifiers
+    computes them.  msms: a sequence of (points, scalars), each as g1_msm takes them; an MSM
+    of no terms gives G1.zero(); different lengths in one of them raise ValueError before any
+    device call; no MSMs give [] without one."""
+    parts = []
+    for points, scalars in msms:
+        p, k = _images(points, 12), _images(scalars, 4)
+        if p.shape[0] != k.shape[0]:
+            raise ValueError("g1_msm_many: %d points and %d scalars in MSM %d" % (p.shape[0], k.shape[0], len(parts)))
+        parts.append((p, k))
+    if not parts:
+        return []
+    offsets = np.zeros(len(parts) + 1, np.uintp)
+    offsets[1:] = np.cumsum([p.shape[0] for p, _ in parts])
+    p = np.concatenate([p for p, _ in parts])
+    k = np.concatenate([k for _, k in parts])
+    return [G1(row) for row in (ctx or context()).g1_msm_many(p, k, offsets)]
+
+
 def g2_msm(points, scalars):
     """sum of points[i] * scalars[i] as a normalized G2 (bn_g2_msm).  Takes sequences of
     G2 / Fr or the (n, 24) / (n, 4) image arrays; no terms give G2.zero() without a

@@ -42,6 +42,8 @@ EXPORTS = [
     "bn_g1_prepared_table_bytes", "bn_g1_bases_prepare", "bn_g1_bases_prepare_dev", "bn_g1_prepared_count",
     "bn_g1_prepared_window", "bn_g1_prepared_destroy", "bn_g1_msm_prepared_many", "bn_g1_msm_prepared_many_dev",
     "bn_set_msm_prepared_lanes",
+    "bn_g1_msm_many", "bn_g1_msm_many_dev", "bn_set_msm_many_window", "bn_set_msm_many_unit", "bn_set_msm_many_max",
+    "bn_set_msm_many_chunk", "bn_g1_msm_many_reserve",
     "bn_pairing_batch_many", "bn_pairing_batch_many_dev", "bn_set_products_min", "bn_set_products_chunk",
     "bn_g2_prepare", "bn_g2_prepare_dev", "bn_g2_prepared_count", "bn_g2_prepared_destroy",
     "bn_pairing_prepared_many", "bn_pairing_prepared_many_dev", "bn_miller_loop_prepared_many",
@@ -147,6 +149,13 @@ def load():
         "bn_g1_msm_prepared_many": ([vp, vp, vp, sz, vp, sz], i),
         "bn_g1_msm_prepared_many_dev": ([vp, vp, vp, sz, vp, sz, vp], i),
         "bn_set_msm_prepared_lanes": ([vp, i], i),
+        "bn_g1_msm_many": ([vp, vp, vp, vp, sz, vp, sz], i),
+        "bn_g1_msm_many_dev": ([vp, vp, vp, vp, sz, vp, sz, vp], i),
+        "bn_set_msm_many_window": ([vp, i], i),
+        "bn_set_msm_many_unit": ([vp, i], i),
+        "bn_set_msm_many_max": ([vp, sz], i),
+        "bn_set_msm_many_chunk": ([vp, sz], i),
+        "bn_g1_msm_many_reserve": ([vp, sz, sz], i),
         "bn_pairing_batch_many": ([vp, vp, vp, vp, sz, vp], i),
         "bn_pairing_batch_many_dev": ([vp, vp, vp, vp, sz, vp, vp], i),
         "bn_set_products_min": ([vp, sz], i),
@@ -588,6 +597,55 @@ class Context:
         """Lanes per output of the prepared-bases lookup kernel: a power of two from 1 to 64;
         0: chosen from m and k."""
         self._check(self._L.bn_set_msm_prepared_lanes(self._h, lanes))
+
+    # ---- many small MSMs over fresh bases (bn_g1_msm_many)
+    def g1_msm_many(self, p, k, offsets, out_stride=1):
+        """bn_g1_msm_many: row j of the (m, 12) result is the normalized image of the sum of
+        p[i] * k[i] over offsets[j] <= i < offsets[j + 1] (G1::zero() for an empty segment or a
+        zero sum).  With out_stride > 1 the result is the (m * out_stride, 12) strided buffer
+        itself: row j * out_stride holds output j and the other rows stay zero.  Malformed
+        offsets, offsets that do not end at the row count, p and k of different lengths and an
+        out_stride below 1 raise ValueError before any native call."""
+        p, k = _arr(p, 12), _arr(k, 4)
+        n = _same_rows(p, k)
+        if out_stride < 1:
+            raise ValueError("out_stride must be at least 1, not %d" % out_stride)
+        off = _offsets(offsets, n)
+        m = off.shape[0] - 1
+        out = np.zeros((m * out_stride, 12), np.uint64)
+        if m == 0:
+            return out
+        self._check(self._L.bn_g1_msm_many(self._h, _ptr(p) if n else None, _ptr(k) if n else None, _ptr(off), m,
+                                           _ptr(out), out_stride))
+        return out
+
+    def g1_msm_many_dev(self, d_p, d_k, offsets, d_out, out_stride=1, stream=None):
+        """bn_g1_msm_many_dev: d_p, d_k and d_out are device addresses; offsets stays on the host
+        and is checked as in g1_msm_many.  Nothing is reported: no outcome depends on the data."""
+        if out_stride < 1:
+            raise ValueError("out_stride must be at least 1, not %d" % out_stride)
+        off = _offsets(offsets)
+        self._check(self._L.bn_g1_msm_many_dev(self._h, d_p, d_k, _ptr(off), off.shape[0] - 1, d_out, out_stride,
+                                               stream))
+
+    def set_msm_many_window(self, c):
+        """Window width of bn_g1_msm_many's packed path: 2 .. 8; 0: the default."""
+        self._check(self._L.bn_set_msm_many_window(self._h, c))
+
+    def set_msm_many_unit(self, terms):
+        """Terms per unit (one lane's shared doublings): 1 .. 64; 0: chosen per launch set."""
+        self._check(self._L.bn_set_msm_many_unit(self._h, terms))
+
+    def set_msm_many_max(self, terms):
+        """Segments of more terms run alone on g1_msm's path: at most 4096; 0: the default."""
+        self._check(self._L.bn_set_msm_many_max(self._h, terms))
+
+    def set_msm_many_chunk(self, terms):
+        """The most terms of a launch set of the packed path; 0: the default."""
+        self._check(self._L.bn_set_msm_many_chunk(self._h, terms))
+
+    def g1_msm_many_reserve(self, terms, segments):
+        self._check(self._L.bn_g1_msm_many_reserve(self._h, terms, segments))
 
     def fq12_op_many(self, op, a, b=None):
         a = _arr(a, 48)
