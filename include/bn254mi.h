@@ -264,7 +264,9 @@ int bn_pairing_batch_prepared_many_dev(bn_ctx* ctx, const bn_g1* d_p, const bn_g
 /* ---- group path (src/groups/mod.rs:250-334, lib.rs:425-431) ---- */
 
 /* out[i] = p[i] * k[i]: the reference's double-and-add chain (mod.rs:272-292), so the
- * Jacobian output is bit-identical, not merely an equal point. */
+ * Jacobian output is bit-identical, not merely an equal point -- also where the chain meets
+ * res == zero, res == p or res == -p on its way, and for a zero image p (z == 0 under any x, y;
+ * see the group law section below). */
 int bn_g1_mul_many(bn_ctx* ctx, const bn_g1* p, const bn_fr* k, size_t n, bn_g1* out);
 int bn_g1_mul_many_dev(bn_ctx* ctx, const bn_g1* d_p, const bn_fr* d_k, size_t n, bn_g1* d_out, void* stream);
 int bn_g2_mul_many(bn_ctx* ctx, const bn_g2* p, const bn_fr* k, size_t n, bn_g2* out);
@@ -422,7 +424,19 @@ int bn_g2_msm_reserve(bn_ctx* ctx, size_t n);
  *   neg        out = -a         (mod.rs:336-350: zero unchanged, else (x, -y, z))
  *   normalize  out = a.normalize() (lib.rs:391-398: to_affine then to_jacobian, z = one,
  *              mod.rs:199-226; zero unchanged)
- *   eq         eq[i] = (a == b) (PartialEq, mod.rs:169-195: projective equality) as 0 / 1 */
+ *   eq         eq[i] = (a == b) (PartialEq, mod.rs:169-195: projective equality) as 0 / 1
+ * A zero point is any image with z == 0, whatever its x, y (mod.rs:246-248; G::new takes any x, y, z):
+ * every entry point of this header accepts such an image, and every returned image is the
+ * reference's.  zero + b is b's own image, a + zero is a's, and zero + zero the second operand's;
+ * neg and normalize leave a zero image as it is; eq looks only at z when either side is zero.
+ * double() has no zero check, so a zero image keeps its z == 0 while its x, y go on through the
+ * doubling formulas: p * k for a zero image p is p doubled once per trailing zero bit of k (and
+ * (0, one, 0) for k == 0).  The pairing entry points skip a pair with a zero image on either side,
+ * or return BN_ERR_TO_AFFINE where the reference fails (bn_miller_loop_batch,
+ * bn_g2_precompute_many); a prepared zero q[j] sets that point's zero flag.  The chains take the
+ * doubling branch and the h == 0 branch (z3 == 0) wherever the data leads them, also mid-chain:
+ * on-curve G2 images outside the order-r subgroup (small-order twist points) are multiplied and
+ * summed exactly as the reference does. */
 int bn_g1_add_many(bn_ctx* ctx, const bn_g1* a, const bn_g1* b, size_t n, bn_g1* out);
 int bn_g1_sub_many(bn_ctx* ctx, const bn_g1* a, const bn_g1* b, size_t n, bn_g1* out);
 int bn_g1_neg_many(bn_ctx* ctx, const bn_g1* a, size_t n, bn_g1* out);

@@ -259,9 +259,10 @@ def gcd_points(point_index=3):
 
 
 def zero_point(width):
-    """(0, 1, 0): G1::zero() for width 12, G2::zero() for 24.  A zero z under nonzero
-    x, y is not generated: no existing GPU test feeds one in (tests/test_gpu_group.py
-    plants (0, 1, 0) only), so no entry point is shown to define its outcome."""
+    """(0, 1, 0): G1::zero() for width 12, G2::zero() for 24.  A zero z under other x, y is
+    just as much a zero point to the reference (mod.rs:246-248), which defines the outcome
+    of every operation on it; tests/group_exceptional_cases.py:zero_images generates those
+    and tests/test_gpu_group_exceptional.py feeds them to every entry point."""
     z = np.zeros(width, np.uint64)
     z[width // 3:width // 3 + 4] = O.canon_to_mont_array([1]).reshape(4)
     return z

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as O
+from tests.group_exceptional_cases import random_twist_points
 
 KATS = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "reference_kats.json")))
 P, R = O.P, O.R
@@ -132,26 +133,6 @@ def test_g2_from_compressed_kat_and_errors():
     assert st_b == O.OK and canon(neg) == [int(v) for v in k["x"] + k["y"]] + [1, 0]
     assert O.g2_from_compressed_one(bytes.fromhex(k["bytes_0c_invalid"]))[1] == O.CURVE_INVALID_ENCODING
     assert O.g2_from_compressed_one(bytes.fromhex(k["bytes_0a"])[:-1])[1] == O.CURVE_INVALID_ENCODING
-
-
-def random_twist_points(n, seed):
-    """(x, y) on E'(Fq2) but (almost surely) outside the order-r subgroup."""
-    rng = np.random.default_rng(seed)
-    xs, ys = [], []
-    # b' of the twist from the generator: y^2 - x^3 (groups/mod.rs:452-467)
-    g = O.g2_one()
-    gy2 = O.binary("orc_fq2_mul", g[8:16], g[8:16], 8, 8, 8)
-    gx3 = O.binary("orc_fq2_mul", O.binary("orc_fq2_mul", g[:8], g[:8], 8, 8, 8), g[:8], 8, 8, 8)
-    b = [(u - v) % P for u, v in zip(canon(gy2), canon(gx3))]
-    while len(xs) < n:
-        x = mont([int.from_bytes(rng.bytes(32), "big") % P for _ in range(2)])
-        x3 = O.binary("orc_fq2_mul", O.binary("orc_fq2_mul", x, x, 8, 8, 8), x, 8, 8, 8)
-        rhs = [(u + v) % P for u, v in zip(canon(x3), b)]
-        y, ok = O.fq2_sqrt(mont(rhs))
-        if ok[0]:
-            xs.append(x.reshape(8))
-            ys.append(y.reshape(8))
-    return np.stack(xs), np.stack(ys)
 
 
 def test_affine_new_subgroup_and_curve_checks():
