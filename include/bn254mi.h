@@ -293,6 +293,32 @@ int bn_set_msm_window(bn_ctx* ctx, int c);
  * kernels + an addition tree); 0 sends every n >= 1 down the bucket path.  Default: each group's own
  * measured crossover, or $BN254MI_MSM_MIN for both.  Results are identical on either path. */
 int bn_set_msm_min(bn_ctx* ctx, size_t n);
+/* The run cap L of the bucket path of both groups.  A (window, bucket) key that more than L terms
+ * fall into -- many equal scalars, a witness of zeros and ones -- is not summed by one lane as one
+ * chain of dependent additions: its run is cut into chunks of at most L entries, one lane each, and
+ * the chunk sums are folded by a tree of fan-in 32, so no bucket costs more than
+ * L + 32 * ceil(log32(ceil(n / L))) dependent additions.  All of it is enqueued from n, the window
+ * and this setting alone: no readback, no synchronization, the _dev forms still only enqueue.
+ *   0 (default)         L = max(128, 2 * ceil(n / 2^(c-1))): twice the mean run of uniform scalars at
+ *                       window c, so uniform scalars essentially never split
+ *   1 .. 65536          exactly this cap
+ *   BN_MSM_RUN_UNSPLIT  never split: one lane per key whatever its run (all-equal scalars at 2^18
+ *                       terms then take seconds; kept for measurements)
+ * Anything else is refused with BN_ERR_INVALID_ARGUMENT.  With the default, skewed batches of 2^18 terms
+ * (all scalars equal; half of them 1; 1 % equal to r - 1) take 4 - 9 ms and beat the small path; only a
+ * batch whose scalars are ALL 0 or 1 is still faster there (bn_set_msm_min above n), since G * 1 is no
+ * chain at all.  No value changes a result: the pieces are
+ * the same points added in another order, the group law is exact and the image normalized.  On a
+ * multi-device context it applies to every device.
+ * Workspace: the partial sums live beside the bucket sums (one point each: 96 bytes for G1, 192 for
+ * G2), sized by bn_msm_reserve / bn_g2_msm_reserve for the setting current then, else grown on first
+ * use, and not counted by bn_workspace_bytes.  With E = n * windows entries and K = min(buckets *
+ * windows, E / (L + 1)) the most keys that can be long, the chunk sums take at most E / L + K points
+ * (at most 2 E / L) and the first fold level 1/32 of that plus K; further levels reuse the two.
+ * Nothing is allocated when n <= L.  A forced tiny L at a huge n may fail to allocate, and the call
+ * then returns BN_ERR_HIP like any other allocation failure. */
+#define BN_MSM_RUN_UNSPLIT ((size_t)-1)
+int bn_set_msm_run_max(bn_ctx* ctx, size_t entries);
 /* pre-size the G1 MSM workspace for up to n terms (else allocated on first use, as bn_reserve);
  * it is separate from the pairing workspace and not counted by bn_workspace_bytes */
 int bn_msm_reserve(bn_ctx* ctx, size_t n);

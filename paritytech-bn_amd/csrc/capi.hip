@@ -948,7 +948,8 @@ static void ctx_teardown(bn_ctx* c) {
     for (void* p : {(void*)c->coeffs, (void*)c->paff, (void*)c->slots, (void*)c->flags, (void*)c->d_err,
                     (void*)c->d_prog, c->stage, (void*)c->tail_ws, (void*)c->fe_ds_ws, (void*)c->msm_keys,
                     (void*)c->msm_sorted, (void*)c->msm_g1.buckets, (void*)c->msm_g1.parts, (void*)c->msm_g1.tmp,
-                    (void*)c->msm_g2.buckets, (void*)c->msm_g2.parts, (void*)c->msm_g2.tmp, (void*)c->msm_g1.fixed})
+                    (void*)c->msm_g2.buckets, (void*)c->msm_g2.parts, (void*)c->msm_g2.tmp, (void*)c->msm_g1.fixed,
+                    (void*)c->msm_g1.run_a, (void*)c->msm_g1.run_b, (void*)c->msm_g2.run_a, (void*)c->msm_g2.run_b})
         if (p) (void)hipFree(p);
     for (bn_g2_prepared* h : c->prepared) {  // the handles still alive (the streams are drained)
         if (h->table) (void)hipFree(h->table);

@@ -26,6 +26,8 @@ struct MsmGroup<bn_g1> {
     static constexpr auto k_count = k_msm_count;
     static constexpr auto k_scatter = k_msm_scatter;
     static constexpr auto k_accumulate = k_msm_accumulate;
+    static constexpr auto k_chunk = k_msm_chunk;
+    static constexpr auto k_fold = k_msm_fold;
     static constexpr auto k_reduce = k_msm_reduce;
     static constexpr auto k_horner = k_msm_horner;
     static constexpr auto k_finish = k_msm_finish;
@@ -52,6 +54,8 @@ struct MsmGroup<bn_g2> {
     static constexpr auto k_count = k_msm_count_g2;
     static constexpr auto k_scatter = k_msm_scatter_g2;
     static constexpr auto k_accumulate = k_msm_accumulate_g2;
+    static constexpr auto k_chunk = k_msm_chunk_g2;
+    static constexpr auto k_fold = k_msm_fold_g2;
     static constexpr auto k_reduce = k_msm_reduce_g2;
     static constexpr auto k_horner = k_msm_horner_g2;
     static constexpr auto k_finish = k_msm_finish_g2;
@@ -78,6 +82,11 @@ struct MsmPlan {
     int c;
     uint32_t nwin, nkeys, nseg;
     size_t nent;  // n * W(c): the most entries
+    // the overlong runs (msm.h): the run cap (kMsmRunUnsplit when no key of n terms can be
+    // long), the fold levels launched, and the slots of the even and the odd levels' arrays
+    uint32_t L;
+    int levels;
+    size_t slots_a, slots_b;
 };
 template <class P>
 static MsmPlan msm_plan(bn_ctx* c, size_t n) {
@@ -89,15 +98,27 @@ static MsmPlan msm_plan(bn_ctx* c, size_t n) {
     m.nkeys = msm_num_keys(m.c);
     m.nseg = (msm_buckets(m.c) + kMsmSegment - 1) / kMsmSegment;
     m.nent = n * m.nwin;
+    m.L = g.run_max == BN_MSM_RUN_UNSPLIT ? kMsmRunUnsplit
+          : g.run_max                     ? (uint32_t)g.run_max
+                                          : msm_run_cap_default((uint32_t)n, m.c);
+    m.levels = msm_fold_levels((uint32_t)n, m.L);
+    if (m.levels == 0) m.L = kMsmRunUnsplit;
+    if (m.levels && m.nent <= (size_t)0x7fffffff) {
+        m.slots_a = msm_level_slots((uint32_t)m.nent, m.nkeys, m.L, 0);
+        if (m.levels > 1) m.slots_b = msm_level_slots((uint32_t)m.nent, m.nkeys, m.L, 1);
+    }
     return m;
 }
 template <class P>
 static int msm_reserve(bn_ctx* c, size_t n, const MsmPlan& m) {
     MsmGroupWs<P>& g = MsmGroup<P>::ws(c);
     if (m.small) return grow_dev(c, &g.tmp, &g.tmp_cap, n);
-    RET_IF(grow_dev(c, &c->msm_keys, &c->msm_keys_cap, 3 * (size_t)m.nkeys + 1));
+    // counts | cursors | offsets (nkeys + 1) | the count of long keys | the long keys
+    RET_IF(grow_dev(c, &c->msm_keys, &c->msm_keys_cap, 4 * (size_t)m.nkeys + 2));
     RET_IF(grow_dev(c, &c->msm_sorted, &c->msm_sorted_cap, m.nent));
     RET_IF(grow_dev(c, &g.buckets, &g.buckets_cap, (size_t)m.nkeys));
+    RET_IF(grow_dev(c, &g.run_a, &g.run_a_cap, m.slots_a));
+    RET_IF(grow_dev(c, &g.run_b, &g.run_b_cap, m.slots_b));
     return grow_dev(c, &g.parts, &g.parts_cap, (size_t)m.nseg * m.nwin);
 }
 // buf[0 .. width) = sum of the m rows of `width` points at buf by a halving addition tree in
@@ -154,9 +175,27 @@ static int msm_dev_impl(bn_ctx* c, const P* d_p, const bn_fr* d_k, size_t n, P* 
     const size_t nparts = (size_t)m.nseg * m.nwin;
     HIPCHK(c, hipMemsetAsync(counts, 0, (size_t)m.nkeys * 4, s));
     G::k_count<<<grid_for(n), kBlock, 0, s>>>(d_p, d_k, n, m.c, m.nkeys, counts);
-    k_msm_scan<<<1, kMsmScanBlock, 0, s>>>(counts, m.nkeys, offsets, cursors);
+    uint32_t* longinfo = offsets + m.nkeys + 1;
+    k_msm_scan<<<1, kMsmScanBlock, 0, s>>>(counts, m.nkeys, offsets, cursors, m.L, longinfo);
     G::k_scatter<<<grid_for(n), kBlock, 0, s>>>(d_p, d_k, n, m.c, m.nkeys, cursors, offsets, c->msm_sorted, nent);
-    G::k_accumulate<<<grid_for(G::kLanes * m.nkeys), kBlock, 0, s>>>(d_p, n, c->msm_sorted, offsets, m.nkeys, nent, g.buckets);
+    G::k_accumulate<<<grid_for(G::kLanes * m.nkeys), kBlock, 0, s>>>(d_p, n, c->msm_sorted, offsets, m.nkeys, nent, m.L, g.buckets);
+    if (m.levels) {
+        // The runs above the cap: their chunks, then one fold launch per level the largest
+        // run n terms can have needs; every grid is the host's bound for its level, and a
+        // lane whose slot no long key holds returns.  Even levels write run_a, odd ones run_b.
+        const uint32_t s0 = (uint32_t)std::min(m.slots_a, g.run_a_cap);
+        G::k_chunk<<<grid_for(G::kLanes * (size_t)s0), kBlock, 0, s>>>(d_p, n, c->msm_sorted, offsets, longinfo, m.nkeys, nent, m.L, g.run_a, s0);
+        uint32_t nsrc = s0;
+        for (int lv = 1; lv <= m.levels; ++lv) {
+            P* src = lv & 1 ? g.run_a : g.run_b;
+            P* dst = lv & 1 ? g.run_b : g.run_a;
+            const size_t cap = lv == m.levels ? 0 : (lv & 1 ? g.run_b_cap : g.run_a_cap);  // the last level writes buckets only
+            const uint32_t slots = msm_level_slots(nent, m.nkeys, m.L, lv);
+            const uint32_t ndst = (uint32_t)std::min<size_t>(slots, cap);
+            G::k_fold<<<grid_for(G::kLanes * (size_t)slots), kBlock, 0, s>>>(src, nsrc, offsets, longinfo, m.nkeys, nent, m.L, lv, dst, ndst, slots, g.buckets);
+            nsrc = ndst;
+        }
+    }
     G::k_reduce<<<grid_for(G::kLanes * nparts), kBlock, 0, s>>>(g.buckets, m.c, m.nkeys, m.nseg, g.parts);
     RET_IF(msm_tree_out<P>(c, g.parts, m.nseg, m.nwin, 0, nullptr, s));
     G::k_horner<<<1, 64, 0, s>>>(g.parts, m.c, finish, d_out);
@@ -575,6 +614,15 @@ int bn_set_msm_min(bn_ctx* c, size_t n) {
     CTX_GUARD(c);
     c->msm_g1.min = n;
     c->msm_g2.min = n;
+    return BN_OK;
+}
+int bn_set_msm_run_max(bn_ctx* c, size_t entries) {
+    if (c && entries != BN_MSM_RUN_UNSPLIT && entries > kMsmRunMax)
+        return fail(c, BN_ERR_INVALID_ARGUMENT, "run cap outside 1 .. 65536 (0: default, BN_MSM_RUN_UNSPLIT: never split)");
+    if (is_multi(c)) return for_each_sub(c, [&](bn_ctx* d) { return bn_set_msm_run_max(d, entries); });
+    CTX_GUARD(c);
+    c->msm_g1.run_max = entries;
+    c->msm_g2.run_max = entries;
     return BN_OK;
 }
 int bn_msm_reserve(bn_ctx* c, size_t n) {

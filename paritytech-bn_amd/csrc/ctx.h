@@ -22,6 +22,12 @@ struct MsmGroupWs {
     P* parts = nullptr;
     P* tmp = nullptr;
     size_t buckets_cap = 0, parts_cap = 0, tmp_cap = 0;
+    // the run cap (msm.h): 0 the default rule, (size_t)-1 never split; run_a / run_b the partial
+    // sums of the overlong runs, the even and the odd levels of the chunk and fold tree
+    size_t run_max = 0;
+    P* run_a = nullptr;
+    P* run_b = nullptr;
+    size_t run_a_cap = 0, run_b_cap = 0;
     int fixed_lanes = 0;  // lanes per output of the lookup kernel; 0: chosen from m and k (msm_fixed.h)
     P* fixed = nullptr;
     size_t fixed_cap = 0;
@@ -125,7 +131,7 @@ struct bn_ctx {
     // kernels_msm_g2.hip).  Its workspace is its own (not part of bn_workspace_bytes),
     // grown by bn_msm_reserve / bn_g2_msm_reserve or on first use, ordered like the
     // shared one (ws_event) and freed with the context.  Both groups share the integer
-    // buffers: msm_keys = counts | cursors | offsets of the (window, bucket) keys,
+    // buffers: msm_keys = counts | cursors | offsets | long keys of the (window, bucket) keys,
     // msm_sorted the entries sorted by key.  Each group has its own settings and point
     // buffers (MsmGroupWs).
     uint32_t* msm_keys = nullptr;

@@ -599,11 +599,18 @@ __global__ void __launch_bounds__(kBlock) k_g2_op(int op, const bn_g2* a, const 
                                                   uint8_t* __restrict__ eq);
 // kernels_msm.hip
 __global__ void __launch_bounds__(kBlock) k_msm_count(const bn_g1* __restrict__ p, const bn_fr* __restrict__ k, size_t n, int c, uint32_t nkeys, uint32_t* __restrict__ counts);
-__global__ void __launch_bounds__(kMsmScanBlock) k_msm_scan(const uint32_t* __restrict__ counts, uint32_t nkeys, uint32_t* __restrict__ offsets, uint32_t* __restrict__ cursors);
+__global__ void __launch_bounds__(kMsmScanBlock) k_msm_scan(const uint32_t* __restrict__ counts, uint32_t nkeys, uint32_t* __restrict__ offsets, uint32_t* __restrict__ cursors, uint32_t L,
+                                                            uint32_t* __restrict__ longinfo);
 __global__ void __launch_bounds__(kBlock) k_msm_scatter(const bn_g1* __restrict__ p, const bn_fr* __restrict__ k, size_t n, int c, uint32_t nkeys, uint32_t* __restrict__ cursors,
                                                         const uint32_t* __restrict__ offsets, uint32_t* __restrict__ sorted, uint32_t nent);
 __global__ void __launch_bounds__(kBlock) k_msm_accumulate(const bn_g1* __restrict__ p, size_t n, const uint32_t* __restrict__ sorted, const uint32_t* __restrict__ offsets,
-                                                           uint32_t nkeys, uint32_t nent, bn_g1* __restrict__ buckets);
+                                                           uint32_t nkeys, uint32_t nent, uint32_t L, bn_g1* __restrict__ buckets);
+// the overlong runs (msm.h): longinfo = the count of long keys, then those keys
+__global__ void __launch_bounds__(kBlock) k_msm_chunk(const bn_g1* __restrict__ p, size_t n, const uint32_t* __restrict__ sorted, const uint32_t* __restrict__ offsets,
+                                                      const uint32_t* __restrict__ longinfo, uint32_t nkeys, uint32_t nent, uint32_t L, bn_g1* __restrict__ sums, uint32_t nslots);
+__global__ void __launch_bounds__(kBlock) k_msm_fold(const bn_g1* __restrict__ src, uint32_t nsrc, const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ longinfo,
+                                                     uint32_t nkeys, uint32_t nent, uint32_t L, int level, bn_g1* __restrict__ dst, uint32_t ndst, uint32_t nslots,
+                                                     bn_g1* __restrict__ buckets);
 __global__ void __launch_bounds__(kBlock) k_msm_reduce(const bn_g1* __restrict__ buckets, int c, uint32_t nkeys, uint32_t nseg, bn_g1* __restrict__ parts);
 __global__ void __launch_bounds__(64) k_msm_horner(const bn_g1* __restrict__ win, int c, int finish, bn_g1* __restrict__ out);
 __global__ void __launch_bounds__(64) k_msm_finish(const bn_g1* in, bn_g1* out);
@@ -612,7 +619,12 @@ __global__ void __launch_bounds__(kBlock) k_msm_scatter_g2(const bn_g2* __restri
                                                            const uint32_t* __restrict__ offsets, uint32_t* __restrict__ sorted, uint32_t nent);
 // kernels_msm_g2.hip: kPathLanes lanes per (window, bucket) key, per (segment, window), per result
 __global__ void __launch_bounds__(kBlock) k_msm_accumulate_g2(const bn_g2* __restrict__ p, size_t n, const uint32_t* __restrict__ sorted, const uint32_t* __restrict__ offsets,
-                                                              uint32_t nkeys, uint32_t nent, bn_g2* __restrict__ buckets);
+                                                              uint32_t nkeys, uint32_t nent, uint32_t L, bn_g2* __restrict__ buckets);
+__global__ void __launch_bounds__(kBlock) k_msm_chunk_g2(const bn_g2* __restrict__ p, size_t n, const uint32_t* __restrict__ sorted, const uint32_t* __restrict__ offsets,
+                                                         const uint32_t* __restrict__ longinfo, uint32_t nkeys, uint32_t nent, uint32_t L, bn_g2* __restrict__ sums, uint32_t nslots);
+__global__ void __launch_bounds__(kBlock) k_msm_fold_g2(const bn_g2* __restrict__ src, uint32_t nsrc, const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ longinfo,
+                                                        uint32_t nkeys, uint32_t nent, uint32_t L, int level, bn_g2* __restrict__ dst, uint32_t ndst, uint32_t nslots,
+                                                        bn_g2* __restrict__ buckets);
 __global__ void __launch_bounds__(kBlock) k_msm_reduce_g2(const bn_g2* __restrict__ buckets, int c, uint32_t nkeys, uint32_t nseg, bn_g2* __restrict__ parts);
 __global__ void __launch_bounds__(64) k_msm_horner_g2(const bn_g2* __restrict__ win, int c, int finish, bn_g2* __restrict__ out);
 __global__ void __launch_bounds__(64) k_msm_finish_g2(const bn_g2* in, bn_g2* out);

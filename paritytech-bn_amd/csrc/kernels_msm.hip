@@ -4,9 +4,13 @@
 // are msm_group.h's).  The phases pass data only across kernel boundaries on one
 // stream (no block waits for another):
 //   k_msm_count       signed-digit recoding (msm.h), histogram of the (window, bucket) keys
-//   k_msm_scan        exclusive scan of the histogram -> bucket offsets and scatter cursors
+//   k_msm_scan        exclusive scan of the histogram -> bucket offsets and scatter cursors,
+//                     and the list of the long keys (runs above the run cap, msm.h)
 //   k_msm_scatter     recoding again, each entry (term index, sign) to its bucket's run
-//   k_msm_accumulate  one lane per bucket: gathers its run's points and adds them
+//   k_msm_accumulate  one lane per bucket: gathers its run's points and adds them (short keys)
+//   k_msm_chunk       one lane per chunk of a long key's run: the chunk's sum
+//   k_msm_fold        one lane per group of up to kMsmFoldFan partial sums of a long key, once
+//                     per level of the tree; a key's last group writes its bucket
 //   k_msm_reduce      one lane per segment of kMsmSegment buckets: sum_j (j + 1) * B_j
 //   (k_g1_op add)     addition tree over each window's segments (capi_msm.hip)
 //   k_msm_horner      one lane: Horner over the window sums, then normalize
@@ -36,6 +40,39 @@ __device__ __forceinline__ void st_g1(bn_g1& o, const G1J& r) {
 // zero points produce no entry.  All it reads of a point is whether z is zero.
 __device__ __forceinline__ bool msm_point_is_zero(const bn_g1& a) { return F_is_zero(ld_ref(a.z)); }
 __device__ __forceinline__ bool msm_point_is_zero(const bn_g2& a) { return F_is_zero(ld_ref2(a.z)); }
+// The lanes of a wave that hold the same key share one atomic: skewed scalars (all equal, a
+// witness of zeros and ones) send most of a wave to one address, and 2^18 x W(c) atomics on
+// one address per hot key took 4.2 ms (count) and 8.6 ms (scatter) of an all-equal batch whose
+// group-law kernels took 2 ms.  kMsmAggRounds times: the first lane not yet
+// served names its key, the lanes with that key (a ballot) take consecutive positions from
+// one atomicAdd of their count by that lane; whoever is left adds alone.  Two rounds find a
+// key that half the wave holds with probability 3/4 and cost uniform scalars two ballots and
+// two broadcasts per round.  Returns the value of counts[key] before this lane's own
+// increment; every lane of the wave that has not returned calls it together (`has`: with a key).
+constexpr int kMsmAggRounds = 2;
+__device__ __forceinline__ uint32_t msm_claim(uint32_t* __restrict__ counts, uint32_t key, bool has) {
+    const uint32_t lane = __lane_id();
+    uint32_t pos = 0;
+    bool done = !has;
+#pragma unroll
+    for (int round = 0; round < kMsmAggRounds; ++round) {
+        const uint64_t rem = __ballot(!done);
+        if (rem == 0) break;  // wave-uniform
+        const int leader = __ffsll((long long)rem) - 1;
+        const uint32_t lkey = __shfl(key, leader);
+        const bool mine = !done && key == lkey;
+        const uint64_t grp = __ballot(mine);
+        uint32_t base = 0;
+        if (mine && lane == (uint32_t)leader) base = atomicAdd(&counts[key], (uint32_t)__popcll(grp));
+        base = __shfl(base, leader);
+        if (mine) {
+            pos = base + (uint32_t)__popcll(grp & ((1ull << lane) - 1ull));
+            done = true;
+        }
+    }
+    if (!done) pos = atomicAdd(&counts[key], 1u);
+    return pos;
+}
 template <bool kScatter, class P>
 __device__ __forceinline__ void msm_digits(const P* __restrict__ p, const bn_fr* __restrict__ k, size_t n, int c,
                                            uint32_t nkeys, uint32_t* __restrict__ counts,
@@ -49,16 +86,13 @@ __device__ __forceinline__ void msm_digits(const P* __restrict__ p, const bn_fr*
     fr_to_canonical(k[i], s);
     uint32_t carry = 0;
     const int nw = msm_windows(c);
-    for (int w = 0; w < nw; ++w) {
+    for (int w = 0; w < nw; ++w) {  // the same trip count on every lane: msm_claim's ballots see the whole wave
         const int32_t d = msm_signed_digit(msm_raw_window(s, c, w), c, &carry);
-        if (d == 0) continue;
-        const uint32_t key = msm_key(c, w, d, (uint32_t)i);
-        if (key >= nkeys) continue;
-        if constexpr (!kScatter) {
-            atomicAdd(&counts[key], 1u);
-        } else {
-            const uint32_t pos = atomicAdd(&counts[key], 1u);  // counts = the cursors here
-            if (pos < offsets[key + 1] && pos < nent) sorted[pos] = msm_entry((uint32_t)i, d);
+        const uint32_t key = d != 0 ? msm_key(c, w, d, (uint32_t)i) : nkeys;
+        const bool has = key < nkeys;
+        const uint32_t pos = msm_claim(counts, key, has);  // counts = the cursors when scattering
+        if constexpr (kScatter) {
+            if (has && pos < offsets[key + 1] && pos < nent) sorted[pos] = msm_entry((uint32_t)i, d);
         }
     }
 }
@@ -85,42 +119,59 @@ __global__ void __launch_bounds__(kBlock) k_msm_scatter_g2(const bn_g2* __restri
     msm_digits<true>(p, k, n, c, nkeys, cursors, offsets, sorted, nent);
 }
 
-// offsets[0 .. nkeys] = exclusive scan of counts[0 .. nkeys), cursors[key] = offsets[key].
-// One block: each thread scans a contiguous piece, the piece totals go through LDS.
+// offsets[0 .. nkeys] = exclusive scan of counts[0 .. nkeys), cursors[key] = offsets[key];
+// longinfo[0] = the number of keys with more than L entries, longinfo[1 ..] those keys in
+// key order (at most nkeys; none at L = kMsmRunUnsplit).  One block: each thread scans a
+// contiguous piece, the piece totals (entries in the low half, long keys in the high half
+// of one 64-bit word: the entries stay below 2^31) go through LDS.
 __global__ void __launch_bounds__(kMsmScanBlock) k_msm_scan(const uint32_t* __restrict__ counts, uint32_t nkeys,
                                                             uint32_t* __restrict__ offsets,
-                                                            uint32_t* __restrict__ cursors) {
-    __shared__ uint32_t tot[kMsmScanBlock];
+                                                            uint32_t* __restrict__ cursors, uint32_t L,
+                                                            uint32_t* __restrict__ longinfo) {
+    __shared__ uint64_t tot[kMsmScanBlock];
     const uint32_t t = threadIdx.x;
     const uint32_t per = (nkeys + kMsmScanBlock - 1) / kMsmScanBlock;
     const uint32_t lo = t * per < nkeys ? t * per : nkeys;
     const uint32_t hi = lo + per < nkeys ? lo + per : nkeys;
-    uint32_t sum = 0;
-    for (uint32_t j = lo; j < hi; ++j) sum += counts[j];
+    uint64_t sum = 0;
+    for (uint32_t j = lo; j < hi; ++j) {
+        const uint32_t cnt = counts[j];
+        sum += (uint64_t)cnt + ((uint64_t)(cnt > L ? 1u : 0u) << 32);
+    }
     tot[t] = sum;
     __syncthreads();
     for (uint32_t d = 1; d < kMsmScanBlock; d <<= 1) {  // inclusive scan of the piece totals
-        const uint32_t v = t >= d ? tot[t - d] : 0u;
+        const uint64_t v = t >= d ? tot[t - d] : 0u;
         __syncthreads();
         tot[t] += v;
         __syncthreads();
     }
-    uint32_t run = tot[t] - sum;
+    const uint64_t before = tot[t] - sum;
+    uint32_t run = (uint32_t)before, rank = (uint32_t)(before >> 32);
     for (uint32_t j = lo; j < hi; ++j) {
+        const uint32_t cnt = counts[j];
         offsets[j] = run;
         cursors[j] = run;
-        run += counts[j];
+        run += cnt;
+        if (cnt > L) {
+            if (rank < nkeys) longinfo[1 + rank] = j;
+            ++rank;
+        }
     }
-    if (t == kMsmScanBlock - 1) offsets[nkeys] = tot[t];
+    if (t == kMsmScanBlock - 1) {
+        offsets[nkeys] = (uint32_t)tot[t];
+        longinfo[0] = (uint32_t)(tot[t] >> 32);
+    }
 }
 
 // ---------------------------------------------------------------- bucket accumulation
 // One lane per (window, bucket): the sum of its run of sorted entries
-// (msm_group.h msm_bucket_sum).  An empty bucket is zero.
+// (msm_group.h msm_bucket_sum).  An empty bucket is zero.  A run of more than L entries is
+// left to k_msm_chunk / k_msm_fold, which write its bucket.
 __global__ void __launch_bounds__(kBlock) k_msm_accumulate(const bn_g1* __restrict__ p, size_t n,
                                                            const uint32_t* __restrict__ sorted,
                                                            const uint32_t* __restrict__ offsets, uint32_t nkeys,
-                                                           uint32_t nent, bn_g1* __restrict__ buckets) {
+                                                           uint32_t nent, uint32_t L, bn_g1* __restrict__ buckets) {
     fold_table_init();
     const size_t key = lane_id();
     if (key >= nkeys) return;
@@ -128,8 +179,44 @@ __global__ void __launch_bounds__(kBlock) k_msm_accumulate(const bn_g1* __restri
     hi = hi < nent ? hi : nent;
     uint32_t lo = offsets[key];
     lo = lo < hi ? lo : hi;
+    if (hi - lo > L) return;
     const G1J acc = msm_bucket_sum<Fq>([&](uint32_t idx) { return ld_g1(p[idx]); }, n, sorted, lo, hi);
     st_g1(buckets[key], acc);
+}
+
+// ---------------------------------------------------------------- overlong runs (msm.h)
+// One lane per level-0 slot: the sum of one chunk of at most L entries of a long key's run
+// (msm_run_task finds the key and the chunk from the slot).  A slot no key holds does
+// nothing; with no long key every lane returns after one load.
+__global__ void __launch_bounds__(kBlock) k_msm_chunk(const bn_g1* __restrict__ p, size_t n,
+                                                      const uint32_t* __restrict__ sorted,
+                                                      const uint32_t* __restrict__ offsets,
+                                                      const uint32_t* __restrict__ longinfo, uint32_t nkeys,
+                                                      uint32_t nent, uint32_t L, bn_g1* __restrict__ sums,
+                                                      uint32_t nslots) {
+    fold_table_init();
+    const size_t t = lane_id();
+    if (t >= nslots) return;
+    const MsmRunTask task = msm_run_task(longinfo + 1, offsets, longinfo[0], nkeys, nent, L, 0, (uint32_t)t);
+    if (!task.some) return;
+    const G1J acc = msm_bucket_sum<Fq>([&](uint32_t idx) { return ld_g1(p[idx]); }, n, sorted, task.lo, task.hi);
+    st_g1(sums[t], acc);
+}
+// One lane per slot of fold level `level` >= 1: the sum of up to kMsmFoldFan consecutive
+// partial sums of one long key at the level below (src[0 .. nsrc)), into the key's bucket
+// when it is the key's only group, else into dst[slot] (dst[0 .. ndst)).
+__global__ void __launch_bounds__(kBlock) k_msm_fold(const bn_g1* __restrict__ src, uint32_t nsrc,
+                                                     const uint32_t* __restrict__ offsets,
+                                                     const uint32_t* __restrict__ longinfo, uint32_t nkeys,
+                                                     uint32_t nent, uint32_t L, int level, bn_g1* __restrict__ dst,
+                                                     uint32_t ndst, uint32_t nslots, bn_g1* __restrict__ buckets) {
+    fold_table_init();
+    const size_t t = lane_id();
+    if (t >= nslots) return;
+    const MsmRunTask task = msm_run_task(longinfo + 1, offsets, longinfo[0], nkeys, nent, L, level, (uint32_t)t);
+    if (!task.some || task.hi > nsrc || (!task.last && t >= ndst)) return;
+    const G1J acc = msm_fold_sum<Fq>([&](uint32_t i) { return ld_g1(src[i]); }, task.lo, task.hi);
+    st_g1(task.last ? buckets[task.key] : dst[t], acc);
 }
 
 // ---------------------------------------------------------------- bucket reduction

@@ -2,7 +2,9 @@
 // (bn_g2_msm; the phases are kernels_msm.hip's, the bodies msm_group.h's) on the
 // pairing path's two-lane layout (fq2_split.h): lanes 2j and 2j + 1
 // hold coordinates c0 and c1 of the points of element j.
-//   k_msm_accumulate_g2  one lane pair per (window, bucket) key
+//   k_msm_accumulate_g2  one lane pair per (window, bucket) key (short keys)
+//   k_msm_chunk_g2       one lane pair per chunk of a long key's run (msm.h)
+//   k_msm_fold_g2        one lane pair per group of partial sums of a long key, once per level
 //   k_msm_reduce_g2      one lane pair per (segment, window)
 //   k_msm_horner_g2      one lane pair: Horner over the window sums
 //   k_msm_finish_g2      one lane pair: the returned image
@@ -46,7 +48,7 @@ __device__ __forceinline__ void st_g2(bn_g2& o, const G2J& r) {
 __global__ void __launch_bounds__(kBlock) k_msm_accumulate_g2(const bn_g2* __restrict__ p, size_t n,
                                                               const uint32_t* __restrict__ sorted,
                                                               const uint32_t* __restrict__ offsets, uint32_t nkeys,
-                                                              uint32_t nent, bn_g2* __restrict__ buckets) {
+                                                              uint32_t nent, uint32_t L, bn_g2* __restrict__ buckets) {
     fold_table_init();
     const size_t key = lane_id() / kL;
     if (key >= nkeys) return;
@@ -54,8 +56,40 @@ __global__ void __launch_bounds__(kBlock) k_msm_accumulate_g2(const bn_g2* __res
     hi = hi < nent ? hi : nent;
     uint32_t lo = offsets[key];
     lo = lo < hi ? lo : hi;
+    if (hi - lo > L) return;  // a long key: k_msm_chunk_g2 / k_msm_fold_g2 write its bucket
     const G2J acc = msm_bucket_sum<Fq2>([&](uint32_t idx) { return ld_g2(p[idx]); }, n, sorted, lo, hi);
     st_g2(buckets[key], acc);
+}
+
+// The overlong runs (msm.h; the G1 kernels are kernels_msm.hip's k_msm_chunk / k_msm_fold).
+// Both lanes of a pair derive the slot, and from it the key, the chunk or group and every
+// bound, from lane_id() / kL and the same loads, so they take every branch together.
+__global__ void __launch_bounds__(kBlock) k_msm_chunk_g2(const bn_g2* __restrict__ p, size_t n,
+                                                         const uint32_t* __restrict__ sorted,
+                                                         const uint32_t* __restrict__ offsets,
+                                                         const uint32_t* __restrict__ longinfo, uint32_t nkeys,
+                                                         uint32_t nent, uint32_t L, bn_g2* __restrict__ sums,
+                                                         uint32_t nslots) {
+    fold_table_init();
+    const size_t t = lane_id() / kL;
+    if (t >= nslots) return;
+    const MsmRunTask task = msm_run_task(longinfo + 1, offsets, longinfo[0], nkeys, nent, L, 0, (uint32_t)t);
+    if (!task.some) return;
+    const G2J acc = msm_bucket_sum<Fq2>([&](uint32_t idx) { return ld_g2(p[idx]); }, n, sorted, task.lo, task.hi);
+    st_g2(sums[t], acc);
+}
+__global__ void __launch_bounds__(kBlock) k_msm_fold_g2(const bn_g2* __restrict__ src, uint32_t nsrc,
+                                                        const uint32_t* __restrict__ offsets,
+                                                        const uint32_t* __restrict__ longinfo, uint32_t nkeys,
+                                                        uint32_t nent, uint32_t L, int level, bn_g2* __restrict__ dst,
+                                                        uint32_t ndst, uint32_t nslots, bn_g2* __restrict__ buckets) {
+    fold_table_init();
+    const size_t t = lane_id() / kL;
+    if (t >= nslots) return;
+    const MsmRunTask task = msm_run_task(longinfo + 1, offsets, longinfo[0], nkeys, nent, L, level, (uint32_t)t);
+    if (!task.some || task.hi > nsrc || (!task.last && t >= ndst)) return;
+    const G2J acc = msm_fold_sum<Fq2>([&](uint32_t i) { return ld_g2(src[i]); }, task.lo, task.hi);
+    st_g2(task.last ? buckets[task.key] : dst[t], acc);
 }
 
 // parts[s * nwin + w], so that the addition tree over the segments is k_g2_op on

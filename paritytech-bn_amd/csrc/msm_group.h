@@ -42,6 +42,20 @@ BN_INLINE Jac<F> msm_bucket_sum(Load&& point, size_t n, const uint32_t* sorted, 
     return acc;
 }
 
+// An overlong run (msm.h: more than the run cap's entries) is summed in pieces: each chunk
+// sorted[lo .. hi) of at most L entries by msm_bucket_sum itself, then the chunk sums by a
+// tree of msm_fold_sum over at most kFan consecutive partial sums part(lo .. hi).  The
+// pieces are the same points in another bracketing, so the bucket's point is the same and
+// the normalized result the same bytes; jac_add's doubling branch and zero short-cuts
+// cover equal and cancelling partial sums.
+template <template <int> class F, uint32_t kFan = kMsmFoldFan, class Load>
+BN_INLINE Jac<F> msm_fold_sum(Load&& part, uint32_t lo, uint32_t hi) {
+    hi = hi < lo ? lo : (hi - lo > kFan ? lo + kFan : hi);
+    Jac<F> acc = jac_zero<F>();
+    for (uint32_t i = lo; i < hi; ++i) acc = jac_add(acc, part(i));
+    return acc;
+}
+
 // Segment s of window w holds the buckets j0 .. j0 + len - 1 (j0 = s * kMsmSegment);
 // bucket b weighs (b >> rs) + 1, rs the window's replica shift (msm.h: 0 except in
 // the top window).  Running sums from the top give S = sum B_b and, adding S into T

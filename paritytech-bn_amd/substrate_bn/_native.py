@@ -38,6 +38,7 @@ EXPORTS = [
     "bn_pairing_batch_dev", "bn_miller_loop_batch_dev", "bn_set_fe_wide_max", "bn_g2_precompute_many",
     "bn_set_latency_max", "bn_dev_status", "bn_set_fq12_op_unit",
     "bn_g1_msm", "bn_g1_msm_dev", "bn_set_msm_window", "bn_set_msm_min", "bn_msm_reserve",
+    "bn_set_msm_run_max",
     "bn_g2_msm", "bn_g2_msm_dev", "bn_g2_msm_reserve",
     "bn_g1_prepared_table_bytes", "bn_g1_bases_prepare", "bn_g1_bases_prepare_dev", "bn_g1_prepared_count",
     "bn_g1_prepared_window", "bn_g1_prepared_destroy", "bn_g1_msm_prepared_many", "bn_g1_msm_prepared_many_dev",
@@ -136,6 +137,7 @@ def load():
         "bn_g1_msm_dev": ([vp, vp, vp, sz, vp, vp], i),
         "bn_set_msm_window": ([vp, i], i),
         "bn_set_msm_min": ([vp, sz], i),
+        "bn_set_msm_run_max": ([vp, sz], i),
         "bn_msm_reserve": ([vp, sz], i),
         "bn_g2_msm": ([vp, vp, vp, sz, vp], i),
         "bn_g2_msm_dev": ([vp, vp, vp, sz, vp, vp], i),
@@ -248,6 +250,7 @@ def _indices(idx, n, nq):
 
 
 QIDX_FRESH = 0xffffffff   # BN_QIDX_FRESH: the term's G2 point is the next entry of q
+MSM_RUN_UNSPLIT = ctypes.c_size_t(-1).value  # BN_MSM_RUN_UNSPLIT: bn_set_msm_run_max's "never split"
 PRODUCT_LANE_MAX = 64     # terms per product of pairing_batch_prepared_many
 
 
@@ -683,6 +686,12 @@ class Context:
     def set_msm_min(self, n):
         """MSM batches below n terms take the small path; 0: always the bucket path."""
         self._check(self._L.bn_set_msm_min(self._h, n))
+
+    def set_msm_run_max(self, entries):
+        """The run cap of the MSM bucket path of both groups: a bucket with more entries is
+        summed in chunks of that many and a fold tree.  0: the default rule; 1 .. 65536: that
+        cap; MSM_RUN_UNSPLIT: never split.  No value changes a result."""
+        self._check(self._L.bn_set_msm_run_max(self._h, entries))
 
     def msm_reserve(self, n):
         self._check(self._L.bn_msm_reserve(self._h, n))

@@ -10,9 +10,20 @@ warm-up before timing), alternating in one process:
   default  a context with untouched settings (the window table and the threshold)
 Before a size is timed every form must return the same 96 (g2: 192) bytes, else the
 script exits non-zero.  One JSON line per size, then one line for all-equal scalars at
---skew terms (one lane, or lane pair, per window walks every term: the documented skew
-limit).  `frac` is the integer-VALU roofline fraction as DESIGN.md §4.5 counts it:
+--skew terms (every window has one bucket that holds every term; --run-cap measures the
+skew patterns in full).  `frac` is the integer-VALU roofline fraction as DESIGN.md §4.5 counts it:
 algorithmic Fq products x 128 MAD32 over the time, against 39.3 T MAD32/s.
+
+With --run-cap the sweep is over the run cap instead (bn_set_msm_run_max; msm.h), on the
+bucket path at the automatic window, alternating in one process:
+  unsplit  BN_MSM_RUN_UNSPLIT: one lane per key whatever its run
+  default  the default rule max(128, 2 * ceil(n / 2^(c-1)))
+  L0=K     the same rule with K for the 128, set as an explicit cap
+one JSON line per size with `default_in_unsplit_spread` (the default's median inside the
+unsplit form's own min .. max), then at --skew terms four skewed scalar patterns (all equal,
+all 1, half 1 / half uniform, 1 % equal to r - 1), each as unsplit (one repetition: it takes
+seconds), split (the default cap) and small (the small path), after checking that the three
+return the same bytes.
 """
 import argparse
 import json
@@ -32,6 +43,23 @@ PEAK_MAD32 = 39.3e12
 # square one on each lane (fq2.rs:105-117) = 2
 OPS = {"g1": (16, 7), "g2": (11 * 4 + 5 * 2, 2 * 4 + 5 * 2)}
 SEGMENT = 16      # kMsmSegment (msm.h)
+# capi_msm.hip MsmGroup<P>::auto_window: (first n of the next row, c)
+AUTO_WINDOW = {"g1": ((6144, 10), (92682, 12), (370728, 14), (741455, 15)),
+               "g2": ((1449, 10), (23171, 11), (46341, 12), (370728, 14), (741455, 15))}
+RUN_MIN = 128                     # kMsmRunMin (msm.h)
+RUN_MINS = (16, 32, 64, 128, 256)
+
+
+def auto_window(group, n):
+    for below, c in AUTO_WINDOW[group]:
+        if n < below:
+            return c
+    return 16
+
+
+def run_cap(n, c, run_min):
+    """msm.h msm_run_cap_default with run_min for kMsmRunMin"""
+    return max(run_min, 2 * -(-n // (1 << (c - 1))))
 
 
 def windows(c):
@@ -63,11 +91,13 @@ def main():
     ap.add_argument("--windows", default="8,9,10,11,12,13,14,15,16")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--skew", type=int, default=1 << 18)
+    ap.add_argument("--run-cap", action="store_true", help="sweep the run cap and the skew patterns instead of the window")
+    ap.add_argument("--skew-reps", type=int, default=10)
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     args = ap.parse_args()
     import torch
 
-    from substrate_bn import Context, synth
+    from substrate_bn import Context, _native, synth
 
     grp = args.group
     words = {"g1": 12, "g2": 24}[grp]
@@ -119,8 +149,20 @@ def main():
         else:
             c.g2_msm_reserve(n)
 
+    def setup_cap(name, n):
+        """the same for the forms of --run-cap"""
+        if name == "small":
+            return setup("small")
+        ctx.set_msm_min(0)
+        ctx.set_msm_window(0)
+        if name in ("unsplit", "default", "split"):
+            ctx.set_msm_run_max(_native.MSM_RUN_UNSPLIT if name == "unsplit" else 0)
+        else:
+            ctx.set_msm_run_max(run_cap(n, auto_window(grp, n), int(name[3:])))
+        return ctx
+
     def run(name, n, kd, timed):
-        c = setup(name)
+        c = setup_cap(name, n) if args.run_cap else setup(name)
         if not timed:
             reserve(c, n)
         msm_dev = c.g1_msm_dev if grp == "g1" else c.g2_msm_dev
@@ -135,6 +177,9 @@ def main():
     def stats(ts):
         return {"median_ms": round(statistics.median(ts), 4), "min_ms": round(min(ts), 4), "max_ms": round(max(ts), 4)}
 
+    if args.run_cap:
+        run_cap_sweep(args, grp, sizes, run, stats, emit, k, K, dev)
+        return
     forms = ["small"] + ["c=%d" % c for c in cs] + ["default"]
     for n in sizes:
         want = None
@@ -175,6 +220,66 @@ def main():
             sys.exit(1)
         ms_small, _ = run("small", n, ke, True)
         emit({"skew_all_equal_n": n, "bucket_ms": round(ms, 3), "small_ms": round(ms_small, 3), "reps": 1})
+
+
+def run_cap_sweep(args, grp, sizes, run, stats, emit, k, K, dev):
+    import torch
+
+    from oracle import oracle as O
+    forms = ["unsplit", "default"] + ["L0=%d" % m for m in RUN_MINS]
+    for n in sizes:
+        want = None
+        for f in forms:  # warm-up (allocates) and the agreement check
+            _, got = run(f, n, K, False)
+            if want is None:
+                want = got
+            elif not np.array_equal(got, want):
+                print("MISMATCH at n=%d: %s differs from unsplit" % (n, f), file=sys.stderr)
+                sys.exit(1)
+        times = {f: [] for f in forms}
+        for _ in range(args.reps):
+            for f in forms:
+                times[f].append(run(f, n, K, True)[0])
+        c = auto_window(grp, n)
+        rec = {"n": n, "reps": args.reps, "c": c, "default_cap": run_cap(n, c, RUN_MIN)}
+        for f in forms:
+            rec[f] = stats(times[f])
+        rec["default_in_unsplit_spread"] = rec["unsplit"]["min_ms"] <= rec["default"]["median_ms"] <= rec["unsplit"]["max_ms"]
+        rec["default_over_unsplit"] = round(rec["default"]["median_ms"] / rec["unsplit"]["median_ms"], 4)
+        emit(rec)
+    if not args.skew:
+        return
+    n = args.skew
+    one, minus_one = O.canon_to_mont_array([1, O.R - 1], O.FR).reshape(2, 4)
+    uni = k[:n]
+    pats = {"all_equal": np.tile(k[7], (n, 1)), "all_one": np.tile(one, (n, 1))}
+    half = uni.copy()
+    half[0::2] = one
+    pats["half_one"] = half
+    pct = uni.copy()
+    pct[0::100] = minus_one
+    pats["one_pct_minus_one"] = pct
+    for name, kv in pats.items():
+        kd = torch.from_numpy(np.ascontiguousarray(kv).view(np.int64)).to(dev)
+        torch.cuda.synchronize(dev)
+        _, want = run("small", n, kd, False)
+        _, got = run("split", n, kd, False)
+        if not np.array_equal(got, want):
+            print("MISMATCH on %s: split differs from the small path" % name, file=sys.stderr)
+            sys.exit(1)
+        # the split form's warm-up has allocated all unsplit needs; its one repetition is also its check
+        ms_unsplit, got = run("unsplit", n, kd, True)
+        if not np.array_equal(got, want):
+            print("MISMATCH on %s: unsplit differs from the small path" % name, file=sys.stderr)
+            sys.exit(1)
+        times = {"split": [], "small": []}
+        for _ in range(args.skew_reps):
+            for f in times:
+                times[f].append(run(f, n, kd, True)[0])
+        rec = {"skew": name, "n": n, "c": auto_window(grp, n), "unsplit_ms": round(ms_unsplit, 3), "unsplit_reps": 1,
+               "reps": args.skew_reps, "split": stats(times["split"]), "small": stats(times["small"])}
+        rec["split_beats_small"] = rec["split"]["median_ms"] < rec["small"]["median_ms"]
+        emit(rec)
 
 
 if __name__ == "__main__":
