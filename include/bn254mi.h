@@ -118,11 +118,21 @@ int bn_pairing_batch(bn_ctx* ctx, const bn_g1* p, const bn_g2* q, size_t n, bn_g
  * all-skipped product gives Gt::one(), and every out[j] is bit-identical to bn_pairing_batch
  * on the same slice.  A zero Miller product (no input is known to give one) makes that out[j]
  * the zero image and the call return BN_ERR_FE_ZERO, with every other row written.
- * Products of at most 64 terms run one per lane pair of one kernel (k_miller_products, the
- * shared-squaring loop per product) in launch sets of at most bn_set_products_chunk terms,
- * followed by one final exponentiation per product; a longer product, and every product of
- * a call with fewer than bn_set_products_min of the short ones, runs alone as
- * bn_pairing_batch_dev does.  Results are identical on every path.
+ * Three paths, chosen per call from its offsets; results are identical on
+ * every one.
+ * Wide: a call whose products of at most 64 terms are at least two and hold together at most
+ * bn_set_products_wide_max terms sends those products through the one-launch latency kernel
+ * (k_pairing_latency: every term's Miller value, 16 lanes per term), then one 16-lane group
+ * per product multiplies its terms' values (k_fq12_products_wide), then one final
+ * exponentiation per product: the path for calls too small to fill the GPU with lane pairs.
+ * Its launch sets hold at most min(bn_set_latency_max, bn_set_products_chunk) terms, and a
+ * product above that (when the minimum is below 64) is not eligible.
+ * Packed: otherwise, products of at most 64 terms run one per lane pair of one kernel
+ * (k_miller_products, the shared-squaring loop per product) in launch sets of at most
+ * bn_set_products_chunk terms, followed by one final exponentiation per product.
+ * Alone: a product of more than 64 terms, and, off the wide path, every product of a call
+ * with fewer than bn_set_products_min of the short ones, runs as bn_pairing_batch_dev does.
+ * bn_set_products_min(0) keeps the wide path off as well: every short product is packed.
  * The _dev form enqueues on `stream` without synchronizing and reports the data-dependent
  * outcome through bn_dev_status, as bn_pairing_many_dev does; it reads offsets before it
  * returns, may wait for the previous call's upload of its offsets (not for its kernels),
@@ -141,9 +151,15 @@ int bn_pairing_batch_many_dev(bn_ctx* ctx, const bn_g1* d_p, const bn_g2* d_q, c
  * crossover or $BN254MI_PRODUCTS_MIN.  On a multi-device context it applies
  * to every device (and to each device's shard). */
 int bn_set_products_min(bn_ctx* ctx, size_t m);
-/* terms per launch set of the packed path (a single product may exceed it); 0 = the default,
- * 2^18, and more than that is refused with BN_ERR_INVALID_ARGUMENT */
+/* terms per launch set of the packed path (a single product may exceed it) and of the wide
+ * path; 0 = the default, 2^18, and more than that is refused with BN_ERR_INVALID_ARGUMENT */
 int bn_set_products_chunk(bn_ctx* ctx, size_t terms);
+/* bn_pairing_batch_many and bn_pairing_batch_prepared_many calls of at most this many terms
+ * (the plain form: the terms of its products of at most 64 terms) take the wide path; 0 turns
+ * it off, any other value is accepted.  bn_set_latency_max(0) turns it off too: the path is
+ * built on that kernel.  Default: the measured crossover or
+ * $BN254MI_PRODUCTS_WIDE_MAX.  On a multi-device context it applies to every device. */
+int bn_set_products_wide_max(bn_ctx* ctx, size_t terms);
 
 /* *out = miller_loop_batch(&[(q[i], p[i])]) -- note the (G2, G1) order (lib.rs:625-633,
  * mod.rs:609-640).  No final exponentiation.  BN_ERR_TO_AFFINE if any point is zero. */
@@ -188,7 +204,9 @@ int bn_g2_precompute_many(bn_ctx* ctx, const bn_g2* q, size_t n, bn_fq2* out);
  *   BN_ERR_INVALID_ARGUMENT.  bn_g2_prepared_destroy waits for the work that uses the handle, then
  *   frees it; bn_ctx_destroy frees the handles still alive (they must not be used afterwards).
  *   The table is the handle's own memory: it is separate from the pairing workspace and not counted
- *   by bn_workspace_bytes.  Filling it uses the pairing workspace (bn_reserve(nq) pre-sizes that).
+ *   by bn_workspace_bytes.  Beside the table the handle keeps the nq points themselves (192 bytes
+ *   each; the products' wide path reads points, not lines): 18,985 bytes per point in all with the
+ *   zero flag.  Filling it uses the pairing workspace (bn_reserve(nq) pre-sizes that).
  * The _dev form takes device q and enqueues on `stream` without synchronizing (it allocates the
  * table, and may grow the workspace and then wait for earlier work, before it enqueues). */
 typedef struct bn_g2_prepared bn_g2_prepared;
@@ -241,11 +259,19 @@ int bn_miller_loop_prepared_many(bn_ctx* ctx, const bn_g1* p, const bn_g2_prepar
  *   is neither BN_QIDX_FRESH nor below the handle's count; a handle of another context or a
  *   destroyed one; a multi-device context (its device contexts work); any product of more than 64
  *   terms.  m == 0 returns BN_OK and touches nothing.
- * There is no alone path and bn_set_products_min does not apply: every product runs one per lane
- * pair of the packed kernel (k_miller_products_mapped), so a small call costs the time of one lane
- * pair's chain, as with the prepared calls above.  Callers who need small-batch
- * latency, or products of more than 64 terms, keep bn_pairing_batch.
- * Per launch set (cut at product boundaries, at most bn_set_products_chunk terms and 2^18
+ * Two paths; bn_set_products_min does not apply and there is no alone path.
+ * Wide: a call of at most bn_set_products_wide_max terms, one product included (and
+ * min(bn_set_latency_max, bn_set_products_chunk) at least 64, so that every product fits a launch
+ * set), gathers each set's G2 points in term order -- the next fresh point, or the handle's own
+ * copy of point qidx[i] -- and runs bn_pairing_batch_many's wide path over them: the latency
+ * kernel's Miller value per term, a 16-lane group per product, one final exponentiation per
+ * product.  It recomputes the fixed points' line steps, on 16 lanes per term, which at these sizes
+ * is far below the time of a lone lane pair's chain.  The gathered points (192 bytes per term of a
+ * set) grow on first use and are not counted by bn_workspace_bytes.
+ * Packed: every larger call runs one product per lane pair of the packed kernel
+ * (k_miller_products_mapped) and costs at least the time of one lane pair's chain.  Products of
+ * more than 64 terms keep bn_pairing_batch.
+ * Per packed launch set (cut at product boundaries, at most bn_set_products_chunk terms and 2^18
  * products): the line producers over the fresh terms only, k_prepared_expand over the prepared
  * ones (the table's lines scaled by the term's Jacobian P; no inversion), the products' loop, one
  * final exponentiation per product.  bn_reserve(n) guarantees that sets of at most n terms and n
@@ -581,6 +607,11 @@ int bn_set_latency_max(bn_ctx* ctx, size_t n);
  * the segmented latency path ms[0] k_prepare_wide, ms[1] k_miller_seg, ms[2] k_horner_wide.
  * *launches = launch sets measured */
 int bn_get_phase_times(bn_ctx* ctx, float ms[4], int* launches);
+/* the products that bn_pairing_batch_many and bn_pairing_batch_prepared_many (both forms of
+ * each) planned on each path since the last read: counts[0] wide, counts[1] packed, counts[2]
+ * alone; the read clears them.  Counted on the host when a call plans its work, so a call
+ * refused before that counts nothing.  On a multi-device context: the sum over its devices. */
+int bn_get_products_routes(bn_ctx* ctx, size_t counts[3]);
 
 /* ---- workspace ---- */
 /* device bytes the context holds for a batch of n pairings (allocated on first use) */

@@ -41,6 +41,14 @@ constexpr size_t kMsmG2MinDefault = 0;
 // crossover at 4 terms per product, rounded to a power of two;
 // $BN254MI_PRODUCTS_MIN or bn_set_products_min override
 constexpr size_t kProductsMinDefault = 8;
+// product calls of at most this many terms take the wide path (k_pairing_latency's Miller
+// values, a 16-lane group per product: capi_products.hip): the largest term
+// count of the sweep at which the path's median stayed below the other route's minimum in
+// all three shapes -- 8,192 terms: 2.65 against 5.18 ms at 4 fresh terms per product, 2.64
+// against 3.18 ms at 2 prepared terms, where 16,384 terms lose (4.98 against 3.94 ms)
+// (profiles/products_wide_sweep.jsonl).  $BN254MI_PRODUCTS_WIDE_MAX or
+// bn_set_products_wide_max override (0: never)
+constexpr size_t kProductsWideMaxDefault = 8192;
 
 size_t ws_bytes(size_t n) {
     return n * ((size_t)kCoeffFq * 9 * 4 + kPathLanes * (2 * 9 * 4 + 1) + (size_t)kFeSlots * kSlotWords * 4) + 64;
@@ -706,6 +714,15 @@ int bn::run_fe(bn_ctx* c, const uint32_t* f, size_t n, const uint8_t* flags, bn_
     return BN_OK;
 }
 
+int bn::latency_values(bn_ctx* c, const bn_g1* d_p, const bn_g2* d_q, size_t n, hipStream_t s, uint32_t** f) {
+    if (n > c->cap) return fail(c, BN_ERR_INTERNAL, "latency values exceed the workspace");
+    *f = slot_region(c, kRegionSeg);
+    if (n == 0) return BN_OK;
+    launch_latency(c, d_p, d_q, n, nullptr, *f, 0, s);
+    HIPCHK(c, hipGetLastError());
+    return BN_OK;
+}
+
 // the whole product of n device pairs into *d_out; the caller holds the workspace
 int bn::miller_product_dev(bn_ctx* c, const bn_g1* d_p, const bn_g2* d_q, size_t n, int mode, bn_gt* d_out,
                            hipStream_t s) {
@@ -875,6 +892,8 @@ int bn_ctx_create(int device, bn_ctx** out) {
     c->products_min = kProductsMinDefault;
     if (const char* e = getenv("BN254MI_PRODUCTS_MIN")) c->products_min = (size_t)strtoull(e, nullptr, 10);
     c->products_chunk = kChunk;
+    c->products_wide_max = kProductsWideMaxDefault;
+    if (const char* e = getenv("BN254MI_PRODUCTS_WIDE_MAX")) c->products_wide_max = (size_t)strtoull(e, nullptr, 10);
     if (const char* e = getenv("BN254MI_PRODUCTS_BLOCK")) {
         const int v = atoi(e);
         if (v == 128 || v == 256 || v == kPairBlock) c->products_block = (unsigned)v;
@@ -936,6 +955,7 @@ static void ctx_teardown(bn_ctx* c) {
     if (c->prod_map_h) (void)hipHostFree(c->prod_map_h);
     if (c->prod_map_d) (void)hipFree(c->prod_map_d);
     if (c->prod_fresh) (void)hipFree(c->prod_fresh);
+    if (c->prod_gq) (void)hipFree(c->prod_gq);
     if (c->many_words_event) (void)hipEventDestroy(c->many_words_event);
     if (c->many_words_h) (void)hipHostFree(c->many_words_h);
     for (void* p : {(void*)c->many_words_d, (void*)c->many_digits, (void*)c->many_table, (void*)c->many_parts})
@@ -954,6 +974,7 @@ static void ctx_teardown(bn_ctx* c) {
     for (bn_g2_prepared* h : c->prepared) {  // the handles still alive (the streams are drained)
         if (h->table) (void)hipFree(h->table);
         if (h->zero) (void)hipFree(h->zero);
+        if (h->points) (void)hipFree(h->points);
         delete h;
     }
     c->prepared.clear();

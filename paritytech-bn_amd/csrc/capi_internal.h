@@ -100,6 +100,10 @@ BN_HIDDEN int prepare(bn_ctx* c, const bn_g1* d_p, const bn_g2* d_q, size_t m, i
                       bool scaled_inputs = false);
 BN_HIDDEN int run_fe(bn_ctx* c, const uint32_t* f, size_t n, const uint8_t* flags, bn_gt* out, uint8_t* ok,
                      hipStream_t s);
+// the Miller values of n <= c->cap device pairs from one k_pairing_latency launch (mode 0:
+// a pair with a zero point gives one; no launch when n == 0) -> *f, split layout, stride n,
+// in a region of the workspace's slots that slot 0's n values do not reach
+BN_HIDDEN int latency_values(bn_ctx* c, const bn_g1* d_p, const bn_g2* d_q, size_t n, hipStream_t s, uint32_t** f);
 BN_HIDDEN int miller_product_dev(bn_ctx* c, const bn_g1* d_p, const bn_g2* d_q, size_t n, int mode, bn_gt* d_out,
                                  hipStream_t s);
 BN_HIDDEN int batch_host(bn_ctx* c, const bn_g1* p, const bn_g2* q, size_t n, int mode, bool do_fe, bn_gt* out);

@@ -1,6 +1,7 @@
 // capi_products.hip -- host side of the C ABI's pairing products and prepared G2 points:
 // bn_pairing_batch_many, the bn_g2_prepared handles with
-// bn_pairing_prepared_many (§6b), and bn_pairing_batch_prepared_many (§6c).  The plain and
+// bn_pairing_prepared_many (§6b), bn_pairing_batch_prepared_many (§6c), and the wide path of
+// both product calls for calls too small to fill the GPU (§6d).  The plain and
 // the prepared products share one plan (products_plan.h), one upload of its words, one
 // workspace rule, one launch tail and one host loop; they differ in the producers in front
 // of the products' loop and in the loop's kernel.
@@ -13,7 +14,13 @@
 using namespace bn;
 
 static ProductsLimits products_limits(const bn_ctx* c) {
-    return {kChunk, (size_t)kProductLaneMax, c->products_min, c->products_chunk};
+    return {kChunk, (size_t)kProductLaneMax, c->products_min, c->products_chunk, c->products_wide_max, c->latency_max};
+}
+// a call's plan, its products counted by route for bn_get_products_routes
+static ProductsPlan products_plan_counted(bn_ctx* c, const size_t* off, size_t m, const uint32_t* qidx) {
+    ProductsPlan plan = products_plan(products_limits(c), off, m, qidx);
+    for (const ProductsItem& it : plan.items) c->products_routes[it.wide ? 0 : it.packed ? 1 : 2] += it.j1 - it.j0;
+    return plan;
 }
 static int offsets_check(bn_ctx* c, const size_t* off, size_t m) {
     if (const char* why = products_offsets_refusal(off, m)) return fail(c, BN_ERR_INVALID_ARGUMENT, why);
@@ -25,7 +32,7 @@ static int products_reserve(bn_ctx* c, const size_t* off, const ProductsPlan& pl
     size_t need = 1;
     for (const ProductsItem& it : plan.items) {
         const size_t nt = off[it.j1] - off[it.j0];
-        need = std::max(need, it.packed ? std::max(nt, it.j1 - it.j0) : std::min(nt, kChunk));
+        need = std::max(need, it.alone() ? std::min(nt, kChunk) : std::max(nt, it.j1 - it.j0));
     }
     return reserve(c, need);
 }
@@ -43,6 +50,7 @@ static int products_upload(bn_ctx* c, const ProductsPlan& plan, const size_t* of
     RET_IF(grow_pinned_pair(c, &c->prod_off_h, &c->prod_off_d, &c->prod_off_cap, plan.off_words));
     RET_IF(grow_pinned_pair(c, &c->prod_map_h, &c->prod_map_d, &c->prod_map_cap, plan.map_words));
     products_fill(plan, off, qidx, compact_p, kMapRegionB, c->prod_off_h, c->prod_map_h);
+    if (qidx) products_wide_fill(plan, off, qidx, kMapRegionB, c->prod_map_h);
     HIPCHK(c, hipMemcpyAsync(c->prod_off_d, c->prod_off_h, plan.off_words * 4, hipMemcpyHostToDevice, s));
     if (plan.map_words)
         HIPCHK(c, hipMemcpyAsync(c->prod_map_d, c->prod_map_h, plan.map_words * 4, hipMemcpyHostToDevice, s));
@@ -91,8 +99,40 @@ static int prepared_set_dev(bn_ctx* c, const ProductsItem& st, const bn_g1* d_pf
                                                         c->slots);
     });
 }
+// one launch set of the wide path: the Miller values of the nt device pairs
+// from one k_pairing_latency launch (a pair with a zero point comes out as one), a 16-lane
+// group per product over them into slot 0, then the packed path's tail
+static int wide_set_dev(bn_ctx* c, const bn_g1* d_p, const bn_g2* d_q, size_t nt, const uint32_t* d_off, size_t mc,
+                        bn_gt* d_out, hipStream_t s) {
+    if (nt > c->cap || mc > c->cap) return fail(c, BN_ERR_INTERNAL, "launch set exceeds the workspace");
+    uint32_t* f = nullptr;
+    RET_IF(latency_values(c, d_p, d_q, nt, s, &f));
+    constexpr size_t kGroups = kBlock / 16;
+    k_fq12_products_wide<<<(unsigned)((mc + kGroups - 1) / kGroups), kBlock, 0, s>>>(f, nt, nt, d_off, mc, c->slots);
+    HIPCHK(c, hipGetLastError());
+    return run_fe(c, c->slots, mc, nullptr, d_out, nullptr, s);
+}
+// the same with prepared terms: the set's G2 points gathered in term order into prod_gq (the
+// caller has grown it) from its nf fresh points at d_qf and the handle's points; d_p in term order
+static int wide_prepared_set_dev(bn_ctx* c, const ProductsItem& st, const bn_g1* d_p, const bn_g2* d_qf,
+                                 const bn_g2_prepared* h, bn_gt* d_out, hipStream_t s) {
+    const size_t nt = st.nf + st.np;
+    if (nt > c->prod_gq_cap) return fail(c, BN_ERR_INTERNAL, "launch set exceeds the gathered points");
+    if (nt) {
+        launch_g2_gather(d_qf, st.nf, h->points, (uint32_t)h->nq, c->prod_map_d + st.map_at, nt, c->prod_gq, s);
+        HIPCHK(c, hipGetLastError());
+    }
+    return wide_set_dev(c, d_p, c->prod_gq, nt, c->prod_off_d + st.off_at, st.j1 - st.j0, d_out, s);
+}
+// prod_gq for the largest wide set of a plan of the prepared form
+static int wide_gather_reserve(bn_ctx* c, const ProductsPlan& plan) {
+    size_t ntmax = 0;
+    for (const ProductsItem& st : plan.items)
+        if (st.wide) ntmax = std::max(ntmax, st.nf + st.np);
+    return grow_dev(c, &c->prod_gq, &c->prod_gq_cap, ntmax, 4096, true);
+}
 // The host forms: every item in turn through the context's stage.  run_set stages a packed
-// item's pairs and its products' Gt, copies the pairs in and runs the set, leaving the
+// (or wide) item's pairs and its products' Gt, copies the pairs in and runs the set, leaving the
 // device rows in *d; an item alone (the plain form only: p and q are the caller's pairs)
 // goes through batch_host, which clears the outcome word for its own product.  The device
 // outcome is read after each item, BN_ERR_FE_ZERO reported at the end with every row written.
@@ -101,7 +141,7 @@ static int products_host_loop(bn_ctx* c, const ProductsPlan& plan, const bn_g1* 
                               bn_gt* out, RunSet&& run_set) {
     int zero = 0;
     for (const ProductsItem& it : plan.items) {
-        if (!it.packed) {
+        if (it.alone()) {
             const size_t lo = off[it.j0], nt = off[it.j1] - lo;
             if (nt == 0) {  // mod.rs:922-924
                 gt_one(out + it.j0);
@@ -138,14 +178,16 @@ int bn_pairing_batch_many_dev(bn_ctx* c, const bn_g1* d_p, const bn_g2* d_q, con
     if (m == 0) return BN_OK;
     RET_IF(products_check(c, d_p, d_q, offsets, m, d_out));
     const hipStream_t s = pick(c, stream);
-    const ProductsPlan plan = products_plan(products_limits(c), offsets, m, nullptr);
+    const ProductsPlan plan = products_plan_counted(c, offsets, m, nullptr);
     RET_IF(products_reserve(c, offsets, plan));
     RET_IF(ws_acquire(c, s));
     WsUse use{c, s};
     RET_IF(products_upload(c, plan, offsets, nullptr, false, s));
     for (const ProductsItem& it : plan.items) {
         const size_t lo = offsets[it.j0], nt = offsets[it.j1] - lo;
-        if (it.packed)
+        if (it.wide)
+            RET_IF(wide_set_dev(c, d_p + lo, d_q + lo, nt, c->prod_off_d + it.off_at, it.j1 - it.j0, d_out + it.j0, s));
+        else if (it.packed)
             RET_IF(products_set_dev(c, d_p + lo, d_q + lo, nt, c->prod_off_d + it.off_at, it.j1 - it.j0, d_out + it.j0, s));
         else if (nt == 0)  // mod.rs:922-924
             HIPCHK(c, hipMemcpyAsync(d_out + it.j0, &kGtOne, sizeof(bn_gt), hipMemcpyHostToDevice, s));
@@ -159,7 +201,7 @@ int bn_pairing_batch_many(bn_ctx* c, const bn_g1* p, const bn_g2* q, const size_
     CTX_GUARD_HOST(c);
     if (m == 0) return BN_OK;
     RET_IF(products_check(c, p, q, offsets, m, out));
-    const ProductsPlan plan = products_plan(products_limits(c), offsets, m, nullptr);
+    const ProductsPlan plan = products_plan_counted(c, offsets, m, nullptr);
     RET_IF(products_reserve(c, offsets, plan));
     RET_IF(products_upload(c, plan, offsets, nullptr, false, c->stream));
     return products_host_loop(c, plan, p, q, offsets, out, [&](const ProductsItem& it, bn_gt** d) -> int {
@@ -171,13 +213,40 @@ int bn_pairing_batch_many(bn_ctx* c, const bn_g1* p, const bn_g2* q, const size_
             HIPCHK(c, hipMemcpyAsync(at[1], q + lo, nt * sizeof(bn_g2), hipMemcpyHostToDevice, c->stream));
         }
         *d = (bn_gt*)at[2];
-        return products_set_dev(c, (bn_g1*)at[0], (bn_g2*)at[1], nt, c->prod_off_d + it.off_at, mc, *d, c->stream);
+        return (it.wide ? wide_set_dev : products_set_dev)(c, (bn_g1*)at[0], (bn_g2*)at[1], nt,
+                                                           c->prod_off_d + it.off_at, mc, *d, c->stream);
     });
 }
 int bn_set_products_min(bn_ctx* c, size_t m) {
     if (is_multi(c)) return for_each_sub(c, [&](bn_ctx* d) { return bn_set_products_min(d, m); });
     CTX_GUARD(c);
     c->products_min = m;
+    return BN_OK;
+}
+int bn_set_products_wide_max(bn_ctx* c, size_t terms) {
+    if (is_multi(c)) return for_each_sub(c, [&](bn_ctx* d) { return bn_set_products_wide_max(d, terms); });
+    CTX_GUARD(c);
+    c->products_wide_max = terms;
+    return BN_OK;
+}
+int bn_get_products_routes(bn_ctx* c, size_t counts[3]) {
+    if (!c || !counts) return BN_ERR_INVALID_ARGUMENT;
+    if (is_multi(c)) {
+        size_t sum[3] = {0, 0, 0};
+        RET_IF(for_each_sub(c, [&](bn_ctx* d) -> int {
+            size_t one[3];
+            RET_IF(bn_get_products_routes(d, one));
+            for (int k = 0; k < 3; ++k) sum[k] += one[k];
+            return BN_OK;
+        }));
+        for (int k = 0; k < 3; ++k) counts[k] = sum[k];
+        return BN_OK;
+    }
+    CTX_GUARD(c);
+    for (int k = 0; k < 3; ++k) {
+        counts[k] = c->products_routes[k];
+        c->products_routes[k] = 0;
+    }
     return BN_OK;
 }
 int bn_set_products_chunk(bn_ctx* c, size_t terms) {
@@ -198,6 +267,7 @@ static int g2_prepare_fill(bn_ctx* c, bn_g2_prepared* h, const bn_g2* q, bool q_
     const size_t nq = h->nq;
     HIPCHK(c, hipMalloc(&h->table, nq * (size_t)kPreparedWords * 4));
     HIPCHK(c, hipMalloc(&h->zero, nq));
+    HIPCHK(c, hipMalloc(&h->points, nq * sizeof(bn_g2)));
     const size_t mmax = nq < kChunk ? nq : kChunk;
     RET_IF(reserve(c, mmax));
     void* at[2];
@@ -209,6 +279,7 @@ static int g2_prepare_fill(bn_ctx* c, bn_g2_prepared* h, const bn_g2* q, bool q_
             HIPCHK(c, hipMemcpyAsync(at[1], q + off, m * sizeof(bn_g2), hipMemcpyHostToDevice, s));
             dq = (const bn_g2*)at[1];
         }
+        HIPCHK(c, hipMemcpyAsync(h->points + off, dq, m * sizeof(bn_g2), hipMemcpyDeviceToDevice, s));
         k_g1_fill_one<<<grid_for(m), kBlock, 0, s>>>(dp, m);
         RET_IF(prepare(c, dp, dq, m, 0, s, 0));
         k_prepared_repack<<<grid_for(kPathLanes * m), kBlock, 0, s>>>(c->coeffs, c->flags, m,
@@ -227,6 +298,7 @@ static int g2_prepare(bn_ctx* c, const bn_g2* q, bool q_dev, size_t nq, bn_g2_pr
         (void)hipStreamSynchronize(s);  // nothing queued may still write the table
         if (h->table) (void)hipFree(h->table);
         if (h->zero) (void)hipFree(h->zero);
+        if (h->points) (void)hipFree(h->points);
         delete h;
         return rc;
     }
@@ -276,6 +348,7 @@ int bn_g2_prepared_destroy(bn_ctx* c, bn_g2_prepared* h) {
     c->prepared.erase(std::find(c->prepared.begin(), c->prepared.end(), h));
     (void)hipFree(h->table);
     (void)hipFree(h->zero);
+    (void)hipFree(h->points);
     delete h;
     return BN_OK;
 }
@@ -368,6 +441,7 @@ static int prepared_products_check(bn_ctx* c, const void* p, const void* q, cons
 }
 // The _dev form gathers a set's fresh G1 points into prod_fresh (grown on first use) in
 // front of the producers; the prepared terms read the caller's points in place.
+// A wide set reads every G1 point in place and gathers its G2 points into prod_gq instead.
 int bn_pairing_batch_prepared_many_dev(bn_ctx* c, const bn_g1* d_p, const bn_g2* d_q, const bn_g2_prepared* h,
                                        const uint32_t* qidx, const size_t* offsets, size_t m, bn_gt* d_out,
                                        void* stream) {
@@ -375,16 +449,22 @@ int bn_pairing_batch_prepared_many_dev(bn_ctx* c, const bn_g1* d_p, const bn_g2*
     if (m == 0) return BN_OK;
     RET_IF(prepared_products_check(c, d_p, d_q, h, qidx, offsets, m, d_out));
     const hipStream_t s = pick(c, stream);
-    const ProductsPlan plan = products_plan(products_limits(c), offsets, m, qidx);
+    const ProductsPlan plan = products_plan_counted(c, offsets, m, qidx);
     RET_IF(products_reserve(c, offsets, plan));
     size_t nfmax = 0;
-    for (const ProductsItem& st : plan.items) nfmax = std::max(nfmax, st.nf);
+    for (const ProductsItem& st : plan.items)
+        if (st.packed) nfmax = std::max(nfmax, st.nf);
     RET_IF(grow_dev(c, &c->prod_fresh, &c->prod_fresh_cap, nfmax, 4096, true));
+    RET_IF(wide_gather_reserve(c, plan));
     RET_IF(ws_acquire(c, s));
     WsUse use{c, s};
     RET_IF(products_upload(c, plan, offsets, qidx, false, s));
     for (const ProductsItem& st : plan.items) {
         const size_t lo = offsets[st.j0];
+        if (st.wide) {  // p is read in term order, in place
+            RET_IF(wide_prepared_set_dev(c, st, d_p + lo, d_q + st.f0, h, d_out + st.j0, s));
+            continue;
+        }
         if (st.nf) {
             launch_g1_gather(d_p + lo, c->prod_map_d + st.map_at + st.nf + 3 * st.np, st.nf, c->prod_fresh, s);
             HIPCHK(c, hipGetLastError());
@@ -393,28 +473,36 @@ int bn_pairing_batch_prepared_many_dev(bn_ctx* c, const bn_g1* d_p, const bn_g2*
     }
     return BN_OK;
 }
-// The host form stages a set's G1 points compacted, fresh first, then its fresh G2 points.
+// The host form stages a set's G1 points compacted, fresh first, then its fresh G2 points
+// (a wide set's G1 points in term order: its G2 points are gathered to match).
 int bn_pairing_batch_prepared_many(bn_ctx* c, const bn_g1* p, const bn_g2* q, const bn_g2_prepared* h,
                                    const uint32_t* qidx, const size_t* offsets, size_t m, bn_gt* out) {
     CTX_GUARD_HOST(c);
     if (m == 0) return BN_OK;
     RET_IF(prepared_products_check(c, p, q, h, qidx, offsets, m, out));
-    const ProductsPlan plan = products_plan(products_limits(c), offsets, m, qidx);
+    const ProductsPlan plan = products_plan_counted(c, offsets, m, qidx);
     std::vector<bn_g1> hp;
     int rc = products_reserve(c, offsets, plan);
+    if (!rc) rc = wide_gather_reserve(c, plan);
     if (!rc) rc = products_upload(c, plan, offsets, qidx, true, c->stream);
     if (!rc) rc = products_host_loop(c, plan, p, q, offsets, out, [&](const ProductsItem& st, bn_gt** d) -> int {
         const size_t lo = offsets[st.j0], nt = st.nf + st.np, mc = st.j1 - st.j0;
         void* at[3];
         RET_IF(stage_regions(c, {nt * sizeof(bn_g1), st.nf * sizeof(bn_g2), mc * sizeof(bn_gt)}, at));
         bn_g1* dp = (bn_g1*)at[0];
+        *d = (bn_gt*)at[2];
+        if (st.wide) {  // p in term order, the compacted fresh q, the same gather as the _dev form
+            if (nt) HIPCHK(c, hipMemcpyAsync(dp, p + lo, nt * sizeof(bn_g1), hipMemcpyHostToDevice, c->stream));
+            if (st.nf)
+                HIPCHK(c, hipMemcpyAsync(at[1], q + st.f0, st.nf * sizeof(bn_g2), hipMemcpyHostToDevice, c->stream));
+            return wide_prepared_set_dev(c, st, dp, (bn_g2*)at[1], h, *d, c->stream);
+        }
         hp.resize(nt);  // (the previous set's copy has completed: check_err synchronizes)
         size_t kf = 0, kp = st.nf;
         for (size_t t = 0; t < nt; ++t) hp[qidx[lo + t] == BN_QIDX_FRESH ? kf++ : kp++] = p[lo + t];
         if (nt) HIPCHK(c, hipMemcpyAsync(dp, hp.data(), nt * sizeof(bn_g1), hipMemcpyHostToDevice, c->stream));
         if (st.nf)
             HIPCHK(c, hipMemcpyAsync(at[1], q + st.f0, st.nf * sizeof(bn_g2), hipMemcpyHostToDevice, c->stream));
-        *d = (bn_gt*)at[2];
         return prepared_set_dev(c, st, dp, (bn_g2*)at[1], dp, h, *d, c->stream);
     });
     (void)hipStreamSynchronize(c->stream);  // an early error may leave copies queued

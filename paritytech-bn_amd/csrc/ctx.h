@@ -34,13 +34,15 @@ struct MsmGroupWs {
 };
 
 // bn_g2_prepare's handle: the 87 line coefficients of each of nq affine G2 points
-// (kernels.h kPreparedWords words per point) and a zero flag per point, device-resident,
+// (kernels.h kPreparedWords words per point), a zero flag per point and the points as they
+// were given (for the products' wide path, whose kernel takes points), device-resident,
 // owned by the single-device context whose `prepared` list holds it (which frees the
 // handles still alive when destroyed).
 struct bn_g2_prepared {
     size_t nq = 0;
     uint32_t* table = nullptr;
     uint8_t* zero = nullptr;  // zero[j] != 0: q[j] was G2::zero(), its table row is never used
+    bn_g2* points = nullptr;  // q[0 .. nq)
 };
 
 // bn_g1_bases_prepare's handle: the window table of k G1 bases at width c (msm_fixed.h:
@@ -162,6 +164,15 @@ struct bn_ctx {
     size_t prod_map_cap = 0;  // words
     bn_g1* prod_fresh = nullptr;
     size_t prod_fresh_cap = 0;  // points
+    // The wide path of both product calls: calls of at most products_wide_max
+    // terms run k_pairing_latency's Miller values and a 16-lane group per product (0: never).
+    // prod_gq: the G2 points of a wide set of the prepared form in term order (k_g2_gather),
+    // grown on first use.  products_routes: the products planned as {wide, packed, alone}
+    // since bn_get_products_routes last read them (host counters).
+    size_t products_wide_max = 0;
+    bn_g2* prod_gq = nullptr;
+    size_t prod_gq_cap = 0;  // points
+    size_t products_routes[3] = {0, 0, 0};
     // the bn_g2_prepared handles this context made and has not destroyed yet (capi_products.hip).
     // Their tables are their own memory, not part of the workspace; the calls that read
     // them order themselves through ws_event like every workspace user, which is what

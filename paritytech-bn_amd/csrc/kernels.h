@@ -523,6 +523,11 @@ void launch_prepared_expand(const bn_g1* p, const uint32_t* pterm, const uint32_
                             hipStream_t s);
 // k_g1_gather: out[i] = p[term[i]], i < n
 void launch_g1_gather(const bn_g1* p, const uint32_t* term, size_t n, bn_g1* out, hipStream_t s);
+// k_g2_gather: out[t] = q[map[t]] (one of the nf fresh points) or, with kMapRegionB set,
+// point map[t] & 0x7fffffff of the nq >= 1 in hq, t < n.  The host has checked every index:
+// a table index >= nq is still clamped to 0 and a fresh index >= nf gives the zero image
+void launch_g2_gather(const bn_g2* q, size_t nf, const bn_g2* hq, uint32_t nq, const uint32_t* map, size_t n,
+                      bn_g2* out, hipStream_t s);
 __global__ void __launch_bounds__(kBlock) k_fe_out(const uint32_t* __restrict__ slots, size_t n, int out_slot, const uint8_t* __restrict__ flags,
                          bn_gt* __restrict__ out, uint8_t* __restrict__ ok, int* __restrict__ err);
 // kernels_wide.hip (fq12_wide.h): final exponentiation and product reduction on 16-lane groups
@@ -532,6 +537,12 @@ __global__ void __launch_bounds__(kBlock) k_fe_wide(const uint32_t* __restrict__
 __global__ void __launch_bounds__(kBlock) k_fq12_reduce_wide(const uint32_t* __restrict__ in, size_t in_stride,
                                                              SetSpan sets, uint32_t* __restrict__ out,
                                                              size_t out_stride, size_t out_base, size_t out_set, int per_group);
+// kernels_products_wide.hip: product j < m = the elements off[j] .. off[j + 1] - 1 of the nt in `in`
+// (split layout, stride in_stride), a 16-lane group per product -> element j of `out`
+// (stride m); kBlock / 16 products per block
+__global__ void __launch_bounds__(kBlock) k_fq12_products_wide(const uint32_t* __restrict__ in, size_t in_stride,
+                                                               size_t nt, const uint32_t* __restrict__ off, size_t m,
+                                                               uint32_t* __restrict__ out);
 // kernels_tail.hip: k_horner_tree's recombination + final exponentiation of ONE
 // product, the final exponentiation's last chunk digit-sliced on the whole block (fq12_ds.h)
 constexpr int kTailBlock = 256;

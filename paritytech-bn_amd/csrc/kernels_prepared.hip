@@ -193,6 +193,27 @@ __global__ void __launch_bounds__(kBlock) k_g1_gather(const bn_g1* __restrict__ 
     reinterpret_cast<uint4*>(out + i)[part] = reinterpret_cast<const uint4*>(p + term[i])[part];
 }
 
+// out[t] = the G2 point of term t < n of a wide launch set (bn_pairing_batch_prepared_many's wide
+// path), for k_pairing_latency: fresh point map[t] of the set's nf at q, or,
+// with kMapRegionB set, point map[t] & 0x7fffffff of the handle's nq at hq.  One thread per
+// 16-byte twelfth of a point.  The host has checked every index; a table index >= nq is still
+// clamped to 0 and a fresh index >= nf gives the zero image, before any address is formed.
+__global__ void __launch_bounds__(kBlock) k_g2_gather(const bn_g2* __restrict__ q, size_t nf,
+                                                      const bn_g2* __restrict__ hq, uint32_t nq,
+                                                      const uint32_t* __restrict__ map, size_t n,
+                                                      bn_g2* __restrict__ out) {
+    constexpr size_t kParts = sizeof(bn_g2) / sizeof(uint4);
+    const size_t t = lane_id(), i = t / kParts, part = t % kParts;
+    if (i >= n) return;
+    const uint32_t w = map[i], k = w & ~kMapRegionB;
+    uint4 v = make_uint4(0, 0, 0, 0);
+    if (w & kMapRegionB)
+        v = reinterpret_cast<const uint4*>(hq + (k < nq ? k : 0u))[part];
+    else if (k < nf)
+        v = reinterpret_cast<const uint4*>(q + k)[part];
+    reinterpret_cast<uint4*>(out + i)[part] = v;
+}
+
 void launch_prepared_expand(const bn_g1* p, const uint32_t* pterm, const uint32_t* pidx, const uint32_t* table,
                             const uint8_t* qzero, uint32_t nq, size_t np, uint32_t* coeffs, uint8_t* flags,
                             hipStream_t s) {
@@ -201,6 +222,10 @@ void launch_prepared_expand(const bn_g1* p, const uint32_t* pterm, const uint32_
 }
 void launch_g1_gather(const bn_g1* p, const uint32_t* term, size_t n, bn_g1* out, hipStream_t s) {
     k_g1_gather<<<grid_for(n * (sizeof(bn_g1) / sizeof(uint4))), kBlock, 0, s>>>(p, term, n, out);
+}
+void launch_g2_gather(const bn_g2* q, size_t nf, const bn_g2* hq, uint32_t nq, const uint32_t* map, size_t n,
+                      bn_g2* out, hipStream_t s) {
+    k_g2_gather<<<grid_for(n * (sizeof(bn_g2) / sizeof(uint4))), kBlock, 0, s>>>(q, nf, hq, nq, map, n, out);
 }
 
 void launch_pairing_prepared(bool final_exp, const bn_g1* p, const uint32_t* table, const uint8_t* qzero, uint32_t nq,

@@ -46,6 +46,7 @@ EXPORTS = [
     "bn_g1_msm_many", "bn_g1_msm_many_dev", "bn_set_msm_many_window", "bn_set_msm_many_unit", "bn_set_msm_many_max",
     "bn_set_msm_many_chunk", "bn_g1_msm_many_reserve",
     "bn_pairing_batch_many", "bn_pairing_batch_many_dev", "bn_set_products_min", "bn_set_products_chunk",
+    "bn_set_products_wide_max", "bn_get_products_routes",
     "bn_g2_prepare", "bn_g2_prepare_dev", "bn_g2_prepared_count", "bn_g2_prepared_destroy",
     "bn_pairing_prepared_many", "bn_pairing_prepared_many_dev", "bn_miller_loop_prepared_many",
     "bn_pairing_batch_prepared_many", "bn_pairing_batch_prepared_many_dev",
@@ -162,6 +163,8 @@ def load():
         "bn_pairing_batch_many_dev": ([vp, vp, vp, vp, sz, vp, vp], i),
         "bn_set_products_min": ([vp, sz], i),
         "bn_set_products_chunk": ([vp, sz], i),
+        "bn_set_products_wide_max": ([vp, sz], i),
+        "bn_get_products_routes": ([vp, vp], i),
         "bn_g2_prepare": ([vp, vp, sz, ctypes.POINTER(vp)], i),
         "bn_g2_prepare_dev": ([vp, vp, sz, ctypes.POINTER(vp), vp], i),
         "bn_g2_prepared_count": ([vp], sz),
@@ -721,6 +724,23 @@ class Context:
         """Terms per launch set of the packed path; 0: the default (2^18), which is also the
         largest value accepted."""
         self._check(self._L.bn_set_products_chunk(self._h, terms))
+
+    def set_products_wide_max(self, terms):
+        """Product calls (pairing_batch_many, pairing_batch_prepared_many) of at most `terms`
+        terms take the wide path: the latency kernel's Miller value per term, a 16-lane group
+        per product.  0 turns it off.  A negative or non-integer value raises ValueError."""
+        if isinstance(terms, bool) or not isinstance(terms, (int, np.integer)):
+            raise ValueError("terms must be an integer")
+        if terms < 0 or terms >= 1 << 64:
+            raise ValueError("terms must be within 0 .. 2^64 - 1")
+        self._check(self._L.bn_set_products_wide_max(self._h, int(terms)))
+
+    def products_routes(self):
+        """(wide, packed, alone): the products the product calls planned on each path since
+        the last read, which clears the counts."""
+        counts = np.zeros(3, np.uintp)
+        self._check(self._L.bn_get_products_routes(self._h, _ptr(counts)))
+        return tuple(int(v) for v in counts)
 
     def set_fe_wide_max(self, n):
         """Batches of at most n elements use the 16-lane final exponentiation (latency path)."""

@@ -25,7 +25,7 @@ os.environ.setdefault("BN254MI_LIB", os.path.join(ROOT, "paritytech-bn_amd", "li
 
 from substrate_bn import _native, synth  # noqa: E402
 
-TUS = ["pairing", "prepared", "fe", "wide", "latency_w2", "group", "msm", "msm_g2", "gtpow", "codec", "util", "reduce", "tail"]  # every unit (Makefile dbg)
+TUS = ["pairing", "prepared", "fe", "wide", "latency_w2", "group", "msm", "msm_g2", "gtpow", "codec", "util", "reduce", "products_wide", "tail"]  # every unit (Makefile dbg)
 
 
 def counters(L):
@@ -66,6 +66,8 @@ def main():
     ctx.pairing_prepared_many(p, prepared, idx)
     ctx.miller_loop_prepared_many(p[:256], prepared, idx[:256])
     ctx.g2_prepared_destroy(prepared)
+    # the products' wide path (k_pairing_latency's values, k_fq12_products_wide): 256 products of 4 terms
+    ctx.pairing_batch_many(p[:1024], q[:1024], np.arange(0, 1025, 4))
     ctx.gt_pow_many(gt, synth.fr_images(n, 3, lo=0))
     for op in ("mul", "sqr", "inv", "cyc_sqr", "exp_by_neg_z", "frob1", "frob2", "frob3"):
         ctx.fq12_op_many(op, gt[:256], gt[256:512] if op == "mul" else None)

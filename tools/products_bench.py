@@ -22,7 +22,18 @@ ways in the same alternating rounds:
   p  bn_pairing_batch_prepared_many_dev (the fresh terms' G2 points compacted)
   a  bn_pairing_batch_many_dev on the same terms with every G2 point written out
 The rows of the two must be equal before a shape is timed, else the script exits non-zero.
-One JSON line per shape with both forms and p's time over a's."""
+One JSON line per shape with both forms and p's time over a's.
+
+--wide: the wide path against the route the call takes without it, for three
+kinds of product -- "fresh4" (k = 4, bn_pairing_batch_many_dev), "groth16" (k = 4, one fresh
+term and three prepared) and "prepared2" (k = 2, both prepared; both through
+bn_pairing_batch_prepared_many_dev) -- over --wide-ms products.  Per shape one warm-up of both
+routes, the rows of the two compared (a difference exits non-zero), then --reps alternating
+rounds: "wide" with bn_set_products_wide_max above the call, "base" with 0, every other
+setting at its default.  One JSON line per shape with median / min / max of both, the routes
+each planned (bn_get_products_routes) and wide_wins = wide's median below base's minimum;
+then per kind the crossover -- the largest term count up to which wide_wins held at every
+shape of the sweep -- and the smallest of the three, the default the sweep supports."""
 import argparse
 import json
 import os
@@ -48,6 +59,9 @@ def main():
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     ap.add_argument("--prepared", type=int, default=None, metavar="F",
                     help="time the prepared-terms call: the first F terms of each product are fresh")
+    ap.add_argument("--wide", action="store_true", help="time the wide path against the route without it")
+    ap.add_argument("--wide-ms", default="1,2,8,64,256,1024,2048,4096,8192")
+    ap.add_argument("--wide-kinds", default="fresh4,groth16,prepared2")
     args = ap.parse_args()
     import torch
 
@@ -63,11 +77,13 @@ def main():
     forms = args.forms.split(",")
     ks = [int(v) for v in args.ks.split(",")]
     ms = [int(v) for v in args.ms.split(",")]
+    if args.wide:
+        ks, ms = [4], [int(v) for v in args.wide_ms.split(",")]
     shapes = [(k, m) for k in ks for m in ms if m * k <= NMAX]
     nmax = max(m * k for k, m in shapes)
     dev = torch.device("cuda", 0)
     ctx = Context(0)
-    if "a" in forms:
+    if "a" in forms and not args.wide:
         ctx.set_products_min(0)
     stream = torch.cuda.Stream(dev)
     sh = stream.cuda_stream
@@ -120,6 +136,9 @@ def main():
     def stats(ts):
         return {"median_ms": round(statistics.median(ts), 4), "min_ms": round(min(ts), 4), "max_ms": round(max(ts), 4)}
 
+    if args.wide:
+        wide_sweep(args, ctx, torch, dev, sh, ms, P, Q, timed, stats, emit)
+        return
     if args.prepared is not None:
         prepared_sweep(args, ctx, torch, dev, sh, shapes, P, Q, timed, stats, emit)
         return
@@ -211,6 +230,65 @@ def prepared_sweep(args, ctx, torch, dev, sh, shapes, P, Q, timed, stats, emit):
         emit(rec)
     ctx.dev_status()
     ctx.g2_prepared_destroy(handle)
+
+
+def wide_sweep(args, ctx, torch, dev, sh, ms, P, Q, timed, stats, emit):
+    """The --wide sweep: the handle's points are Q[0 .. 2]; a product's fresh terms take Q from
+    row 3 on (compacted for the prepared call)."""
+    nq, big = 3, 1 << 30
+    kinds = {"fresh4": (4, 4), "groth16": (4, 1), "prepared2": (2, 0)}  # k, fresh terms per product
+    handle = ctx.g2_prepare_dev(Q.data_ptr(), nq, sh)
+    out_w = torch.zeros((max(ms), 48), dtype=torch.int64, device=dev)
+    out_b = torch.zeros_like(out_w)
+    cross = {}
+    for kind in args.wide_kinds.split(","):
+        k, f = kinds[kind]
+        wins = True
+        cross[kind] = 0
+        for m in ms:
+            n = m * k
+            off = np.arange(m + 1, dtype=np.uintp) * k
+            qidx = np.where(np.arange(n) % k < f, 0xFFFFFFFF, (np.arange(n) % k - f) % nq).astype(np.uint32)
+            Qf = Q[nq:]                                        # contiguous rows: the compacted fresh points
+
+            def call(out):
+                if kind == "fresh4":
+                    ctx.pairing_batch_many_dev(P.data_ptr(), Q.data_ptr(), off, out.data_ptr(), sh)
+                else:
+                    ctx.pairing_batch_prepared_many_dev(P.data_ptr(), Qf.data_ptr(), handle, qidx, off,
+                                                        out.data_ptr(), sh)
+
+            def run(route):
+                ctx.set_products_wide_max(big if route == "wide" else 0)
+                ctx.products_routes()
+                ms_ = timed(lambda: call(out_w if route == "wide" else out_b))
+                return ms_, ctx.products_routes()
+
+            routes = {r: run(r)[1] for r in ("wide", "base")}  # warm-up (allocates)
+            ctx.dev_status()
+            if not np.array_equal(out_w[:m].cpu().numpy(), out_b[:m].cpu().numpy()):
+                print("MISMATCH at %s m=%d: the wide rows differ from the base route's" % (kind, m), file=sys.stderr)
+                sys.exit(1)
+            times = {"wide": [], "base": []}
+            for _ in range(args.reps):
+                for r in ("wide", "base"):  # alternating
+                    times[r].append(run(r)[0])
+            rec = {"kind": kind, "k": k, "fresh": f, "m": m, "n": n, "reps": args.reps,
+                   "wide": stats(times["wide"]), "base": stats(times["base"]),
+                   "routes_wide": routes["wide"], "routes_base": routes["base"]}
+            rec["wide_wins"] = rec["wide"]["median_ms"] < rec["base"]["min_ms"]
+            same_route = routes["wide"] == routes["base"]      # (one fresh product: alone either way)
+            if not same_route:
+                wins = wins and rec["wide_wins"]
+                if wins:
+                    cross[kind] = n
+            emit(rec)
+    ctx.dev_status()
+    ctx.set_products_wide_max(0)
+    ctx.g2_prepared_destroy(handle)
+    emit({"crossover_terms": cross, "supported_default": min(cross.values()),
+          "note": "per kind the largest term count up to which the wide route's median stayed below the base "
+                  "route's minimum at every shape of the sweep; the default is the smallest of them"})
 
 
 if __name__ == "__main__":
