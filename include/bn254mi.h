@@ -453,6 +453,58 @@ int bn_set_msm_many_chunk(bn_ctx* ctx, size_t terms);
  * settings (else grown on first use) */
 int bn_g1_msm_many_reserve(bn_ctx* ctx, size_t terms, size_t segments);
 
+/* ---- one large G1 MSM over a FIXED basis (shifted-base table, mixed additions) ----
+ * The caller who runs 2^16 - 2^20-term MSMs over the same bases in every call: a KZG / PLONK
+ * commitment over an SRS, a Groth16 prover's queries over its proving key.  A bn_g1_basis handle holds,
+ * on the device, for every base b and every window w of the signed c-bit recoding (W(c) = 254 / c + 1
+ * windows, as the single MSM), the ONE affine point 2^(c w) bases[b]: 64 bytes each, and one zero flag
+ * per base -- W(c) points per base (1 KiB at c = 16, 1 GiB for 2^20 bases), where a bn_g1_prepared holds
+ * 2^(c-1) W(c).  An MSM is then the bucket method with every digit a lookup of a point that already
+ * carries its window's weight: mixed additions into the buckets, the windows' buckets added together,
+ * one reduction, and no doubling chain.
+ *   c: the window width, 2 .. 16, fixed at prepare time; 0 takes the default from nbases (the basis
+ *   form's own measured table; the handle's window call reports the width used).  bn_set_msm_window and
+ *   bn_set_msm_min do not apply to these calls; bn_set_msm_run_max does, with the same default rule.
+ *   1 <= nbases <= 2^26, and nbases W(c) must not exceed 2^31 - 1.  The table-bytes call is host
+ *   arithmetic (no device needed): the device bytes of that table, 0 for arguments the prepare call
+ *   refuses.
+ *   Refused with BN_ERR_INVALID_ARGUMENT before anything is read, *out untouched: a NULL bases or out,
+ *   an nbases or c outside those limits, a multi-device context (a device context from bn_ctx_device
+ *   works).
+ *   bases[b] may be any Jacobian image (z != one; z == 0 with arbitrary x, y: such a base contributes
+ *   nothing); points are assumed to be on the curve, as everywhere in the group API.
+ *   The handle belongs to the context that made it, exactly as a bn_g1_prepared: any other context
+ *   refuses it; the destroy call waits for the work that reads it, then frees it; bn_ctx_destroy frees
+ *   the handles still alive.  The table is the handle's own memory, not counted by bn_workspace_bytes.
+ *   Preparing costs about c W(c) doublings and W(c) inversions per base, once: 6.3 ms for 2^18 bases,
+ *   20.5 ms for 2^20.
+ * The _dev form takes device bases and enqueues on `stream` without synchronizing (it allocates the
+ * table first). */
+typedef struct bn_g1_basis bn_g1_basis;
+size_t bn_g1_basis_table_bytes(size_t nbases, int c);
+int bn_g1_basis_prepare(bn_ctx* ctx, const bn_g1* bases, size_t nbases, int c, bn_g1_basis** out);
+int bn_g1_basis_prepare_dev(bn_ctx* ctx, const bn_g1* d_bases, size_t nbases, int c, bn_g1_basis** out, void* stream);
+size_t bn_g1_basis_count(const bn_g1_basis* basis);
+int bn_g1_basis_window(const bn_g1_basis* basis);
+int bn_g1_basis_destroy(bn_ctx* ctx, bn_g1_basis* basis);
+/* *out = (sum over i < n of bases[i] * k[i]).normalize() over the FIRST n <= nbases bases of the handle
+ * (a commitment to a polynomial shorter than the SRS): bit for bit the 96 bytes the single MSM returns
+ * on the same bases and scalars, (x, y, one), and (0, one, 0) for a zero sum or n == 0.  The group law
+ * is exact and the normalized image unique: no width and no run cap changes a result.
+ *   Refused with BN_ERR_INVALID_ARGUMENT: a NULL out; a NULL k with n > 0; n above the handle's count;
+ *   a NULL handle, one of another context or a destroyed one; a multi-device context.  No outcome
+ *   depends on the data: the _dev form has no status to report.
+ * The integer buffers and bucket arrays are the G1 MSM workspace, shared with the single MSM and
+ * ordered like it; the reserve call sizes them for n terms at the handle's width and the run cap in
+ * force (else grown on first use).  The _dev form enqueues on `stream` without synchronizing; it may
+ * allocate (and then waits for earlier work) on first use at a larger size.
+ * Which form: with the bases fixed, this one.  Measured against the single MSM on the same terms it is
+ * faster at every size from 1 to 2^20 terms (2.5 against 3.9 ms at 2^18, 6.2 against 8.0 at 2^20) and on
+ * the skewed scalar patterns, each time by more than the run-to-run spread. */
+int bn_g1_msm_basis(bn_ctx* ctx, const bn_g1_basis* basis, const bn_fr* k, size_t n, bn_g1* out);
+int bn_g1_msm_basis_dev(bn_ctx* ctx, const bn_g1_basis* basis, const bn_fr* d_k, size_t n, bn_g1* d_out, void* stream);
+int bn_g1_msm_basis_reserve(bn_ctx* ctx, const bn_g1_basis* basis, size_t n);
+
 /* ---- G2 multi-scalar multiplication (bucket method on the two-lane layout) ---- */
 
 /* The same contract over G2: *out = (sum over i < n of p[i] * k[i]).normalize(), the image (x, y, one)

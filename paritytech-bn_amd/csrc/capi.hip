@@ -984,6 +984,12 @@ static void ctx_teardown(bn_ctx* c) {
         delete h;
     }
     c->g1_prepared.clear();
+    for (bn_g1_basis* h : c->g1_basis) {
+        if (h->table) (void)hipFree(h->table);
+        if (h->zero) (void)hipFree(h->zero);
+        delete h;
+    }
+    c->g1_basis.clear();
     for (auto& ev : c->ev_marks)
         for (auto e : ev) c->ev_pool.push_back(e);
     for (auto e : c->ev_pool)

@@ -3,11 +3,13 @@
 // and the small path return the same image: the group law is exact and the result is
 // normalized.  The host sequence is one template over the point type; MsmGroup<P>
 // names the group's kernels, settings and buffers.  Behind it, the bn_g1_prepared handles
-// and bn_g1_msm_prepared_many (kernels_msm_fixed.hip; §8c), and bn_g1_msm_many
-// (kernels_msm_many.hip, msm_many_plan.h; §8d).
+// and bn_g1_msm_prepared_many (kernels_msm_fixed.hip; §8c), bn_g1_msm_many
+// (kernels_msm_many.hip, msm_many_plan.h; §8d), and the bn_g1_basis handles and
+// bn_g1_msm_basis (kernels_msm_basis.hip; §8e).
 #include <type_traits>
 
 #include "capi_internal.h"
+#include "msm_basis.h"
 #include "msm_fixed.h"
 #include "msm_many.h"
 #include "msm_many_plan.h"
@@ -88,25 +90,30 @@ struct MsmPlan {
     int levels;
     size_t slots_a, slots_b;
 };
-template <class P>
-static MsmPlan msm_plan(bn_ctx* c, size_t n) {
-    const MsmGroupWs<P>& g = MsmGroup<P>::ws(c);
+// the bucket path's plan of n terms at width cw under the run-cap setting run_max
+static MsmPlan msm_plan_at(size_t run_max, size_t n, int cw) {
     MsmPlan m{};
-    m.small = n < g.min;
-    m.c = g.window ? g.window : MsmGroup<P>::auto_window(n);
+    m.c = cw;
     m.nwin = (uint32_t)msm_windows(m.c);
     m.nkeys = msm_num_keys(m.c);
     m.nseg = (msm_buckets(m.c) + kMsmSegment - 1) / kMsmSegment;
     m.nent = n * m.nwin;
-    m.L = g.run_max == BN_MSM_RUN_UNSPLIT ? kMsmRunUnsplit
-          : g.run_max                     ? (uint32_t)g.run_max
-                                          : msm_run_cap_default((uint32_t)n, m.c);
+    m.L = run_max == BN_MSM_RUN_UNSPLIT ? kMsmRunUnsplit
+          : run_max                     ? (uint32_t)run_max
+                                        : msm_run_cap_default((uint32_t)n, m.c);
     m.levels = msm_fold_levels((uint32_t)n, m.L);
     if (m.levels == 0) m.L = kMsmRunUnsplit;
     if (m.levels && m.nent <= (size_t)0x7fffffff) {
         m.slots_a = msm_level_slots((uint32_t)m.nent, m.nkeys, m.L, 0);
         if (m.levels > 1) m.slots_b = msm_level_slots((uint32_t)m.nent, m.nkeys, m.L, 1);
     }
+    return m;
+}
+template <class P>
+static MsmPlan msm_plan(bn_ctx* c, size_t n) {
+    const MsmGroupWs<P>& g = MsmGroup<P>::ws(c);
+    MsmPlan m = msm_plan_at(g.run_max, n, g.window ? g.window : MsmGroup<P>::auto_window(n));
+    m.small = n < g.min;
     return m;
 }
 template <class P>
@@ -147,6 +154,25 @@ static int msm_tree_out(bn_ctx* c, P* buf, size_t m, size_t width, int finish, P
         G::k_finish<<<1, 64, 0, s>>>(nullptr, d_out);  // zero is its own Jacobian image
     return BN_OK;
 }
+// The fold levels above the s0 chunk sums in run_a: one launch per level the largest run can
+// have; every grid is the host's bound for its level.  Even levels write run_a, odd ones run_b.
+template <class P>
+static void msm_folds(bn_ctx* c, const MsmPlan& m, const uint32_t* offsets, const uint32_t* longinfo, uint32_t s0,
+                      hipStream_t s) {
+    using G = MsmGroup<P>;
+    MsmGroupWs<P>& g = G::ws(c);
+    const uint32_t nent = (uint32_t)m.nent;
+    uint32_t nsrc = s0;
+    for (int lv = 1; lv <= m.levels; ++lv) {
+        P* src = lv & 1 ? g.run_a : g.run_b;
+        P* dst = lv & 1 ? g.run_b : g.run_a;
+        const size_t cap = lv == m.levels ? 0 : (lv & 1 ? g.run_b_cap : g.run_a_cap);  // the last level writes buckets only
+        const uint32_t slots = msm_level_slots(nent, m.nkeys, m.L, lv);
+        const uint32_t ndst = (uint32_t)std::min<size_t>(slots, cap);
+        G::k_fold<<<grid_for(G::kLanes * (size_t)slots), kBlock, 0, s>>>(src, nsrc, offsets, longinfo, m.nkeys, nent, m.L, lv, dst, ndst, slots, g.buckets);
+        nsrc = ndst;
+    }
+}
 // the device sequence on stream s; the caller holds the lock and the workspace order.
 // The group-law kernels take G::kLanes lanes per element (kBlock is even: whole pairs).
 template <class P>
@@ -185,16 +211,7 @@ static int msm_dev_impl(bn_ctx* c, const P* d_p, const bn_fr* d_k, size_t n, P* 
         // lane whose slot no long key holds returns.  Even levels write run_a, odd ones run_b.
         const uint32_t s0 = (uint32_t)std::min(m.slots_a, g.run_a_cap);
         G::k_chunk<<<grid_for(G::kLanes * (size_t)s0), kBlock, 0, s>>>(d_p, n, c->msm_sorted, offsets, longinfo, m.nkeys, nent, m.L, g.run_a, s0);
-        uint32_t nsrc = s0;
-        for (int lv = 1; lv <= m.levels; ++lv) {
-            P* src = lv & 1 ? g.run_a : g.run_b;
-            P* dst = lv & 1 ? g.run_b : g.run_a;
-            const size_t cap = lv == m.levels ? 0 : (lv & 1 ? g.run_b_cap : g.run_a_cap);  // the last level writes buckets only
-            const uint32_t slots = msm_level_slots(nent, m.nkeys, m.L, lv);
-            const uint32_t ndst = (uint32_t)std::min<size_t>(slots, cap);
-            G::k_fold<<<grid_for(G::kLanes * (size_t)slots), kBlock, 0, s>>>(src, nsrc, offsets, longinfo, m.nkeys, nent, m.L, lv, dst, ndst, slots, g.buckets);
-            nsrc = ndst;
-        }
+        msm_folds<P>(c, m, offsets, longinfo, s0, s);
     }
     G::k_reduce<<<grid_for(G::kLanes * nparts), kBlock, 0, s>>>(g.buckets, m.c, m.nkeys, m.nseg, g.parts);
     RET_IF(msm_tree_out<P>(c, g.parts, m.nseg, m.nwin, 0, nullptr, s));
@@ -336,6 +353,102 @@ static int msm_prepared_dev_impl(bn_ctx* c, const bn_g1_prepared* h, const bn_fr
         msm_tree(g.fixed, L, mc, s);
         k_g1_msm_fixed_finish<<<grid_for(mc), kBlock, 0, s>>>(g.fixed, mc, d_out + off * out_stride, out_stride);
     }
+    HIPCHK(c, hipGetLastError());
+    return BN_OK;
+}
+
+// ---------------------------------------------------------------- one large MSM over a fixed basis
+// a live handle of this context (looked up, not dereferenced)
+static bool g1_basis_live(const bn_ctx* c, const bn_g1_basis* h) {
+    return h && std::find(c->g1_basis.begin(), c->g1_basis.end(), h) != c->g1_basis.end();
+}
+// refused before anything is read: a NULL bases or out, a width outside 2 .. 16 (0: the
+// default), an nbases that is 0, above 2^26 or whose nbases * W(c) exceeds the 32-bit positions
+static int g1_basis_args(bn_ctx* c, const void* bases, size_t nbases, int cw, bn_g1_basis** out) {
+    if (!bases || !out) return fail(c, BN_ERR_INVALID_ARGUMENT, "null buffer");
+    if (cw != 0 && !msm_window_ok(cw)) return fail(c, BN_ERR_INVALID_ARGUMENT, "window width outside 2 .. 16 (0: default)");
+    if (!msm_basis_entries(nbases, cw))
+        return fail(c, BN_ERR_INVALID_ARGUMENT, "nbases is 0, above 2^26, or nbases * windows exceeds 2^31 - 1");
+    return BN_OK;
+}
+// A new handle filled on stream s from the bases (host memory, or device memory when dev).
+// The caller holds the lock and has ordered s after the workspace's previous user (the host
+// form stages the bases, and waits for the build).
+static int g1_basis_make(bn_ctx* c, const bn_g1* bases, bool dev, size_t nbases, int cw, bn_g1_basis** out, hipStream_t s) {
+    bn_g1_basis* h = new bn_g1_basis();
+    h->nbases = nbases;
+    h->c = cw ? cw : msm_basis_auto_window(nbases);
+    int rc = [&]() -> int {
+        HIPCHK(c, hipMalloc(&h->table, (size_t)msm_basis_entries(nbases, h->c) * 2 * sizeof(bn_fq)));
+        HIPCHK(c, hipMalloc(&h->zero, nbases));
+        const bn_g1* d = bases;
+        if (!dev) {
+            void* at[1];
+            RET_IF(stage_regions(c, {nbases * sizeof(bn_g1)}, at));
+            HIPCHK(c, hipMemcpyAsync(at[0], bases, nbases * sizeof(bn_g1), hipMemcpyHostToDevice, s));
+            d = (const bn_g1*)at[0];
+        }
+        k_g1_basis_build<<<grid_for(nbases), kBlock, 0, s>>>(d, (uint32_t)nbases, h->c, h->table, h->zero);
+        HIPCHK(c, hipGetLastError());
+        if (!dev) HIPCHK(c, hipStreamSynchronize(s));
+        return BN_OK;
+    }();
+    if (rc != BN_OK) {
+        (void)hipStreamSynchronize(s);  // nothing queued may still write the table
+        if (h->table) (void)hipFree(h->table);
+        if (h->zero) (void)hipFree(h->zero);
+        delete h;
+        return rc;
+    }
+    c->g1_basis.push_back(h);
+    *out = h;
+    return BN_OK;
+}
+static int msm_basis_args(bn_ctx* c, const bn_g1_basis* h, const void* k, size_t n, const void* out) {
+    if (!g1_basis_live(c, h)) return fail(c, BN_ERR_INVALID_ARGUMENT, "not a live basis handle of this context");
+    if (!out) return fail(c, BN_ERR_INVALID_ARGUMENT, "null buffer");
+    if (n > h->nbases) return fail(c, BN_ERR_INVALID_ARGUMENT, "more terms than the handle has bases");
+    if (n && !k) return fail(c, BN_ERR_INVALID_ARGUMENT, "null buffer");
+    return BN_OK;
+}
+// the plan of n terms over the handle: the bucket path's at the handle's width and the run
+// cap in force (bn_set_msm_window and bn_set_msm_min do not apply)
+static MsmPlan msm_basis_plan(bn_ctx* c, const bn_g1_basis* h, size_t n) { return msm_plan_at(c->msm_g1.run_max, n, h->c); }
+// The device sequence on stream s over the first n bases; the caller holds the lock and the
+// workspace order.  n * W(c) <= nbases * W(c) <= 2^31 - 1 (the prepare call's check).
+static int msm_basis_dev_impl(bn_ctx* c, const bn_g1_basis* h, const bn_fr* d_k, size_t n, bn_g1* d_out, hipStream_t s) {
+    if (n == 0) {
+        k_msm_finish<<<1, 64, 0, s>>>(nullptr, d_out);
+        HIPCHK(c, hipGetLastError());
+        return BN_OK;
+    }
+    const MsmPlan m = msm_basis_plan(c, h, n);
+    RET_IF(msm_reserve<bn_g1>(c, n, m));
+    MsmGroupWs<bn_g1>& g = c->msm_g1;
+    uint32_t* counts = c->msm_keys;
+    uint32_t* cursors = counts + m.nkeys;
+    uint32_t* offsets = cursors + m.nkeys;
+    uint32_t* longinfo = offsets + m.nkeys + 1;
+    const uint32_t nent = (uint32_t)m.nent, nb = msm_buckets(m.c), nbases = (uint32_t)h->nbases;
+    HIPCHK(c, hipMemsetAsync(counts, 0, (size_t)m.nkeys * 4, s));
+    k_msm_count_basis<<<grid_for(n), kBlock, 0, s>>>(h->zero, d_k, n, m.c, m.nkeys, counts);
+    k_msm_scan<<<1, kMsmScanBlock, 0, s>>>(counts, m.nkeys, offsets, cursors, m.L, longinfo);
+    k_msm_scatter_basis<<<grid_for(n), kBlock, 0, s>>>(h->zero, d_k, n, m.c, m.nkeys, cursors, offsets, c->msm_sorted, nent);
+    k_msm_basis_accumulate<<<grid_for(m.nkeys), kBlock, 0, s>>>(h->table, nbases, (uint32_t)n, m.c, c->msm_sorted, offsets,
+                                                                m.nkeys, nent, m.L, g.buckets);
+    if (m.levels) {
+        const uint32_t s0 = (uint32_t)std::min(m.slots_a, g.run_a_cap);
+        k_msm_basis_chunk<<<grid_for(s0), kBlock, 0, s>>>(h->table, nbases, (uint32_t)n, m.c, c->msm_sorted, offsets, longinfo,
+                                                          m.nkeys, nent, m.L, g.run_a, s0);
+        msm_folds<bn_g1>(c, m, offsets, longinfo, s0, s);
+    }
+    // Every window's bucket j weighs j + 1 but the top one's, whose slots are replicas: the rows
+    // of the windows below it are added into window 0's row, and two windows are reduced.
+    msm_tree(g.buckets, m.nwin - 1, nb, s);
+    k_msm_basis_reduce<<<grid_for(2 * (size_t)m.nseg), kBlock, 0, s>>>(g.buckets, m.c, m.nkeys, m.nseg, g.parts);
+    msm_tree(g.parts, m.nseg, 2, s);
+    msm_tree(g.parts, 2, 1, s);  // the two window sums: no weight between them, nothing is doubled
+    k_msm_finish<<<1, 64, 0, s>>>(g.parts, d_out);
     HIPCHK(c, hipGetLastError());
     return BN_OK;
 }
@@ -489,6 +602,63 @@ int bn_g1_msm_prepared_many_dev(bn_ctx* c, const bn_g1_prepared* h, const bn_fr*
     RET_IF(ws_acquire(c, s));
     WsUse use{c, s};
     return msm_prepared_dev_impl(c, h, d_k, m, d_out, out_stride, s);
+}
+size_t bn_g1_basis_table_bytes(size_t nbases, int cw) {
+    const uint64_t nent = msm_basis_entries(nbases, cw);
+    return nent ? (size_t)(nent * 2 * sizeof(bn_fq) + nbases) : 0;
+}
+int bn_g1_basis_prepare(bn_ctx* c, const bn_g1* bases, size_t nbases, int cw, bn_g1_basis** out) {
+    CTX_GUARD(c);
+    RET_IF(g1_basis_args(c, bases, nbases, cw, out));
+    RET_IF(ws_acquire(c, c->stream));
+    WsUse use{c, c->stream};
+    return g1_basis_make(c, bases, false, nbases, cw, out, c->stream);
+}
+int bn_g1_basis_prepare_dev(bn_ctx* c, const bn_g1* d_bases, size_t nbases, int cw, bn_g1_basis** out, void* stream) {
+    CTX_GUARD(c);
+    RET_IF(g1_basis_args(c, d_bases, nbases, cw, out));
+    const hipStream_t s = pick(c, stream);
+    RET_IF(ws_acquire(c, s));
+    WsUse use{c, s};
+    return g1_basis_make(c, d_bases, true, nbases, cw, out, s);
+}
+size_t bn_g1_basis_count(const bn_g1_basis* h) { return h ? h->nbases : 0; }
+int bn_g1_basis_window(const bn_g1_basis* h) { return h ? h->c : 0; }
+int bn_g1_basis_destroy(bn_ctx* c, bn_g1_basis* h) {
+    CTX_GUARD(c);
+    if (!g1_basis_live(c, h)) return fail(c, BN_ERR_INVALID_ARGUMENT, "not a live basis handle of this context");
+    RET_IF(ws_drain(c));  // every call that reads the table has recorded ws_event behind its work
+    c->g1_basis.erase(std::find(c->g1_basis.begin(), c->g1_basis.end(), h));
+    (void)hipFree(h->table);
+    (void)hipFree(h->zero);
+    delete h;
+    return BN_OK;
+}
+int bn_g1_msm_basis(bn_ctx* c, const bn_g1_basis* h, const bn_fr* k, size_t n, bn_g1* out) {
+    CTX_GUARD_HOST(c);
+    RET_IF(msm_basis_args(c, h, k, n, out));
+    void* at[2];  // the sum, the scalars
+    RET_IF(stage_regions(c, {sizeof(bn_g1), n * sizeof(bn_fr)}, at));
+    if (n) HIPCHK(c, hipMemcpyAsync(at[1], k, n * sizeof(bn_fr), hipMemcpyHostToDevice, c->stream));
+    RET_IF(msm_basis_dev_impl(c, h, (const bn_fr*)at[1], n, (bn_g1*)at[0], c->stream));
+    HIPCHK(c, hipMemcpyAsync(out, at[0], sizeof(bn_g1), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return BN_OK;
+}
+int bn_g1_msm_basis_dev(bn_ctx* c, const bn_g1_basis* h, const bn_fr* d_k, size_t n, bn_g1* d_out, void* stream) {
+    CTX_GUARD(c);
+    RET_IF(msm_basis_args(c, h, d_k, n, d_out));
+    hipStream_t s = pick(c, stream);
+    RET_IF(ws_acquire(c, s));
+    WsUse use{c, s};
+    return msm_basis_dev_impl(c, h, d_k, n, d_out, s);
+}
+int bn_g1_msm_basis_reserve(bn_ctx* c, const bn_g1_basis* h, size_t n) {
+    CTX_GUARD(c);
+    if (!g1_basis_live(c, h)) return fail(c, BN_ERR_INVALID_ARGUMENT, "not a live basis handle of this context");
+    if (n > h->nbases) return fail(c, BN_ERR_INVALID_ARGUMENT, "more terms than the handle has bases");
+    if (n == 0) return BN_OK;
+    return msm_reserve<bn_g1>(c, n, msm_basis_plan(c, h, n));
 }
 int bn_g1_msm_many(bn_ctx* c, const bn_g1* p, const bn_fr* k, const size_t* offsets, size_t m, bn_g1* out,
                    size_t out_stride) {

@@ -56,6 +56,17 @@ struct bn_g1_prepared {
     uint8_t* zero = nullptr;  // zero[b] != 0: bases[b] had z == 0, its entries are never added
 };
 
+// bn_g1_basis_prepare's handle: for each of nbases G1 bases the W(c) affine points
+// 2^(c w) * base (msm_basis.h: window major, two bn_fq each) and a zero flag per base,
+// device-resident, owned like a bn_g1_prepared by the single-device context whose `g1_basis`
+// list holds it.
+struct bn_g1_basis {
+    size_t nbases = 0;
+    int c = 0;
+    bn_fq* table = nullptr;
+    uint8_t* zero = nullptr;  // zero[b] != 0: bases[b] had z == 0, its entries are never added
+};
+
 struct bn_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -180,6 +191,8 @@ struct bn_ctx {
     std::vector<bn_g2_prepared*> prepared;
     // the same for the bn_g1_prepared handles (capi_msm.hip)
     std::vector<bn_g1_prepared*> g1_prepared;
+    // and for the bn_g1_basis handles (capi_msm.hip)
+    std::vector<bn_g1_basis*> g1_basis;
     // bn_g1_msm_many (capi_msm.hip, kernels_msm_many.hip).  Settings: 0 takes
     // the default (capi_msm.hip).  Its workspace is its own, like the MSM's: the digit bytes,
     // the multiples and the units' partial sums of one launch set, grown on first use or by

@@ -653,6 +653,19 @@ __global__ void __launch_bounds__(kBlock) k_g1_msm_many_unit(const uint8_t* __re
                                                              const uint32_t* __restrict__ unit_off, uint32_t nunits, bn_g1* __restrict__ parts);
 __global__ void __launch_bounds__(kBlock) k_g1_msm_many_finish(const bn_g1* __restrict__ parts, uint32_t nunits, const uint32_t* __restrict__ seg_unit, size_t m,
                                                                bn_g1* __restrict__ out, size_t stride);
+// kernels_msm_basis.hip (msm_basis.h): one large MSM over a fixed basis.  table: nbases * W(c)
+// entries of two bn_fq (x, y), window major; zero: one flag per base; the recoding kernels are
+// kernels_msm.hip's over the flags
+__global__ void __launch_bounds__(kBlock) k_g1_basis_build(const bn_g1* __restrict__ bases, uint32_t nbases, int c, bn_fq* __restrict__ table, uint8_t* __restrict__ zero);
+__global__ void __launch_bounds__(kBlock) k_msm_count_basis(const uint8_t* __restrict__ zero, const bn_fr* __restrict__ k, size_t n, int c, uint32_t nkeys, uint32_t* __restrict__ counts);
+__global__ void __launch_bounds__(kBlock) k_msm_scatter_basis(const uint8_t* __restrict__ zero, const bn_fr* __restrict__ k, size_t n, int c, uint32_t nkeys, uint32_t* __restrict__ cursors,
+                                                              const uint32_t* __restrict__ offsets, uint32_t* __restrict__ sorted, uint32_t nent);
+__global__ void __launch_bounds__(kBlock) k_msm_basis_accumulate(const bn_fq* __restrict__ table, uint32_t nbases, uint32_t n, int c, const uint32_t* __restrict__ sorted,
+                                                                 const uint32_t* __restrict__ offsets, uint32_t nkeys, uint32_t nent, uint32_t L, bn_g1* __restrict__ buckets);
+__global__ void __launch_bounds__(kBlock) k_msm_basis_chunk(const bn_fq* __restrict__ table, uint32_t nbases, uint32_t n, int c, const uint32_t* __restrict__ sorted,
+                                                            const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ longinfo, uint32_t nkeys, uint32_t nent, uint32_t L,
+                                                            bn_g1* __restrict__ sums, uint32_t nslots);
+__global__ void __launch_bounds__(kBlock) k_msm_basis_reduce(const bn_g1* __restrict__ buckets, int c, uint32_t nkeys, uint32_t nseg, bn_g1* __restrict__ parts);
 __global__ void __launch_bounds__(kPairBlock) k_gt_pow(const bn_gt* __restrict__ a, const bn_fr* __restrict__ k, size_t n,
                                                    bn_gt* __restrict__ out, uint32_t* __restrict__ ws);
 // kernels_codec.hip (codec.h): encodings, square roots, validation, decompression

@@ -1,7 +1,7 @@
 // kernels_msm.hip -- G1 multi-scalar multiplication by the bucket method:
 // S = sum_i k[i] * P[i], normalized (and the recoding, histogram and scatter of the
-// G2 one, whose group-law kernels are kernels_msm_g2.hip; the group-law bodies of both
-// are msm_group.h's).  The phases pass data only across kernel boundaries on one
+// G2 one, whose group-law kernels are kernels_msm_g2.hip, and of the fixed-basis one of
+// kernels_msm_basis.hip; the group-law bodies of both are msm_group.h's).  The phases pass data only across kernel boundaries on one
 // stream (no block waits for another):
 //   k_msm_count       signed-digit recoding (msm.h), histogram of the (window, bucket) keys
 //   k_msm_scan        exclusive scan of the histogram -> bucket offsets and scatter cursors,
@@ -40,6 +40,8 @@ __device__ __forceinline__ void st_g1(bn_g1& o, const G1J& r) {
 // zero points produce no entry.  All it reads of a point is whether z is zero.
 __device__ __forceinline__ bool msm_point_is_zero(const bn_g1& a) { return F_is_zero(ld_ref(a.z)); }
 __device__ __forceinline__ bool msm_point_is_zero(const bn_g2& a) { return F_is_zero(ld_ref2(a.z)); }
+// a fixed basis (msm_basis.h) keeps one zero flag per base in place of the points
+__device__ __forceinline__ bool msm_point_is_zero(const uint8_t& flag) { return flag != 0; }
 // The lanes of a wave that hold the same key share one atomic: skewed scalars (all equal, a
 // witness of zeros and ones) send most of a wave to one address, and 2^18 x W(c) atomics on
 // one address per hot key took 4.2 ms (count) and 8.6 ms (scatter) of an all-equal batch whose
@@ -117,6 +119,19 @@ __global__ void __launch_bounds__(kBlock) k_msm_scatter_g2(const bn_g2* __restri
                                                            const uint32_t* __restrict__ offsets,
                                                            uint32_t* __restrict__ sorted, uint32_t nent) {
     msm_digits<true>(p, k, n, c, nkeys, cursors, offsets, sorted, nent);
+}
+// the same over the first n bases of a fixed basis (bn_g1_msm_basis; kernels_msm_basis.hip)
+__global__ void __launch_bounds__(kBlock) k_msm_count_basis(const uint8_t* __restrict__ zero, const bn_fr* __restrict__ k,
+                                                            size_t n, int c, uint32_t nkeys,
+                                                            uint32_t* __restrict__ counts) {
+    msm_digits<false>(zero, k, n, c, nkeys, counts, nullptr, nullptr, 0);
+}
+__global__ void __launch_bounds__(kBlock) k_msm_scatter_basis(const uint8_t* __restrict__ zero,
+                                                              const bn_fr* __restrict__ k, size_t n, int c,
+                                                              uint32_t nkeys, uint32_t* __restrict__ cursors,
+                                                              const uint32_t* __restrict__ offsets,
+                                                              uint32_t* __restrict__ sorted, uint32_t nent) {
+    msm_digits<true>(zero, k, n, c, nkeys, cursors, offsets, sorted, nent);
 }
 
 // offsets[0 .. nkeys] = exclusive scan of counts[0 .. nkeys), cursors[key] = offsets[key];

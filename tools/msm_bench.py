@@ -24,6 +24,17 @@ unsplit form's own min .. max), then at --skew terms four skewed scalar patterns
 all 1, half 1 / half uniform, 1 % equal to r - 1), each as unsplit (one repetition: it takes
 seconds), split (the default cap) and small (the small path), after checking that the three
 return the same bytes.
+
+With --basis the comparison is bn_g1_msm_dev (a context with untouched settings: its automatic
+width) against bn_g1_msm_basis_dev over a bn_g1_basis of the same n bases, by
+the same protocol: HBM-resident inputs, workspace reserved, a warm-up of every form, --reps
+repetitions per form alternating in one process, torch events on the launch stream, median
+ms, and a check first that every form returns the same bytes.  The basis form runs at its
+default width and at the two widths on either side (--basis-windows lists other widths).  One
+JSON line per size with the prepare time (events around the _dev prepare call, its table
+allocation included) and table bytes of every width, then at --skew terms
+the four skewed patterns of --run-cap.  `gain_outside_spread`: the default-width basis form's
+median is below bn_g1_msm's by more than the wider of the two forms' own min .. max spreads.
 """
 import argparse
 import json
@@ -87,12 +98,15 @@ def small_products(n, group="g1"):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--group", choices=("g1", "g2"), default="g1")
-    ap.add_argument("--sizes", default="1,16,128,512," + ",".join(str(1 << e) for e in range(10, 21)))
+    ap.add_argument("--sizes", default=None,
+                    help="default: 1,16,128,512,2^10 .. 2^20; with --basis 1,2^10,2^12,2^14,2^16 .. 2^20")
     ap.add_argument("--windows", default="8,9,10,11,12,13,14,15,16")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--skew", type=int, default=1 << 18)
     ap.add_argument("--run-cap", action="store_true", help="sweep the run cap and the skew patterns instead of the window")
     ap.add_argument("--skew-reps", type=int, default=10)
+    ap.add_argument("--basis", action="store_true", help="bn_g1_msm against bn_g1_msm_basis over a fixed basis (g1)")
+    ap.add_argument("--basis-windows", default="", help="widths of the basis form; empty: its default and the two on either side")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     args = ap.parse_args()
     import torch
@@ -113,7 +127,12 @@ def main():
 
     dev = torch.device("cuda", 0)
     ctx, dctx = Context(0), Context(0)
-    sizes = [int(s) for s in args.sizes.split(",")]
+    if args.sizes:
+        sizes = [int(s) for s in args.sizes.split(",")]
+    elif args.basis:
+        sizes = [1, 1 << 10, 1 << 12, 1 << 14] + [1 << e for e in range(16, 21)]
+    else:
+        sizes = [1, 16, 128, 512] + [1 << e for e in range(10, 21)]
     cs = [int(c) for c in args.windows.split(",")]
     nmax = max(sizes + [args.skew])
     s = synth.fr_images_raw(nmax, 0x6d736d31)
@@ -177,6 +196,11 @@ def main():
     def stats(ts):
         return {"median_ms": round(statistics.median(ts), 4), "min_ms": round(min(ts), 4), "max_ms": round(max(ts), 4)}
 
+    if args.basis:
+        if grp != "g1":
+            sys.exit("--basis is G1 only")
+        basis_sweep(args, sizes, dctx, P, K, k, out, stream, stats, emit, dev)
+        return
     if args.run_cap:
         run_cap_sweep(args, grp, sizes, run, stats, emit, k, K, dev)
         return
@@ -225,7 +249,6 @@ def main():
 def run_cap_sweep(args, grp, sizes, run, stats, emit, k, K, dev):
     import torch
 
-    from oracle import oracle as O
     forms = ["unsplit", "default"] + ["L0=%d" % m for m in RUN_MINS]
     for n in sizes:
         want = None
@@ -250,16 +273,7 @@ def run_cap_sweep(args, grp, sizes, run, stats, emit, k, K, dev):
     if not args.skew:
         return
     n = args.skew
-    one, minus_one = O.canon_to_mont_array([1, O.R - 1], O.FR).reshape(2, 4)
-    uni = k[:n]
-    pats = {"all_equal": np.tile(k[7], (n, 1)), "all_one": np.tile(one, (n, 1))}
-    half = uni.copy()
-    half[0::2] = one
-    pats["half_one"] = half
-    pct = uni.copy()
-    pct[0::100] = minus_one
-    pats["one_pct_minus_one"] = pct
-    for name, kv in pats.items():
+    for name, kv in skew_patterns(k, n).items():
         kd = torch.from_numpy(np.ascontiguousarray(kv).view(np.int64)).to(dev)
         torch.cuda.synchronize(dev)
         _, want = run("small", n, kd, False)
@@ -280,6 +294,117 @@ def run_cap_sweep(args, grp, sizes, run, stats, emit, k, K, dev):
                "reps": args.skew_reps, "split": stats(times["split"]), "small": stats(times["small"])}
         rec["split_beats_small"] = rec["split"]["median_ms"] < rec["small"]["median_ms"]
         emit(rec)
+
+
+def skew_patterns(k, n):
+    """the four skewed scalar patterns of --run-cap and --basis: {name: (n, 4) images}"""
+    from oracle import oracle as O
+    one, minus_one = O.canon_to_mont_array([1, O.R - 1], O.FR).reshape(2, 4)
+    uni = k[:n]
+    pats = {"all_equal": np.tile(k[7], (n, 1)), "all_one": np.tile(one, (n, 1))}
+    half = uni.copy()
+    half[0::2] = one
+    pats["half_one"] = half
+    pct = uni.copy()
+    pct[0::100] = minus_one
+    pats["one_pct_minus_one"] = pct
+    return pats
+
+
+def basis_sweep(args, sizes, dctx, P, K, k, out, stream, stats, emit, dev):
+    import torch
+
+    from substrate_bn import _native
+    sh = stream.cuda_stream
+
+    def timed(call):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        with torch.cuda.stream(stream):
+            e0.record()
+            call()
+            e1.record()
+        torch.cuda.synchronize(dev)
+        return e0.elapsed_time(e1), out.cpu().numpy().view(np.uint64).copy()
+
+    def prepared(n, c):
+        """-> a handle over P[:n] at width c (0: the default) and the device time of its build,
+        the second of two (the first warms up)"""
+        made = []
+        for _ in range(2):
+            if made:
+                dctx.g1_basis_destroy(made.pop())
+            ms, _ = timed(lambda: made.append(dctx.g1_basis_prepare_dev(P.data_ptr(), n, c, sh)))
+        return made[0], ms
+
+    def compare(n, kd, handles, reps, what):
+        """-> {form: stats} of bn_g1_msm and the basis form at every width over the scalars kd,
+        after a warm-up of every form that is also the agreement check"""
+        forms = {"msm": lambda: dctx.g1_msm_dev(P.data_ptr(), kd.data_ptr(), n, out.data_ptr(), sh)}
+        for c, h in handles.items():
+            forms["basis c=%d" % c] = lambda h=h: dctx.g1_msm_basis_dev(h, kd.data_ptr(), n, out.data_ptr(), sh)
+        dctx.msm_reserve(n)
+        for h in handles.values():
+            dctx.g1_msm_basis_reserve(h, n)
+        want = None
+        for f, call in forms.items():
+            _, got = timed(call)
+            if want is None:
+                want = got
+            elif not np.array_equal(got, want):
+                print("MISMATCH at %s: %s differs from bn_g1_msm" % (what, f), file=sys.stderr)
+                sys.exit(1)
+        times = {f: [] for f in forms}
+        for _ in range(reps):
+            for f, call in forms.items():
+                times[f].append(timed(call)[0])
+        return {f: stats(ts) for f, ts in times.items()}
+
+    def verdict(rec, c0):
+        a, b = rec["msm"], rec["basis c=%d" % c0]
+        spread = max(a["max_ms"] - a["min_ms"], b["max_ms"] - b["min_ms"])
+        rec["msm_over_basis"] = round(a["median_ms"] / b["median_ms"], 3)
+        rec["spread_ms"] = round(spread, 4)
+        rec["gain_outside_spread"] = a["median_ms"] - b["median_ms"] > spread
+        rec["basis_not_slower"] = b["median_ms"] <= a["median_ms"]
+
+    def sized(n, body):
+        """body(c0, {c: handle}, {width: prepare time and table bytes}) over handles of n bases"""
+        h0, ms0 = prepared(n, 0)
+        c0 = dctx.g1_basis_window(h0)
+        handles, prep = {c0: h0}, {c0: ms0}
+        try:
+            others = [int(c) for c in args.basis_windows.split(",")] if args.basis_windows else [c0 - 1, c0 + 1]
+            for c in others:
+                if 2 <= c <= 16 and c not in handles:
+                    handles[c], prep[c] = prepared(n, c)
+            handles = dict(sorted(handles.items()))
+            body(c0, handles, {"c=%d" % c: {"prepare_ms": round(prep[c], 3), "table_bytes": _native.g1_basis_table_bytes(n, c)}
+                               for c in handles})
+        finally:
+            for h in handles.values():
+                dctx.g1_basis_destroy(h)
+
+    for n in sizes:
+        def body(c0, handles, prep, n=n):
+            rec = {"n": n, "reps": args.reps, "basis_default_c": c0, "msm_auto_c": auto_window("g1", n), "prepare": prep}
+            rec.update(compare(n, K, handles, args.reps, "n=%d" % n))
+            verdict(rec, c0)
+            rec["best_basis_c"] = min(handles, key=lambda c: rec["basis c=%d" % c]["median_ms"])
+            emit(rec)
+        sized(n, body)
+    if not args.skew:
+        return
+    n = args.skew
+
+    def body(c0, handles, prep):
+        for name, kv in skew_patterns(k, n).items():
+            kd = torch.from_numpy(np.ascontiguousarray(kv).view(np.int64)).to(dev)
+            torch.cuda.synchronize(dev)
+            rec = {"skew": name, "n": n, "reps": args.skew_reps, "basis_default_c": c0, "msm_auto_c": auto_window("g1", n)}
+            rec.update(compare(n, kd, {c0: handles[c0]}, args.skew_reps, name))
+            verdict(rec, c0)
+            emit(rec)
+    sized(n, body)
 
 
 if __name__ == "__main__":
