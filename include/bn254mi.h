@@ -51,10 +51,26 @@ typedef enum {
 typedef struct bn_ctx bn_ctx;
 
 /* One context per device.  A context may be shared by host threads: each call holds
- * it for its whole duration (staging, kernels, readback).  *_dev calls enqueued on
- * different streams run on the device in call order (the context's workspace is
- * shared; each call's stream waits for the previous call's work).  The reference
- * is reentrant from any thread (lib.rs:303-305, Group: Send + Sync). */
+ * it for its whole duration (staging, kernels, readback).
+ * Ordering across streams.  The *_dev calls that use a workspace of the context or read a
+ * handle run on the device in call order, whatever streams they are enqueued on (the
+ * workspaces are shared; each such call's stream first waits for the work of the one
+ * before it).  They are: bn_pairing_many_dev, bn_pairing_batch_dev, bn_miller_loop_batch_dev,
+ * bn_pairing_batch_many_dev, bn_g2_prepare_dev, bn_pairing_prepared_many_dev,
+ * bn_pairing_batch_prepared_many_dev, bn_g1_msm_dev, bn_g2_msm_dev, bn_g1_bases_prepare_dev,
+ * bn_g1_msm_prepared_many_dev, bn_g1_basis_prepare_dev, bn_g1_msm_basis_dev,
+ * bn_g1_msm_many_dev and bn_gt_pow_many_dev (bn_pairing_many_allgather_dev is
+ * bn_pairing_many_dev on every device's context); bn_dev_status and the host-buffer calls,
+ * which run on the context's own stream, take their place in that order too.  A caller may
+ * therefore hand one such call's output to the next on another stream without an event of
+ * its own.
+ * The other *_dev calls use no workspace and are ordered by their own stream ONLY:
+ * bn_g1_mul_many_dev and bn_g2_mul_many_dev, the ten group-law calls
+ * (bn_g1/g2_{add,sub,neg,normalize,eq}_many_dev) and the three codec calls
+ * (bn_g2_affine_new_many_dev, bn_g1/g2_from_compressed_many_dev).  They neither wait for the
+ * calls above nor make them wait: a caller who chains one of them with any other call across
+ * two streams must order the two itself (an event, or one stream).
+ * The reference is reentrant from any thread (lib.rs:303-305, Group: Send + Sync). */
 int bn_ctx_create(int device, bn_ctx** out);
 int bn_ctx_destroy(bn_ctx* ctx);
 const char* bn_last_error(const bn_ctx* ctx);
@@ -64,7 +80,9 @@ void* bn_ctx_stream(bn_ctx* ctx);
  * bn_pairing_many_allgather_dev): synchronizes `stream` (NULL: the context's stream), returns
  * BN_ERR_INTERNAL or BN_ERR_FE_ZERO (a Miller value was zero: the reference panics, mod.rs:900)
  * if any such call since the last bn_dev_status (or host-buffer call, which starts from a clear
- * word) set it, else BN_OK, and clears it.  bn_pairing_prepared_many_dev adds BN_ERR_INVALID_ARGUMENT
+ * word) set it, else BN_OK, and clears it.  A call with a status word of its own in between
+ * (bn_pairing_batch_dev, bn_miller_loop_batch_dev) reports only itself there and leaves the
+ * sticky outcome of the calls before it in place.  bn_pairing_prepared_many_dev adds BN_ERR_INVALID_ARGUMENT
  * (an index past the handle's points), reported after BN_ERR_INTERNAL and before BN_ERR_FE_ZERO.  On a multi-device context it checks every device,
  * each on its own context stream, and `stream` must be NULL (else BN_ERR_INVALID_ARGUMENT). */
 int bn_dev_status(bn_ctx* ctx, void* stream);

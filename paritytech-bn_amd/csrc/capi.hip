@@ -918,7 +918,8 @@ int bn_ctx_create(int device, bn_ctx** out) {
         hipStreamCreateWithFlags(&c->d2h, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&c->ws_event, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->prod_off_event, hipEventDisableTiming) != hipSuccess ||
-        hipMalloc(&c->d_err, sizeof(int)) != hipSuccess || hipMemset(c->d_err, 0, sizeof(int)) != hipSuccess ||
+        hipMalloc(&c->d_err, kErrWords * sizeof(int)) != hipSuccess ||
+        hipMemset(c->d_err, 0, kErrWords * sizeof(int)) != hipSuccess ||
         hipMalloc(&c->tail_ws, kTailWsWords * 4) != hipSuccess || hipMemset(c->tail_ws, 0, kTailWsWords * 4) != hipSuccess ||
         hipMalloc(&c->fe_ds_ws, (size_t)kFeDsMax * kFeDsWords * 4) != hipSuccess ||
         hipMemset(c->fe_ds_ws, 0, (size_t)kFeDsMax * kFeDsWords * 4) != hipSuccess ||
@@ -1313,7 +1314,9 @@ static int batch_dev(bn_ctx* c, const bn_g1* d_p, const bn_g2* d_q, size_t n, bn
     RET_IF(reserve(c, n == 0 ? 1 : n < kChunk ? n : kChunk));
     RET_IF(ws_acquire(c, s));
     WsUse use{c, s};
-    HIPCHK(c, hipMemsetAsync(c->d_err, 0, sizeof(int), s));
+    // *d_status reports this call alone; what earlier calls left stays for bn_dev_status
+    k_err_hold<<<1, 64, 0, s>>>(c->d_err);
+    HIPCHK(c, hipGetLastError());
     if (n == 0) {  // pairing_batch: mod.rs:922-924; the shared loop starts from one (mod.rs:610)
         HIPCHK(c, hipMemcpyAsync(d_out, &kGtOne, sizeof(bn_gt), hipMemcpyHostToDevice, s));
     } else {

@@ -156,18 +156,23 @@ inline int grow_pinned_pair(bn_ctx* c, uint32_t** h, uint32_t** d, size_t* cap, 
     return BN_OK;
 }
 
+// The device outcome word is two: d_err[0], which the kernels set, and d_err[1], where
+// bn_*_batch_dev (which report d_err[0] alone through their own status word) put aside
+// what the calls before them left (k_err_hold).  check_err reads both, clear_err clears both.
+constexpr size_t kErrWords = 2;
 // the device outcome bits of the calls since the last clear; a wave hand-off that
 // ran out of its wait cap (BN_ERR_INTERNAL) fails the call here, whatever else is set
 inline int check_err(bn_ctx* c, hipStream_t s, int* out_bits) {
-    int h = 0;
-    HIPCHK(c, hipMemcpyAsync(&h, c->d_err, sizeof(int), hipMemcpyDeviceToHost, s));
+    int h[kErrWords] = {};
+    HIPCHK(c, hipMemcpyAsync(h, c->d_err, sizeof h, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
-    *out_bits = h;
-    if (h & (1 << BN_ERR_INTERNAL)) return fail(c, BN_ERR_INTERNAL, "device wave hand-off timed out; result discarded");
+    *out_bits = h[0] | h[1];
+    if (*out_bits & (1 << BN_ERR_INTERNAL))
+        return fail(c, BN_ERR_INTERNAL, "device wave hand-off timed out; result discarded");
     return BN_OK;
 }
 inline int clear_err(bn_ctx* c, hipStream_t s) {
-    HIPCHK(c, hipMemsetAsync(c->d_err, 0, sizeof(int), s));
+    HIPCHK(c, hipMemsetAsync(c->d_err, 0, kErrWords * sizeof(int), s));
     return BN_OK;
 }
 // the outcome bits a call reports (`mask`: those it can set) as its return code

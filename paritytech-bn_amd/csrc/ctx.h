@@ -109,7 +109,7 @@ struct bn_ctx {
     size_t lat_w1_max = 2048;  // CU count x kLatPairs (bn_ctx_create): one round of one-wave blocks
     // batches of at most this many pairs take k_prepare_wide (8 lanes per pair)
     size_t prepare_wide_max = 0;
-    int* d_err = nullptr;
+    int* d_err = nullptr;  // two words: the kernels' outcome bits, and those put aside by k_err_hold (capi_internal.h)
     // pairing_batch's one-launch tail (kernels_tail.hip k_seg_tail): its own words
     // (kTailWsWords, zeroed at creation), every word it polls stamped with the
     // launch's epoch, so no clearing between products

@@ -597,6 +597,7 @@ __global__ void __launch_bounds__(kLatThreads) __attribute__((amdgpu_waves_per_e
 k_pairing_latency_w2(const bn_g1* __restrict__ p, const bn_g2* __restrict__ q, size_t n, bn_gt* __restrict__ out,
                      uint32_t* __restrict__ f_out, int mode, int* __restrict__ err);
 __global__ void __launch_bounds__(kBlock) k_err_status(const int* __restrict__ err, int* __restrict__ status);
+__global__ void __launch_bounds__(kBlock) k_err_hold(int* __restrict__ err);
 __global__ void __launch_bounds__(kBlock) k_gt_load(const bn_gt* __restrict__ g, size_t n, uint32_t* __restrict__ f);
 __global__ void __launch_bounds__(kBlock) k_gt_store(const uint32_t* __restrict__ f, size_t n, size_t stride, bn_gt* __restrict__ g);
 __global__ void __launch_bounds__(kPairBlock) k_g1_mul(const bn_g1* __restrict__ p, const bn_fr* __restrict__ k, size_t n, bn_g1* __restrict__ out);

@@ -259,6 +259,16 @@ __global__ void __launch_bounds__(kBlock) k_err_status(const int* __restrict__ e
     }
 }
 
+// err[1] |= err[0]; err[0] = 0: a call with a status word of its own starts from a clear
+// word without dropping what the calls before it left for bn_dev_status (one thread; the
+// stream orders it between those calls' kernels and this call's)
+__global__ void __launch_bounds__(kBlock) k_err_hold(int* __restrict__ err) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        err[1] |= err[0];
+        err[0] = 0;
+    }
+}
+
 }  // namespace bn
 
 #if BN_LAT_STAMPS

@@ -155,6 +155,158 @@ def test_gt_pow(ctx):
     assert np.array_equal(out, O.gt_pow(b, kb))
 
 
+# ---------------------------------------------------------------- the device-pointer forms
+DEV_SIZES = [1, 63, 64, 65, 129]
+NDEV = 129
+INVALID_ARGUMENT = 1
+
+
+@pytest.fixture(scope="module")
+def dev_cases():
+    """129 inputs of each _dev call, built as the host-form tests above build theirs -- valid
+    and invalid records interleaved by a fixed permutation -- and the oracle's images and
+    status bytes, computed once; every size takes a prefix."""
+    rng = np.random.default_rng(43)
+    mix = np.random.default_rng(44).permutation(NDEV)
+    g2aff, g1aff = subgroup_affine(97, 61, NT)
+    # compressed records: 97 valid, then a bad sign byte, x >= p (p^2 for G2) and a random x
+    c1, c2 = compress_g1(g1aff), compress_g2(g2aff)
+    bad1, bad2 = c1[:32].copy(), c2[:32].copy()
+    bad1[:8, 0] = 4
+    bad1[8:16, 1:] = be(P)
+    bad1[16:, 1:] = np.stack([be(int.from_bytes(rng.bytes(32), "big") % P) for _ in range(16)])
+    bad2[:8, 0] = 12
+    bad2[8:16, 1:] = be(P * P, 64)
+    bad2[16:, 1:] = np.stack([be(int.from_bytes(rng.bytes(64), "big") % (P * P), 64) for _ in range(16)])
+    b33 = np.ascontiguousarray(np.concatenate([c1, bad1])[mix])
+    b65 = np.ascontiguousarray(np.concatenate([c2, bad2])[mix])
+    # AffineG2::new: 97 subgroup points, 16 twist points outside it, 16 points off the curve
+    tx, ty = random_twist_points(16, 62)
+    ty_bad = ty.copy()
+    ty_bad[:, 0] ^= 2
+    x = np.ascontiguousarray(np.concatenate([g2aff[:, :8], tx, tx])[mix])
+    y = np.ascontiguousarray(np.concatenate([g2aff[:, 8:], ty, ty_bad])[mix])
+    # Gt::pow: test_gt_pow's mixed rows -- pairing outputs, a Miller value and a zero element
+    # inside the first wave, more Miller values behind -- and its planted scalars
+    p, q, _, _ = O.random_pairs(64, seed=51, nthreads=NT)
+    g = O.pairing_many(p, q, NT)
+    ml = np.stack([O.miller_loop_batch(q[k:k + 1], p[k:k + 1])[1] for k in range(8)])
+    b = np.concatenate([g[:10], ml[:1], g[10:40], np.zeros((1, 48), np.uint64), g[40:], ml[1:]])
+    a = np.ascontiguousarray(np.concatenate([b, b[:NDEV - b.shape[0]]]))
+    _, k = O.random_scalars(NDEV, 63, lo=0)
+    k[:3] = O.canon_to_mont_array([0, 1, R - 1], O.FR).reshape(3, 4)
+    k[3:7] = O.canon_to_mont_array([(1 << 250) - 1, (1 << 253) - 1, int("01" * 126, 2), int("10000" * 50, 2)],
+                                   O.FR).reshape(4, 4)
+    d = {"b33": b33, "g1": O.g1_from_compressed(b33, NT), "b65": b65, "g2": O.g2_from_compressed(b65, NT),
+         "x": x, "y": y, "aff": O.g2_affine_new(x, y, NT), "a": a, "k": k, "pow": O.gt_pow(a, k)}
+    # valid and invalid records in every prefix of 63 and more
+    for key in ("g1", "g2"):
+        st = d[key][1]
+        assert (st[:63] == 0).any() and len(set(st[:63])) >= 3, (key, sorted(set(st)))
+    assert set(d["aff"][1][:63]) == {0, 6, 7}  # ok, NotOnCurve, NotInSubgroup
+    return d
+
+
+def _torch_dev():
+    import torch
+    return torch, torch.device("cuda", 0)
+
+
+def _words(a):
+    """the uint64 rows of `a` on the device (int64 storage)"""
+    torch, dev = _torch_dev()
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint64).view(np.int64).reshape(-1).copy()).to(dev)
+
+
+def _bytes_at(a, shift):
+    """the bytes of `a` on the device, starting `shift` bytes into a fresh allocation"""
+    torch, dev = _torch_dev()
+    a = np.ascontiguousarray(a, dtype=np.uint8).reshape(-1)
+    raw = torch.zeros(a.size + 8, dtype=torch.uint8, device=dev)
+    view = raw[shift:shift + a.size]
+    view.copy_(torch.from_numpy(a.copy()))
+    assert view.data_ptr() % 8 == shift % 8
+    return view, raw
+
+
+def _run_dev(ctx, call, n, width, st_shift=0):
+    """call(d_out, d_status, stream) on a caller stream -> ((n, width) images, n status bytes)"""
+    torch, dev = _torch_dev()
+    out = torch.full((n * width,), 0x5a5a, dtype=torch.int64, device=dev)
+    sraw = torch.full((n + 8,), 0x5a, dtype=torch.uint8, device=dev)
+    st = sraw[st_shift:st_shift + n]
+    s = torch.cuda.Stream(dev)
+    torch.cuda.synchronize(dev)
+    call(out.data_ptr(), st.data_ptr(), s.cuda_stream)
+    torch.cuda.synchronize(dev)
+    guard = sraw.cpu().numpy()
+    assert (guard[:st_shift] == 0x5a).all() and (guard[st_shift + n:] == 0x5a).all(), "status bytes written outside [0, n)"
+    return out.cpu().numpy().view(np.uint64).reshape(n, width), guard[st_shift:st_shift + n]
+
+
+@pytest.mark.parametrize("shift,st_shift", [(0, 0), (1, 3)])
+@pytest.mark.parametrize("n", DEV_SIZES)
+def test_g1_from_compressed_dev(ctx, dev_cases, n, shift, st_shift):
+    """33-byte records carry no alignment: also with the records from an odd device address
+    and the status bytes from another."""
+    ref, rst = dev_cases["g1"]
+    B, _raw = _bytes_at(dev_cases["b33"][:n], shift)
+    out, st = _run_dev(ctx, lambda o, t, s: ctx.g1_from_compressed_many_dev(B.data_ptr(), n, o, t, s), n, 12, st_shift)
+    assert np.array_equal(st, rst[:n]) and np.array_equal(out, ref[:n])
+
+
+@pytest.mark.parametrize("shift,st_shift", [(0, 0), (1, 3)])
+@pytest.mark.parametrize("n", DEV_SIZES)
+def test_g2_from_compressed_dev(ctx, dev_cases, n, shift, st_shift):
+    ref, rst = dev_cases["g2"]
+    B, _raw = _bytes_at(dev_cases["b65"][:n], shift)
+    out, st = _run_dev(ctx, lambda o, t, s: ctx.g2_from_compressed_many_dev(B.data_ptr(), n, o, t, s), n, 24, st_shift)
+    assert np.array_equal(st, rst[:n]) and np.array_equal(out, ref[:n])
+
+
+@pytest.mark.parametrize("n", DEV_SIZES)
+def test_g2_affine_new_dev(ctx, dev_cases, n):
+    ref, rst = dev_cases["aff"]
+    X, Y = _words(dev_cases["x"][:n]), _words(dev_cases["y"][:n])
+    out, st = _run_dev(ctx, lambda o, t, s: ctx.g2_affine_new_many_dev(X.data_ptr(), Y.data_ptr(), n, o, t, s), n, 24)
+    assert np.array_equal(st, rst[:n]) and np.array_equal(out, ref[:n])
+
+
+@pytest.mark.parametrize("n", DEV_SIZES)
+def test_gt_pow_dev(ctx, dev_cases, n):
+    A, K = _words(dev_cases["a"][:n]), _words(dev_cases["k"][:n])
+    out, _ = _run_dev(ctx, lambda o, t, s: ctx.gt_pow_many_dev(A.data_ptr(), K.data_ptr(), n, o, s), n, 48)
+    assert np.array_equal(out, dev_cases["pow"][:n])
+
+
+def test_dev_forms_null_arguments(ctx, dev_cases):
+    """n == 0 with NULL pointers is BN_OK and touches nothing; a NULL buffer with n > 0 is
+    refused (each buffer in turn, the others real)."""
+    torch, dev = _torch_dev()
+    L, h = ctx._L, ctx.handle
+    buf = torch.zeros(4096, dtype=torch.int64, device=dev)
+    torch.cuda.synchronize(dev)
+    d = buf.data_ptr()
+    assert L.bn_g1_from_compressed_many_dev(h, None, 0, None, None, None) == 0
+    assert L.bn_g2_from_compressed_many_dev(h, None, 0, None, None, None) == 0
+    assert L.bn_g2_affine_new_many_dev(h, None, None, 0, None, None, None) == 0
+    assert L.bn_gt_pow_many_dev(h, None, None, 0, None, None) == 0
+    for fn in (L.bn_g1_from_compressed_many_dev, L.bn_g2_from_compressed_many_dev):
+        for args in ((None, 1, d, d), (d, 1, None, d), (d, 1, d, None)):
+            assert fn(h, *args, None) == INVALID_ARGUMENT
+    for args in ((None, d, 1, d, d), (d, None, 1, d, d), (d, d, 1, None, d), (d, d, 1, d, None)):
+        assert L.bn_g2_affine_new_many_dev(h, *args, None) == INVALID_ARGUMENT
+    for args in ((None, d, 1, d), (d, None, 1, d), (d, d, 1, None)):
+        assert L.bn_gt_pow_many_dev(h, *args, None) == INVALID_ARGUMENT
+    torch.cuda.synchronize(dev)
+    assert not buf.cpu().numpy().any()
+    # the context is still good
+    n = 5
+    A, K = _words(dev_cases["a"][:n]), _words(dev_cases["k"][:n])
+    out, _ = _run_dev(ctx, lambda o, t, s: ctx.gt_pow_many_dev(A.data_ptr(), K.data_ptr(), n, o, s), n, 48)
+    assert np.array_equal(out, dev_cases["pow"][:n])
+
+
 def test_rust_api_mirror_codec(kats):
     import substrate_bn as bn
     k = kats["g1_from_compressed"]
