@@ -326,12 +326,28 @@ int product_wide(bn_ctx* c, const uint32_t* in, size_t in_stride, SetSpan span, 
     }
 }
 
+// The next launch's stamp for the words k_seg_tail and k_fe_ds poll (one counter for both:
+// tail_epoch.h).  When the counter comes back to 1, both buffers are zeroed on the stream
+// the kernel is about to be launched on, in front of that launch (the stream is already
+// ordered after the workspace's previous user, ws_acquire): a word stamped in the last
+// cycle and not rewritten since would otherwise count as published by this one.
+static int tail_epoch_advance(bn_ctx* c, hipStream_t s) {
+    const TailEpochStep next = tail_epoch_next(c->tail_epoch, c->tail_epoch_wrap);
+    if (next.clear) {
+        HIPCHK(c, hipMemsetAsync(c->tail_ws, 0, (size_t)kTailWsWords * 4, s));
+        HIPCHK(c, hipMemsetAsync(c->fe_ds_ws, 0, (size_t)kFeDsMax * kFeDsWords * 4, s));
+    }
+    c->tail_epoch = next.epoch;
+    return BN_OK;
+}
+
 // k_fe_ds over n <= c->fe_ds_max split-layout values of f (stride n): three blocks per
 // value while they fit one round (one 84 KB block per CU), else one
-static void launch_fe_ds(bn_ctx* c, const uint32_t* f, size_t n, bn_gt* out, uint8_t* ok, hipStream_t s) {
-    c->tail_epoch = c->tail_epoch + 1 < (1u << 29) ? c->tail_epoch + 1 : 1u;
+static int launch_fe_ds(bn_ctx* c, const uint32_t* f, size_t n, bn_gt* out, uint8_t* ok, hipStream_t s) {
+    RET_IF(tail_epoch_advance(c, s));
     const int per = 3 * n * kLatPairs <= c->lat_w1_max ? 3 : 1;  // (lat_w1_max = CUs x kLatPairs)
     k_fe_ds<<<(unsigned)(per * n), kTailBlock, 0, s>>>(f, n, out, ok, c->d_err, c->fe_ds_ws, c->tail_epoch, per);
+    return BN_OK;
 }
 
 // ---- pairing_batch / miller_loop_batch: segmented Miller loop + device reduction
@@ -553,7 +569,7 @@ static int recombine_one(bn_ctx* c, const SegPlan& plan, int do_fe, bn_gt* d_out
     }();
     if (tree == 2 && fused && do_fe && plan.S >= 1) {
         // pairing_batch: the whole tail in one launch (kernels_tail.hip k_seg_tail)
-        c->tail_epoch = c->tail_epoch + 1 < (1u << 29) ? c->tail_epoch + 1 : 1u;  // (epoch * 8 fits the role word)
+        RET_IF(tail_epoch_advance(c, s));
         k_seg_tail<<<plan.S > 3 ? plan.S : 3, kTailBlock, 0, s>>>(g, plan, d_out, c->d_err,
                                                                   c->tail_ws, c->tail_epoch);
     } else if (tree == 2) {
@@ -697,7 +713,7 @@ int bn::prepare(bn_ctx* c, const bn_g1* d_p, const bn_g2* d_q, size_t m, int mod
 // (whose program reads and writes the slots from slot 0: f must be slot 0)
 int bn::run_fe(bn_ctx* c, const uint32_t* f, size_t n, const uint8_t* flags, bn_gt* out, uint8_t* ok, hipStream_t s) {
     if (n <= c->fe_ds_max && n <= c->fe_wide_max) {  // digit-sliced blocks per value (kernels_tail.hip k_fe_ds)
-        launch_fe_ds(c, f, n, out, ok, s);
+        RET_IF(launch_fe_ds(c, f, n, out, ok, s));
         HIPCHK(c, hipGetLastError());
         return BN_OK;
     }
@@ -885,6 +901,12 @@ int bn_ctx_create(int device, bn_ctx** out) {
         const size_t v = (size_t)strtoull(e, nullptr, 10);
         c->fe_ds_max = v < (size_t)kFeDsMax ? v : (size_t)kFeDsMax;
     }
+    // $BN254MI_TAIL_EPOCH_WRAP: the last stamp before the tail's counter returns to 1
+    // (tail_epoch.h); for the tests, which cannot make 2^29 launches
+    if (const char* e = getenv("BN254MI_TAIL_EPOCH_WRAP")) {
+        const unsigned long long v = strtoull(e, nullptr, 10);
+        if (tail_epoch_wrap_ok(v)) c->tail_epoch_wrap = (uint32_t)v;
+    }
     if (const char* e = getenv("BN254MI_PREPARE_WIDE_MAX")) c->prepare_wide_max = (size_t)strtoull(e, nullptr, 10);
     c->msm_g1.min = kMsmMinDefault;
     c->msm_g2.min = kMsmG2MinDefault;
@@ -1050,7 +1072,7 @@ static int pairing_many_dev_impl(bn_ctx* c, const bn_g1* d_p, const bn_g2* d_q, 
             // exponentiation on three digit-sliced blocks (kernels_tail.hip k_fe_ds)
             launch_latency(c, d_p + off, d_q + off, m, nullptr, slot_region(c, kRegionSeg), 0, s);
             HIPCHK(c, hipGetLastError());
-            launch_fe_ds(c, slot_region(c, kRegionSeg), m, d_out + off, nullptr, s);
+            RET_IF(launch_fe_ds(c, slot_region(c, kRegionSeg), m, d_out + off, nullptr, s));
             RET_IF(done(1));
             continue;
         }

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/bn254mi.h"
+#include "tail_epoch.h"
 
 // One group's settings and point buffers of the multi-scalar multiplication (P = bn_g1
 // or bn_g2): buckets the bucket sums, parts the segment and window partial sums, tmp
@@ -112,9 +113,12 @@ struct bn_ctx {
     int* d_err = nullptr;  // two words: the kernels' outcome bits, and those put aside by k_err_hold (capi_internal.h)
     // pairing_batch's one-launch tail (kernels_tail.hip k_seg_tail): its own words
     // (kTailWsWords, zeroed at creation), every word it polls stamped with the
-    // launch's epoch, so no clearing between products
+    // launch's epoch, so no clearing between products.  tail_epoch serves k_fe_ds too; it
+    // runs 1 .. tail_epoch_wrap and then returns to 1, and the launch that gets 1 again
+    // zeroes tail_ws and fe_ds_ws first (tail_epoch.h; $BN254MI_TAIL_EPOCH_WRAP, for tests)
     uint32_t* tail_ws = nullptr;
     uint32_t tail_epoch = 0;
+    uint32_t tail_epoch_wrap = bn::kTailEpochWrapDefault;
     // pairing_many of at most fe_ds_max pairs: k_pairing_latency's Miller values, then
     // k_fe_ds (three digit-sliced blocks per pair); its words (kFeDsMax pairs, zeroed)
     uint32_t* fe_ds_ws = nullptr;
