@@ -201,15 +201,7 @@ constexpr size_t kHostPiece = size_t(1) << 17;
 constexpr size_t kHostPieceSmall = size_t(1) << 16;
 // pinned bounce buffers of bn_pairing_many (grown, never shrunk); the caller
 // has drained the copy streams, which are the buffers' only device users
-int pin_reserve(bn_ctx* c, size_t bytes) {
-    if (bytes <= c->pin_bytes) return BN_OK;
-    if (c->pin) HIPCHK(c, hipHostFree(c->pin));
-    c->pin = nullptr;
-    c->pin_bytes = 0;
-    HIPCHK(c, hipHostMalloc(&c->pin, bytes, hipHostMallocDefault));
-    c->pin_bytes = bytes;
-    return BN_OK;
-}
+int pin_reserve(bn_ctx* c, size_t bytes) { return c->pin.grow(c, bytes); }
 // memcpy split over up to 8 host threads for large copies (a single thread
 // moves ~10 GB/s, a 2^16-pair piece is 44 MB)
 void par_copy(void* dst, const void* src, size_t bytes) {
@@ -647,37 +639,12 @@ bool use_latency_product(const bn_ctx* c, size_t n) {
 
 // ---- shared with capi_products.hip and capi_msm.hip (declared in capi_internal.h)
 int bn::reserve(bn_ctx* c, size_t n) {
-    if (n <= c->cap) return BN_OK;
-    n = n < 1024 ? 1024 : n;
-    if (c->cap) {
-        int r = ws_drain(c);
-        if (r) return r;
-    }
-    if (c->coeffs) HIPCHK(c, hipFree(c->coeffs));
-    if (c->paff) HIPCHK(c, hipFree(c->paff));
-    if (c->slots) HIPCHK(c, hipFree(c->slots));
-    if (c->flags) HIPCHK(c, hipFree(c->flags));
-    c->coeffs = nullptr; c->paff = nullptr; c->slots = nullptr; c->flags = nullptr; c->cap = 0;
-    HIPCHK(c, hipMalloc(&c->coeffs, n * (size_t)kCoeffFq * 9 * 4));
-    HIPCHK(c, hipMalloc(&c->paff, n * kPathLanes * 2 * 9 * 4));
-    HIPCHK(c, hipMalloc(&c->slots, n * (size_t)kFeSlots * kSlotWords * 4));
-    HIPCHK(c, hipMalloc(&c->flags, n * kPathLanes));
-    c->cap = n;
-    return BN_OK;
+    // per pairing: words of coeffs, paff and slots, bytes of flags
+    return grow_together(c, &c->cap, n, 1024,
+                         {(size_t)kCoeffFq * 9, (size_t)kPathLanes * 2 * 9, (size_t)kFeSlots * kSlotWords, (size_t)kPathLanes},
+                         c->coeffs, c->paff, c->slots, c->flags);
 }
-int bn::stage(bn_ctx* c, size_t bytes) {
-    if (bytes <= c->stage_bytes) return BN_OK;
-    if (c->stage) {
-        int r = ws_drain(c);
-        if (r) return r;
-        HIPCHK(c, hipFree(c->stage));
-    }
-    c->stage = nullptr;
-    c->stage_bytes = 0;
-    HIPCHK(c, hipMalloc(&c->stage, bytes));
-    c->stage_bytes = bytes;
-    return BN_OK;
-}
+int bn::stage(bn_ctx* c, size_t bytes) { return c->stage.grow(c, bytes); }
 
 // to_affine + the 87 line coefficients of m pairs into c->coeffs / paff / flags:
 // eight lanes per pair (k_prepare_wide, about a third of the step latency) while
@@ -939,13 +906,12 @@ int bn_ctx_create(int device, bn_ctx** out) {
         hipStreamCreateWithFlags(&c->h2d, hipStreamNonBlocking) != hipSuccess ||
         hipStreamCreateWithFlags(&c->d2h, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&c->ws_event, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->prod_off_event, hipEventDisableTiming) != hipSuccess ||
-        hipMalloc(&c->d_err, kErrWords * sizeof(int)) != hipSuccess ||
+        c->d_err.alloc(c, kErrWords) != BN_OK ||
         hipMemset(c->d_err, 0, kErrWords * sizeof(int)) != hipSuccess ||
-        hipMalloc(&c->tail_ws, kTailWsWords * 4) != hipSuccess || hipMemset(c->tail_ws, 0, kTailWsWords * 4) != hipSuccess ||
-        hipMalloc(&c->fe_ds_ws, (size_t)kFeDsMax * kFeDsWords * 4) != hipSuccess ||
+        c->tail_ws.alloc(c, kTailWsWords) != BN_OK || hipMemset(c->tail_ws, 0, kTailWsWords * 4) != hipSuccess ||
+        c->fe_ds_ws.alloc(c, (size_t)kFeDsMax * kFeDsWords) != BN_OK ||
         hipMemset(c->fe_ds_ws, 0, (size_t)kFeDsMax * kFeDsWords * 4) != hipSuccess ||
-        hipMalloc(&c->d_prog, P.s.size() * 4) != hipSuccess ||
+        c->d_prog.alloc(c, P.s.size()) != BN_OK ||
         hipMemcpy(c->d_prog, P.s.data(), P.s.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
         ctx_teardown(c);  // releases whatever was created (null handles are skipped)
         return BN_ERR_HIP;
@@ -963,61 +929,22 @@ int bn_ctx_destroy(bn_ctx* c) {
 
 }  // extern "C"
 
-// releases every resource of a single-device context (also a partially created
-// one: null handles are skipped) and deletes it
+// The ordered part of destroying a single-device context (also a partially created one:
+// null handles are skipped): its queued work awaited, then the events and streams that the
+// context holds by hand.  `delete c` frees everything else: the members own it (ctx_mem.h).
 static void ctx_teardown(bn_ctx* c) {
     (void)hipSetDevice(c->device);
     if (c->ws_pending) (void)hipEventSynchronize(c->ws_event);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (hipStream_t s : {c->h2d, c->d2h})
+    for (hipStream_t s : {c->stream, c->h2d, c->d2h})
         if (s) (void)hipStreamSynchronize(s);
-    if (c->ws_event) (void)hipEventDestroy(c->ws_event);
-    if (c->prod_off_event) (void)hipEventDestroy(c->prod_off_event);
-    if (c->prod_off_h) (void)hipHostFree(c->prod_off_h);
-    if (c->prod_off_d) (void)hipFree(c->prod_off_d);
-    if (c->prod_map_h) (void)hipHostFree(c->prod_map_h);
-    if (c->prod_map_d) (void)hipFree(c->prod_map_d);
-    if (c->prod_fresh) (void)hipFree(c->prod_fresh);
-    if (c->prod_gq) (void)hipFree(c->prod_gq);
-    if (c->many_words_event) (void)hipEventDestroy(c->many_words_event);
-    if (c->many_words_h) (void)hipHostFree(c->many_words_h);
-    for (void* p : {(void*)c->many_words_d, (void*)c->many_digits, (void*)c->many_table, (void*)c->many_parts})
-        if (p) (void)hipFree(p);
-    for (hipEvent_t e : {c->ev_in[0], c->ev_in[1], c->ev_comp[0], c->ev_comp[1], c->ev_out[0], c->ev_out[1]})
+    for (hipEvent_t e : {c->ws_event, c->ev_in[0], c->ev_in[1], c->ev_comp[0], c->ev_comp[1], c->ev_out[0], c->ev_out[1]})
         if (e) (void)hipEventDestroy(e);
-    if (c->pin) (void)hipHostFree(c->pin);
-    for (hipStream_t s : {c->h2d, c->d2h})
-        if (s) (void)hipStreamDestroy(s);
-    for (void* p : {(void*)c->coeffs, (void*)c->paff, (void*)c->slots, (void*)c->flags, (void*)c->d_err,
-                    (void*)c->d_prog, c->stage, (void*)c->tail_ws, (void*)c->fe_ds_ws, (void*)c->msm_keys,
-                    (void*)c->msm_sorted, (void*)c->msm_g1.buckets, (void*)c->msm_g1.parts, (void*)c->msm_g1.tmp,
-                    (void*)c->msm_g2.buckets, (void*)c->msm_g2.parts, (void*)c->msm_g2.tmp, (void*)c->msm_g1.fixed,
-                    (void*)c->msm_g1.run_a, (void*)c->msm_g1.run_b, (void*)c->msm_g2.run_a, (void*)c->msm_g2.run_b})
-        if (p) (void)hipFree(p);
-    for (bn_g2_prepared* h : c->prepared) {  // the handles still alive (the streams are drained)
-        if (h->table) (void)hipFree(h->table);
-        if (h->zero) (void)hipFree(h->zero);
-        if (h->points) (void)hipFree(h->points);
-        delete h;
-    }
-    c->prepared.clear();
-    for (bn_g1_prepared* h : c->g1_prepared) {
-        if (h->table) (void)hipFree(h->table);
-        if (h->zero) (void)hipFree(h->zero);
-        delete h;
-    }
-    c->g1_prepared.clear();
-    for (bn_g1_basis* h : c->g1_basis) {
-        if (h->table) (void)hipFree(h->table);
-        if (h->zero) (void)hipFree(h->zero);
-        delete h;
-    }
-    c->g1_basis.clear();
     for (auto& ev : c->ev_marks)
         for (auto e : ev) c->ev_pool.push_back(e);
     for (auto e : c->ev_pool)
         if (e) (void)hipEventDestroy(e);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
+    for (hipStream_t s : {c->h2d, c->d2h, c->stream})
+        if (s) (void)hipStreamDestroy(s);
     delete c;
 }
 
@@ -1213,15 +1140,15 @@ static int pairing_many_host(bn_ctx* c, const bn_g1* p, const bn_g2* q, size_t n
     auto drain = [&](size_t k) -> int {  // piece k's results: pinned -> caller
         const int b = (int)(k & 1);
         HIPCHK(c, hipEventSynchronize(c->ev_out[b]));
-        par_copy(out + k * piece, (uint8_t*)c->pin + b * half + o_out, rows(k) * sizeof(bn_gt));
+        par_copy(out + k * piece, c->pin + b * half + o_out, rows(k) * sizeof(bn_gt));
         return BN_OK;
     };
     for (size_t k = 0; k < np; ++k) {
         const int b = (int)(k & 1);
         const size_t off = k * piece, m = rows(k);
         if (k >= 2) RET_IF(drain(k - 2));  // frees pinned half b (and its D2H source)
-        uint8_t* hp = (uint8_t*)c->pin + b * half;
-        uint8_t* dp = (uint8_t*)c->stage + b * half;
+        uint8_t* hp = c->pin + b * half;
+        uint8_t* dp = c->stage + b * half;
         par_copy(hp, p + off, m * sizeof(bn_g1));
         par_copy(hp + o_q, q + off, m * sizeof(bn_g2));
         HIPCHK(c, hipStreamWaitEvent(c->h2d, c->ev_comp[b], 0));  // piece k-2 has read stage half b
@@ -1471,7 +1398,7 @@ int bn_fq12_op_many(bn_ctx* c, int op, const bn_gt* a, const bn_gt* b, size_t n,
     for (auto [off, m] : chunks(n)) {
         RET_IF(reserve(c, m));
         RET_IF(stage(c, m * 3 * sizeof(bn_gt) + 4096));
-        bn_gt* da = (bn_gt*)c->stage;
+        bn_gt* da = (bn_gt*)c->stage.get();
         bn_gt* db = da + m;
         bn_gt* dout = db + m;
         uint32_t* dprog = (uint32_t*)(dout + m);

@@ -1,6 +1,7 @@
 // capi_internal.h -- what the host units of the C ABI share (capi.hip, capi_products.hip,
-// capi_msm.hip): error plumbing, the workspace's ordering and growth, staging of host
-// buffers, the device outcome word.  Not a public header.
+// capi_msm.hip): the workspace's ordering, staging of host buffers, the device outcome
+// word.  Error plumbing and the owning types of the context's memory: ctx_mem.h.  Not a
+// public header.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <string.h>
@@ -15,23 +16,7 @@
 #pragma GCC visibility push(hidden)  // nothing here is part of the library's interface
 namespace bn {
 
-inline int fail(bn_ctx* c, int code, const std::string& msg) {
-    if (c) c->err = msg;
-    return code;
-}
-#define HIPCHK(ctx, x)                                                                   \
-    do {                                                                                 \
-        hipError_t e_ = (x);                                                             \
-        if (e_ != hipSuccess)                                                            \
-            return fail(ctx, BN_ERR_HIP, std::string(#x ": ") + hipGetErrorString(e_)); \
-    } while (0)
-
-#define RET_IF(x)              \
-    do {                       \
-        int r_ = (x);          \
-        if (r_) return r_;     \
-    } while (0)
-
+// (fail, HIPCHK, RET_IF and ws_drain: ctx_mem.h and ctx.h)
 // order this call's device work after the workspace's previous user (see bn_ctx)
 inline int ws_acquire(bn_ctx* c, hipStream_t s) {
     if (c->ws_pending) HIPCHK(c, hipStreamWaitEvent(s, c->ws_event, 0));
@@ -45,12 +30,6 @@ struct WsUse {
         if (hipEventRecord(c->ws_event, s) == hipSuccess) c->ws_pending = true;
     }
 };
-// before freeing workspace buffers: wait until no queued work can still read them
-inline int ws_drain(bn_ctx* c) {
-    if (c->ws_pending) HIPCHK(c, hipEventSynchronize(c->ws_event));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return BN_OK;
-}
 
 #define CTX_GUARD(ctx)                                 \
     if (!(ctx)) return BN_ERR_INVALID_ARGUMENT;        \
@@ -116,7 +95,7 @@ inline int stage_regions(bn_ctx* c, const size_t* bytes, size_t n, void** at) {
     size_t total = 0;
     for (size_t i = 0; i < n; ++i) total += round256(bytes[i]);
     RET_IF(stage(c, total));
-    uint8_t* p = (uint8_t*)c->stage;
+    uint8_t* p = c->stage;
     for (size_t i = 0; i < n; ++i) {
         at[i] = p;
         p += round256(bytes[i]);
@@ -126,34 +105,6 @@ inline int stage_regions(bn_ctx* c, const size_t* bytes, size_t n, void** at) {
 template <size_t N>
 int stage_regions(bn_ctx* c, const size_t (&bytes)[N], void* (&at)[N]) {
     return stage_regions(c, bytes, N, at);
-}
-
-// A device buffer of the context grown to `need` elements (at least `floor`; never
-// shrunk).  Queued kernels may still read the old buffer, so growing drains first:
-// when there is an old buffer, or always (drain_always: the products' buffers).
-template <class T>
-int grow_dev(bn_ctx* c, T** buf, size_t* cap, size_t need, size_t floor = 0, bool drain_always = false) {
-    if (need <= *cap) return BN_OK;
-    if (*buf || drain_always) RET_IF(ws_drain(c));
-    if (*buf) HIPCHK(c, hipFree(*buf));
-    *buf = nullptr;
-    *cap = 0;
-    need = std::max(need, floor);
-    HIPCHK(c, hipMalloc((void**)buf, need * sizeof(T)));
-    *cap = need;
-    return BN_OK;
-}
-// the same for a pinned source and its device copy (one capacity for both)
-inline int grow_pinned_pair(bn_ctx* c, uint32_t** h, uint32_t** d, size_t* cap, size_t words) {
-    if (words <= *cap) return BN_OK;
-    size_t n = *cap;
-    *cap = 0;
-    RET_IF(grow_dev(c, d, &n, words, 4096, true));
-    if (*h) HIPCHK(c, hipHostFree(*h));
-    *h = nullptr;
-    HIPCHK(c, hipHostMalloc(h, n * 4, hipHostMallocDefault));
-    *cap = n;
-    return BN_OK;
 }
 
 // The device outcome word is two: d_err[0], which the kernels set, and d_err[1], where

@@ -119,14 +119,14 @@ static MsmPlan msm_plan(bn_ctx* c, size_t n) {
 template <class P>
 static int msm_reserve(bn_ctx* c, size_t n, const MsmPlan& m) {
     MsmGroupWs<P>& g = MsmGroup<P>::ws(c);
-    if (m.small) return grow_dev(c, &g.tmp, &g.tmp_cap, n);
+    if (m.small) return g.tmp.grow(c, n);
     // counts | cursors | offsets (nkeys + 1) | the count of long keys | the long keys
-    RET_IF(grow_dev(c, &c->msm_keys, &c->msm_keys_cap, 4 * (size_t)m.nkeys + 2));
-    RET_IF(grow_dev(c, &c->msm_sorted, &c->msm_sorted_cap, m.nent));
-    RET_IF(grow_dev(c, &g.buckets, &g.buckets_cap, (size_t)m.nkeys));
-    RET_IF(grow_dev(c, &g.run_a, &g.run_a_cap, m.slots_a));
-    RET_IF(grow_dev(c, &g.run_b, &g.run_b_cap, m.slots_b));
-    return grow_dev(c, &g.parts, &g.parts_cap, (size_t)m.nseg * m.nwin);
+    RET_IF(c->msm_keys.grow(c, 4 * (size_t)m.nkeys + 2));
+    RET_IF(c->msm_sorted.grow(c, m.nent));
+    RET_IF(g.buckets.grow(c, (size_t)m.nkeys));
+    RET_IF(g.run_a.grow(c, m.slots_a));
+    RET_IF(g.run_b.grow(c, m.slots_b));
+    return g.parts.grow(c, (size_t)m.nseg * m.nwin);
 }
 // buf[0 .. width) = sum of the m rows of `width` points at buf by a halving addition tree in
 // place (odd tail carried)
@@ -166,12 +166,47 @@ static void msm_folds(bn_ctx* c, const MsmPlan& m, const uint32_t* offsets, cons
     for (int lv = 1; lv <= m.levels; ++lv) {
         P* src = lv & 1 ? g.run_a : g.run_b;
         P* dst = lv & 1 ? g.run_b : g.run_a;
-        const size_t cap = lv == m.levels ? 0 : (lv & 1 ? g.run_b_cap : g.run_a_cap);  // the last level writes buckets only
+        const size_t cap = lv == m.levels ? 0 : (lv & 1 ? g.run_b.cap() : g.run_a.cap());  // the last level writes buckets only
         const uint32_t slots = msm_level_slots(nent, m.nkeys, m.L, lv);
         const uint32_t ndst = (uint32_t)std::min<size_t>(slots, cap);
         G::k_fold<<<grid_for(G::kLanes * (size_t)slots), kBlock, 0, s>>>(src, nsrc, offsets, longinfo, m.nkeys, nent, m.L, lv, dst, ndst, slots, g.buckets);
         nsrc = ndst;
     }
+}
+// The bucket path's front half on s, shared by its two forms: msm_keys carved into counts |
+// cursors | offsets | longinfo, then the entries of n terms counted, scanned and scattered
+// into msm_sorted by key.  count and scatter are the form's kernels, src their first argument
+// (the points, or a basis handle's zero flags).
+struct MsmKeys {
+    uint32_t *offsets, *longinfo;
+    uint32_t nent;
+};
+template <class Count, class Scatter, class Src>
+static int msm_sort(bn_ctx* c, const MsmPlan& m, Count count, Scatter scatter, Src src, const bn_fr* d_k, size_t n,
+                    hipStream_t s, MsmKeys* k) {
+    uint32_t* counts = c->msm_keys;
+    uint32_t* cursors = counts + m.nkeys;
+    k->offsets = cursors + m.nkeys;
+    k->longinfo = k->offsets + m.nkeys + 1;
+    k->nent = (uint32_t)m.nent;
+    HIPCHK(c, hipMemsetAsync(counts, 0, (size_t)m.nkeys * 4, s));
+    count<<<grid_for(n), kBlock, 0, s>>>(src, d_k, n, m.c, m.nkeys, counts);
+    k_msm_scan<<<1, kMsmScanBlock, 0, s>>>(counts, m.nkeys, k->offsets, cursors, m.L, k->longinfo);
+    scatter<<<grid_for(n), kBlock, 0, s>>>(src, d_k, n, m.c, m.nkeys, cursors, k->offsets, c->msm_sorted, k->nent);
+    return BN_OK;
+}
+// The runs above the cap, behind the form's accumulate: their chunks (chunk(grid, ...) launches
+// the form's kernel behind its own leading arguments), then one fold launch per level the
+// largest run n terms can have needs; every grid is the host's bound for its level, and a
+// lane whose slot no long key holds returns.  Even levels write run_a, odd ones run_b.
+template <class P, class Chunk>
+static void msm_long_runs(bn_ctx* c, const MsmPlan& m, const MsmKeys& k, hipStream_t s, Chunk&& chunk) {
+    if (!m.levels) return;
+    MsmGroupWs<P>& g = MsmGroup<P>::ws(c);
+    const uint32_t s0 = (uint32_t)std::min(m.slots_a, g.run_a.cap());
+    chunk(grid_for(MsmGroup<P>::kLanes * (size_t)s0), c->msm_sorted.get(), k.offsets, k.longinfo, m.nkeys, k.nent, m.L,
+          g.run_a.get(), s0);
+    msm_folds<P>(c, m, k.offsets, k.longinfo, s0, s);
 }
 // the device sequence on stream s; the caller holds the lock and the workspace order.
 // The group-law kernels take G::kLanes lanes per element (kBlock is even: whole pairs).
@@ -190,29 +225,15 @@ static int msm_dev_impl(bn_ctx* c, const P* d_p, const bn_fr* d_k, size_t n, P* 
     MsmGroupWs<P>& g = G::ws(c);
     if (m.small) {
         G::mul(d_p, d_k, n, g.tmp, s);
-        RET_IF(msm_tree_out(c, g.tmp, n, 1, finish, d_out, s));
+        RET_IF(msm_tree_out(c, g.tmp.get(), n, 1, finish, d_out, s));
         HIPCHK(c, hipGetLastError());
         return BN_OK;
     }
-    uint32_t* counts = c->msm_keys;
-    uint32_t* cursors = counts + m.nkeys;
-    uint32_t* offsets = cursors + m.nkeys;
-    const uint32_t nent = (uint32_t)m.nent;
     const size_t nparts = (size_t)m.nseg * m.nwin;
-    HIPCHK(c, hipMemsetAsync(counts, 0, (size_t)m.nkeys * 4, s));
-    G::k_count<<<grid_for(n), kBlock, 0, s>>>(d_p, d_k, n, m.c, m.nkeys, counts);
-    uint32_t* longinfo = offsets + m.nkeys + 1;
-    k_msm_scan<<<1, kMsmScanBlock, 0, s>>>(counts, m.nkeys, offsets, cursors, m.L, longinfo);
-    G::k_scatter<<<grid_for(n), kBlock, 0, s>>>(d_p, d_k, n, m.c, m.nkeys, cursors, offsets, c->msm_sorted, nent);
-    G::k_accumulate<<<grid_for(G::kLanes * m.nkeys), kBlock, 0, s>>>(d_p, n, c->msm_sorted, offsets, m.nkeys, nent, m.L, g.buckets);
-    if (m.levels) {
-        // The runs above the cap: their chunks, then one fold launch per level the largest
-        // run n terms can have needs; every grid is the host's bound for its level, and a
-        // lane whose slot no long key holds returns.  Even levels write run_a, odd ones run_b.
-        const uint32_t s0 = (uint32_t)std::min(m.slots_a, g.run_a_cap);
-        G::k_chunk<<<grid_for(G::kLanes * (size_t)s0), kBlock, 0, s>>>(d_p, n, c->msm_sorted, offsets, longinfo, m.nkeys, nent, m.L, g.run_a, s0);
-        msm_folds<P>(c, m, offsets, longinfo, s0, s);
-    }
+    MsmKeys k;
+    RET_IF(msm_sort(c, m, G::k_count, G::k_scatter, d_p, d_k, n, s, &k));
+    G::k_accumulate<<<grid_for(G::kLanes * m.nkeys), kBlock, 0, s>>>(d_p, n, c->msm_sorted, k.offsets, m.nkeys, k.nent, m.L, g.buckets);
+    msm_long_runs<P>(c, m, k, s, [&](auto grid, auto... a) { G::k_chunk<<<grid, kBlock, 0, s>>>(d_p, n, a...); });
     G::k_reduce<<<grid_for(G::kLanes * nparts), kBlock, 0, s>>>(g.buckets, m.c, m.nkeys, m.nseg, g.parts);
     RET_IF(msm_tree_out<P>(c, g.parts, m.nseg, m.nwin, 0, nullptr, s));
     G::k_horner<<<1, 64, 0, s>>>(g.parts, m.c, finish, d_out);
@@ -246,10 +267,10 @@ static int msm_sum_host(bn_ctx* c, const P* a, size_t m, P* out) {
     CTX_GUARD_HOST(c);
     if (!out || (m && !a)) return fail(c, BN_ERR_INVALID_ARGUMENT, "null buffer");
     MsmGroupWs<P>& g = MsmGroup<P>::ws(c);
-    RET_IF(grow_dev(c, &g.tmp, &g.tmp_cap, m + 1));
+    RET_IF(g.tmp.grow(c, m + 1));
     P* dout = g.tmp + m;
     if (m) HIPCHK(c, hipMemcpyAsync(g.tmp, a, m * sizeof(P), hipMemcpyHostToDevice, c->stream));
-    RET_IF(msm_tree_out(c, g.tmp, m, 1, 1, dout, c->stream));
+    RET_IF(msm_tree_out(c, g.tmp.get(), m, 1, 1, dout, c->stream));
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(out, dout, sizeof(P), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -276,15 +297,11 @@ static int msm_reserve_terms(bn_ctx* c, size_t n) {
     RET_IF(msm_reserve<P>(c, n, m));
     // and the partial sums of the prepared-bases MSM for calls of up to n lanes (G1 only)
     if constexpr (std::is_same<P, bn_g1>::value)
-        return grow_dev(c, &c->msm_g1.fixed, &c->msm_g1.fixed_cap, std::min(n, kFixedSetLanes));
+        return c->msm_g1.fixed.grow(c, std::min(n, kFixedSetLanes));
     return BN_OK;
 }
 
 // ---------------------------------------------------------------- prepared bases
-// a live handle of this context (looked up, not dereferenced)
-static bool g1_prepared_live(const bn_ctx* c, const bn_g1_prepared* h) {
-    return h && std::find(c->g1_prepared.begin(), c->g1_prepared.end(), h) != c->g1_prepared.end();
-}
 // refused before anything is read: a NULL bases or out, a width outside 2 .. 16 (0: the
 // default), a k that is 0 or whose table exceeds the 32-bit entry indices
 static int g1_prepare_args(bn_ctx* c, const void* bases, size_t k, int cw, bn_g1_prepared** out) {
@@ -298,8 +315,8 @@ static int g1_prepare_args(bn_ctx* c, const void* bases, size_t k, int cw, bn_g1
 // The caller holds the lock and has ordered s after the workspace's previous user (the host
 // form stages the bases).
 static int g1_prepare_fill(bn_ctx* c, bn_g1_prepared* h, const bn_g1* bases, bool dev, hipStream_t s) {
-    HIPCHK(c, hipMalloc(&h->table, (size_t)h->nent * 2 * sizeof(bn_fq)));
-    HIPCHK(c, hipMalloc(&h->zero, h->k));
+    RET_IF(h->table.alloc(c, (size_t)h->nent * 2));
+    RET_IF(h->zero.alloc(c, h->k));
     const bn_g1* d = bases;
     if (!dev) {
         void* at[1];
@@ -313,26 +330,16 @@ static int g1_prepare_fill(bn_ctx* c, bn_g1_prepared* h, const bn_g1* bases, boo
     return BN_OK;
 }
 static int g1_prepare(bn_ctx* c, const bn_g1* bases, bool dev, size_t k, int cw, bn_g1_prepared** out, hipStream_t s) {
-    bn_g1_prepared* h = new bn_g1_prepared();
+    auto h = std::make_unique<bn_g1_prepared>();
     h->k = k;
     h->c = cw ? cw : kMsmFixedWindow;
     h->nent = (uint32_t)msm_fixed_entries(k, h->c);
-    int rc = g1_prepare_fill(c, h, bases, dev, s);
-    if (rc == BN_OK && !dev && hipStreamSynchronize(s) != hipSuccess) rc = fail(c, BN_ERR_HIP, "hipStreamSynchronize");
-    if (rc != BN_OK) {
-        (void)hipStreamSynchronize(s);  // nothing queued may still write the table
-        if (h->table) (void)hipFree(h->table);
-        if (h->zero) (void)hipFree(h->zero);
-        delete h;
-        return rc;
-    }
-    c->g1_prepared.push_back(h);
-    *out = h;
-    return BN_OK;
+    const int rc = g1_prepare_fill(c, h.get(), bases, dev, s);
+    return c->g1_prepared.settle(c, std::move(h), rc, !dev, s, out);
 }
 static int msm_prepared_args(bn_ctx* c, const bn_g1_prepared* h, const void* k, size_t m, const void* out,
                              size_t out_stride) {
-    if (!g1_prepared_live(c, h)) return fail(c, BN_ERR_INVALID_ARGUMENT, "not a live prepared handle of this context");
+    if (!c->g1_prepared.live(h)) return fail(c, BN_ERR_INVALID_ARGUMENT, "not a live prepared handle of this context");
     if (out_stride == 0) return fail(c, BN_ERR_INVALID_ARGUMENT, "out_stride is 0");
     if (m > kMsmMaxTerms) return fail(c, BN_ERR_INVALID_ARGUMENT, "more than 2^26 outputs");
     if (m && (!k || !out)) return fail(c, BN_ERR_INVALID_ARGUMENT, "null buffer");
@@ -345,12 +352,12 @@ static int msm_prepared_dev_impl(bn_ctx* c, const bn_g1_prepared* h, const bn_fr
     MsmGroupWs<bn_g1>& g = c->msm_g1;
     const uint32_t L = g.fixed_lanes ? (uint32_t)g.fixed_lanes : msm_fixed_auto_lanes(m, h->k, h->c);
     const size_t set = std::max<size_t>(1, kFixedSetLanes / L);
-    RET_IF(grow_dev(c, &g.fixed, &g.fixed_cap, std::min(m, set) * L));
+    RET_IF(g.fixed.grow(c, std::min(m, set) * L));
     for (size_t off = 0; off < m; off += set) {
         const size_t mc = std::min(m - off, set);
         k_g1_msm_fixed<<<grid_for(mc * L), kBlock, 0, s>>>(h->table, h->zero, h->nent, (uint32_t)h->k, h->c,
                                                            d_k + off * h->k, mc, L, g.fixed);
-        msm_tree(g.fixed, L, mc, s);
+        msm_tree(g.fixed.get(), L, mc, s);
         k_g1_msm_fixed_finish<<<grid_for(mc), kBlock, 0, s>>>(g.fixed, mc, d_out + off * out_stride, out_stride);
     }
     HIPCHK(c, hipGetLastError());
@@ -358,10 +365,6 @@ static int msm_prepared_dev_impl(bn_ctx* c, const bn_g1_prepared* h, const bn_fr
 }
 
 // ---------------------------------------------------------------- one large MSM over a fixed basis
-// a live handle of this context (looked up, not dereferenced)
-static bool g1_basis_live(const bn_ctx* c, const bn_g1_basis* h) {
-    return h && std::find(c->g1_basis.begin(), c->g1_basis.end(), h) != c->g1_basis.end();
-}
 // refused before anything is read: a NULL bases or out, a width outside 2 .. 16 (0: the
 // default), an nbases that is 0, above 2^26 or whose nbases * W(c) exceeds the 32-bit positions
 static int g1_basis_args(bn_ctx* c, const void* bases, size_t nbases, int cw, bn_g1_basis** out) {
@@ -371,41 +374,33 @@ static int g1_basis_args(bn_ctx* c, const void* bases, size_t nbases, int cw, bn
         return fail(c, BN_ERR_INVALID_ARGUMENT, "nbases is 0, above 2^26, or nbases * windows exceeds 2^31 - 1");
     return BN_OK;
 }
-// A new handle filled on stream s from the bases (host memory, or device memory when dev).
+// Fills a new handle on stream s from the bases (host memory, or device memory when dev).
 // The caller holds the lock and has ordered s after the workspace's previous user (the host
-// form stages the bases, and waits for the build).
-static int g1_basis_make(bn_ctx* c, const bn_g1* bases, bool dev, size_t nbases, int cw, bn_g1_basis** out, hipStream_t s) {
-    bn_g1_basis* h = new bn_g1_basis();
-    h->nbases = nbases;
-    h->c = cw ? cw : msm_basis_auto_window(nbases);
-    int rc = [&]() -> int {
-        HIPCHK(c, hipMalloc(&h->table, (size_t)msm_basis_entries(nbases, h->c) * 2 * sizeof(bn_fq)));
-        HIPCHK(c, hipMalloc(&h->zero, nbases));
-        const bn_g1* d = bases;
-        if (!dev) {
-            void* at[1];
-            RET_IF(stage_regions(c, {nbases * sizeof(bn_g1)}, at));
-            HIPCHK(c, hipMemcpyAsync(at[0], bases, nbases * sizeof(bn_g1), hipMemcpyHostToDevice, s));
-            d = (const bn_g1*)at[0];
-        }
-        k_g1_basis_build<<<grid_for(nbases), kBlock, 0, s>>>(d, (uint32_t)nbases, h->c, h->table, h->zero);
-        HIPCHK(c, hipGetLastError());
-        if (!dev) HIPCHK(c, hipStreamSynchronize(s));
-        return BN_OK;
-    }();
-    if (rc != BN_OK) {
-        (void)hipStreamSynchronize(s);  // nothing queued may still write the table
-        if (h->table) (void)hipFree(h->table);
-        if (h->zero) (void)hipFree(h->zero);
-        delete h;
-        return rc;
+// form stages the bases).
+static int g1_basis_fill(bn_ctx* c, bn_g1_basis* h, const bn_g1* bases, bool dev, hipStream_t s) {
+    const size_t nbases = h->nbases;
+    RET_IF(h->table.alloc(c, (size_t)msm_basis_entries(nbases, h->c) * 2));
+    RET_IF(h->zero.alloc(c, nbases));
+    const bn_g1* d = bases;
+    if (!dev) {
+        void* at[1];
+        RET_IF(stage_regions(c, {nbases * sizeof(bn_g1)}, at));
+        HIPCHK(c, hipMemcpyAsync(at[0], bases, nbases * sizeof(bn_g1), hipMemcpyHostToDevice, s));
+        d = (const bn_g1*)at[0];
     }
-    c->g1_basis.push_back(h);
-    *out = h;
+    k_g1_basis_build<<<grid_for(nbases), kBlock, 0, s>>>(d, (uint32_t)nbases, h->c, h->table, h->zero);
+    HIPCHK(c, hipGetLastError());
     return BN_OK;
 }
+static int g1_basis_make(bn_ctx* c, const bn_g1* bases, bool dev, size_t nbases, int cw, bn_g1_basis** out, hipStream_t s) {
+    auto h = std::make_unique<bn_g1_basis>();
+    h->nbases = nbases;
+    h->c = cw ? cw : msm_basis_auto_window(nbases);
+    const int rc = g1_basis_fill(c, h.get(), bases, dev, s);
+    return c->g1_basis.settle(c, std::move(h), rc, !dev, s, out);
+}
 static int msm_basis_args(bn_ctx* c, const bn_g1_basis* h, const void* k, size_t n, const void* out) {
-    if (!g1_basis_live(c, h)) return fail(c, BN_ERR_INVALID_ARGUMENT, "not a live basis handle of this context");
+    if (!c->g1_basis.live(h)) return fail(c, BN_ERR_INVALID_ARGUMENT, "not a live basis handle of this context");
     if (!out) return fail(c, BN_ERR_INVALID_ARGUMENT, "null buffer");
     if (n > h->nbases) return fail(c, BN_ERR_INVALID_ARGUMENT, "more terms than the handle has bases");
     if (n && !k) return fail(c, BN_ERR_INVALID_ARGUMENT, "null buffer");
@@ -425,29 +420,20 @@ static int msm_basis_dev_impl(bn_ctx* c, const bn_g1_basis* h, const bn_fr* d_k,
     const MsmPlan m = msm_basis_plan(c, h, n);
     RET_IF(msm_reserve<bn_g1>(c, n, m));
     MsmGroupWs<bn_g1>& g = c->msm_g1;
-    uint32_t* counts = c->msm_keys;
-    uint32_t* cursors = counts + m.nkeys;
-    uint32_t* offsets = cursors + m.nkeys;
-    uint32_t* longinfo = offsets + m.nkeys + 1;
-    const uint32_t nent = (uint32_t)m.nent, nb = msm_buckets(m.c), nbases = (uint32_t)h->nbases;
-    HIPCHK(c, hipMemsetAsync(counts, 0, (size_t)m.nkeys * 4, s));
-    k_msm_count_basis<<<grid_for(n), kBlock, 0, s>>>(h->zero, d_k, n, m.c, m.nkeys, counts);
-    k_msm_scan<<<1, kMsmScanBlock, 0, s>>>(counts, m.nkeys, offsets, cursors, m.L, longinfo);
-    k_msm_scatter_basis<<<grid_for(n), kBlock, 0, s>>>(h->zero, d_k, n, m.c, m.nkeys, cursors, offsets, c->msm_sorted, nent);
-    k_msm_basis_accumulate<<<grid_for(m.nkeys), kBlock, 0, s>>>(h->table, nbases, (uint32_t)n, m.c, c->msm_sorted, offsets,
-                                                                m.nkeys, nent, m.L, g.buckets);
-    if (m.levels) {
-        const uint32_t s0 = (uint32_t)std::min(m.slots_a, g.run_a_cap);
-        k_msm_basis_chunk<<<grid_for(s0), kBlock, 0, s>>>(h->table, nbases, (uint32_t)n, m.c, c->msm_sorted, offsets, longinfo,
-                                                          m.nkeys, nent, m.L, g.run_a, s0);
-        msm_folds<bn_g1>(c, m, offsets, longinfo, s0, s);
-    }
+    const uint32_t nb = msm_buckets(m.c), nbases = (uint32_t)h->nbases;
+    MsmKeys k;
+    RET_IF(msm_sort(c, m, k_msm_count_basis, k_msm_scatter_basis, h->zero.get(), d_k, n, s, &k));
+    k_msm_basis_accumulate<<<grid_for(m.nkeys), kBlock, 0, s>>>(h->table, nbases, (uint32_t)n, m.c, c->msm_sorted, k.offsets,
+                                                                m.nkeys, k.nent, m.L, g.buckets);
+    msm_long_runs<bn_g1>(c, m, k, s, [&](auto grid, auto... a) {
+        k_msm_basis_chunk<<<grid, kBlock, 0, s>>>(h->table.get(), nbases, (uint32_t)n, m.c, a...);
+    });
     // Every window's bucket j weighs j + 1 but the top one's, whose slots are replicas: the rows
     // of the windows below it are added into window 0's row, and two windows are reduced.
-    msm_tree(g.buckets, m.nwin - 1, nb, s);
+    msm_tree(g.buckets.get(), m.nwin - 1, nb, s);
     k_msm_basis_reduce<<<grid_for(2 * (size_t)m.nseg), kBlock, 0, s>>>(g.buckets, m.c, m.nkeys, m.nseg, g.parts);
-    msm_tree(g.parts, m.nseg, 2, s);
-    msm_tree(g.parts, 2, 1, s);  // the two window sums: no weight between them, nothing is doubled
+    msm_tree(g.parts.get(), m.nseg, 2, s);
+    msm_tree(g.parts.get(), 2, 1, s);  // the two window sums: no weight between them, nothing is doubled
     k_msm_finish<<<1, 64, 0, s>>>(g.parts, d_out);
     HIPCHK(c, hipGetLastError());
     return BN_OK;
@@ -481,14 +467,10 @@ static MsmManyLimits many_limits(const bn_ctx* c) {
 // the words of a call
 static int many_grow(bn_ctx* c, size_t nt, size_t nu, size_t words) {
     const int cw = many_window(c);
-    RET_IF(grow_dev(c, &c->many_digits, &c->many_digits_cap, (size_t)msm_many_digits(nt, cw)));
-    RET_IF(grow_dev(c, &c->many_table, &c->many_table_cap, (size_t)msm_many_entries(nt, cw)));
-    RET_IF(grow_dev(c, &c->many_parts, &c->many_parts_cap, nu));
-    if (words && c->many_words_pending) {  // the pinned source may be replaced
-        HIPCHK(c, hipEventSynchronize(c->many_words_event));
-        c->many_words_pending = false;
-    }
-    return grow_pinned_pair(c, &c->many_words_h, &c->many_words_d, &c->many_words_cap, words);
+    RET_IF(c->many_digits.grow(c, (size_t)msm_many_digits(nt, cw)));
+    RET_IF(c->many_table.grow(c, (size_t)msm_many_entries(nt, cw)));
+    RET_IF(c->many_parts.grow(c, nu));
+    return c->many_words.grow(c, c->many_fence, words);
 }
 // Refusals, before any point buffer is read (offsets is the host's control array).  m is
 // not 0.
@@ -497,21 +479,14 @@ static int many_args(bn_ctx* c, const void* p, const void* k, const size_t* off,
     if (!out || (off[m] && (!p || !k))) return fail(c, BN_ERR_INVALID_ARGUMENT, "null buffer");
     return BN_OK;
 }
-// The words of every launch set of the call -> many_words_d in one copy on s in front of the
+// The words of every launch set of the call -> many_words.d in one copy on s in front of the
 // call's kernels.  The pinned source is rewritten by the next call, which first waits for
-// this copy (not for the kernels behind it).
+// this copy (not for the kernels behind it); many_grow has waited for the last call's.
 static int many_upload(bn_ctx* c, const MsmManyPlan& plan, const size_t* off, hipStream_t s) {
     if (!plan.words) return BN_OK;
-    if (!c->many_words_event) HIPCHK(c, hipEventCreateWithFlags(&c->many_words_event, hipEventDisableTiming));
-    if (c->many_words_pending) {
-        HIPCHK(c, hipEventSynchronize(c->many_words_event));
-        c->many_words_pending = false;
-    }
-    msm_many_fill(plan, off, c->many_words_h);
-    HIPCHK(c, hipMemcpyAsync(c->many_words_d, c->many_words_h, plan.words * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipEventRecord(c->many_words_event, s));
-    c->many_words_pending = true;
-    return BN_OK;
+    msm_many_fill(plan, off, c->many_words.h);
+    RET_IF(c->many_words.copy(c, plan.words, s));
+    return c->many_fence.record(c, s);
 }
 // the device sequence on stream s: every packed item as one launch set through the shared
 // buffers, every other segment through bn_g1_msm's path into its own output; the caller holds
@@ -522,7 +497,6 @@ static int many_dev_impl(bn_ctx* c, const bn_g1* d_p, const bn_fr* d_k, const si
     const MsmManyPlan plan = msm_many_plan(many_limits(c), off, m);
     if (plan.set_terms > 0xffffffffull || plan.set_units > 0xffffffffull)
         return fail(c, BN_ERR_INTERNAL, "launch set exceeds its 32-bit offsets");
-    if (!c->many_words_event) HIPCHK(c, hipEventCreateWithFlags(&c->many_words_event, hipEventDisableTiming));
     RET_IF(many_grow(c, plan.set_terms, plan.set_units, plan.words));
     RET_IF(many_upload(c, plan, off, s));
     for (const MsmManyItem& it : plan.items) {
@@ -531,9 +505,9 @@ static int many_dev_impl(bn_ctx* c, const bn_g1* d_p, const bn_fr* d_k, const si
             RET_IF(msm_dev_impl(c, d_p + lo, d_k + lo, nt, d_out + it.j0 * out_stride, s, 1));
             continue;
         }
-        if (nt > c->many_table_cap >> (cw - 1) || it.units > c->many_parts_cap)
+        if (nt > c->many_table.cap() >> (cw - 1) || it.units > c->many_parts.cap())
             return fail(c, BN_ERR_INTERNAL, "launch set exceeds the workspace");
-        const uint32_t* unit_off = c->many_words_d + it.words_at;
+        const uint32_t* unit_off = c->many_words.d + it.words_at;
         if (nt) {
             k_g1_msm_many_table<<<grid_for(nt), kBlock, 0, s>>>(d_p + lo, d_k + lo, (uint32_t)nt, cw, c->many_digits,
                                                                 c->many_table);
@@ -572,13 +546,7 @@ size_t bn_g1_prepared_count(const bn_g1_prepared* h) { return h ? h->k : 0; }
 int bn_g1_prepared_window(const bn_g1_prepared* h) { return h ? h->c : 0; }
 int bn_g1_prepared_destroy(bn_ctx* c, bn_g1_prepared* h) {
     CTX_GUARD(c);
-    if (!g1_prepared_live(c, h)) return fail(c, BN_ERR_INVALID_ARGUMENT, "not a live prepared handle of this context");
-    RET_IF(ws_drain(c));  // every call that reads the table has recorded ws_event behind its work
-    c->g1_prepared.erase(std::find(c->g1_prepared.begin(), c->g1_prepared.end(), h));
-    (void)hipFree(h->table);
-    (void)hipFree(h->zero);
-    delete h;
-    return BN_OK;
+    return c->g1_prepared.destroy(c, h, "not a live prepared handle of this context");
 }
 int bn_g1_msm_prepared_many(bn_ctx* c, const bn_g1_prepared* h, const bn_fr* k, size_t m, bn_g1* out, size_t out_stride) {
     CTX_GUARD_HOST(c);
@@ -626,13 +594,7 @@ size_t bn_g1_basis_count(const bn_g1_basis* h) { return h ? h->nbases : 0; }
 int bn_g1_basis_window(const bn_g1_basis* h) { return h ? h->c : 0; }
 int bn_g1_basis_destroy(bn_ctx* c, bn_g1_basis* h) {
     CTX_GUARD(c);
-    if (!g1_basis_live(c, h)) return fail(c, BN_ERR_INVALID_ARGUMENT, "not a live basis handle of this context");
-    RET_IF(ws_drain(c));  // every call that reads the table has recorded ws_event behind its work
-    c->g1_basis.erase(std::find(c->g1_basis.begin(), c->g1_basis.end(), h));
-    (void)hipFree(h->table);
-    (void)hipFree(h->zero);
-    delete h;
-    return BN_OK;
+    return c->g1_basis.destroy(c, h, "not a live basis handle of this context");
 }
 int bn_g1_msm_basis(bn_ctx* c, const bn_g1_basis* h, const bn_fr* k, size_t n, bn_g1* out) {
     CTX_GUARD_HOST(c);
@@ -655,7 +617,7 @@ int bn_g1_msm_basis_dev(bn_ctx* c, const bn_g1_basis* h, const bn_fr* d_k, size_
 }
 int bn_g1_msm_basis_reserve(bn_ctx* c, const bn_g1_basis* h, size_t n) {
     CTX_GUARD(c);
-    if (!g1_basis_live(c, h)) return fail(c, BN_ERR_INVALID_ARGUMENT, "not a live basis handle of this context");
+    if (!c->g1_basis.live(h)) return fail(c, BN_ERR_INVALID_ARGUMENT, "not a live basis handle of this context");
     if (n > h->nbases) return fail(c, BN_ERR_INVALID_ARGUMENT, "more terms than the handle has bases");
     if (n == 0) return BN_OK;
     return msm_reserve<bn_g1>(c, n, msm_basis_plan(c, h, n));

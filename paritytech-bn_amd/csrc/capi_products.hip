@@ -36,27 +36,20 @@ static int products_reserve(bn_ctx* c, const size_t* off, const ProductsPlan& pl
     }
     return reserve(c, need);
 }
-// The words of every launch set of the call (products_fill) -> prod_off_d and, with qidx,
-// prod_map_d, in one copy each on s in front of the call's kernels.  The pinned sources are
-// rewritten by the next call, which first waits for these copies (one event for both; not
+// The words of every launch set of the call (products_fill) -> prod_off.d and, with qidx,
+// prod_map.d, in one copy each on s in front of the call's kernels.  The pinned sources are
+// rewritten by the next call, which first waits for these copies (one fence for both; not
 // for the kernels behind them).  The caller has ordered s after the workspace's previous user.
 static int products_upload(bn_ctx* c, const ProductsPlan& plan, const size_t* off, const uint32_t* qidx,
                            bool compact_p, hipStream_t s) {
     if (!plan.off_words) return BN_OK;
-    if (c->prod_off_pending) {
-        HIPCHK(c, hipEventSynchronize(c->prod_off_event));
-        c->prod_off_pending = false;
-    }
-    RET_IF(grow_pinned_pair(c, &c->prod_off_h, &c->prod_off_d, &c->prod_off_cap, plan.off_words));
-    RET_IF(grow_pinned_pair(c, &c->prod_map_h, &c->prod_map_d, &c->prod_map_cap, plan.map_words));
-    products_fill(plan, off, qidx, compact_p, kMapRegionB, c->prod_off_h, c->prod_map_h);
-    if (qidx) products_wide_fill(plan, off, qidx, kMapRegionB, c->prod_map_h);
-    HIPCHK(c, hipMemcpyAsync(c->prod_off_d, c->prod_off_h, plan.off_words * 4, hipMemcpyHostToDevice, s));
-    if (plan.map_words)
-        HIPCHK(c, hipMemcpyAsync(c->prod_map_d, c->prod_map_h, plan.map_words * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipEventRecord(c->prod_off_event, s));
-    c->prod_off_pending = true;
-    return BN_OK;
+    RET_IF(c->prod_off.grow(c, c->prod_fence, plan.off_words));
+    RET_IF(c->prod_map.grow(c, c->prod_fence, plan.map_words));
+    products_fill(plan, off, qidx, compact_p, kMapRegionB, c->prod_off.h, c->prod_map.h);
+    if (qidx) products_wide_fill(plan, off, qidx, kMapRegionB, c->prod_map.h);
+    RET_IF(c->prod_off.copy(c, plan.off_words, s));
+    if (plan.map_words) RET_IF(c->prod_map.copy(c, plan.map_words, s));
+    return c->prod_fence.record(c, s);
 }
 // the tail of a launch set: the products' loop over the workspace's coefficients
 // (loop(grid, block) launches it, a lane pair per product), then the final exponentiation
@@ -87,7 +80,7 @@ static int prepared_set_dev(bn_ctx* c, const ProductsItem& st, const bn_g1* d_pf
                             const bn_g1* d_pp, const bn_g2_prepared* h, bn_gt* d_out, hipStream_t s) {
     const size_t nf = st.nf, np = st.np, mc = st.j1 - st.j0;
     if (nf + np > c->cap || mc > c->cap) return fail(c, BN_ERR_INTERNAL, "launch set exceeds the workspace");
-    const uint32_t* map = c->prod_map_d + st.map_at;
+    const uint32_t* map = c->prod_map.d + st.map_at;
     if (nf) RET_IF(prepare(c, d_pf, d_qf, nf, 0, s, 1, true));
     if (np) {
         launch_prepared_expand(d_pp, map + nf + np, map + nf + 2 * np, h->table, h->zero, (uint32_t)h->nq, np,
@@ -95,7 +88,7 @@ static int prepared_set_dev(bn_ctx* c, const ProductsItem& st, const bn_g1* d_pf
         HIPCHK(c, hipGetLastError());
     }
     return products_loop_fe(c, mc, d_out, s, [&](unsigned grid, unsigned block) {
-        k_miller_products_mapped<<<grid, block, 0, s>>>(c->coeffs, c->flags, nf, np, map, c->prod_off_d + st.off_at, mc,
+        k_miller_products_mapped<<<grid, block, 0, s>>>(c->coeffs, c->flags, nf, np, map, c->prod_off.d + st.off_at, mc,
                                                         c->slots);
     });
 }
@@ -117,19 +110,19 @@ static int wide_set_dev(bn_ctx* c, const bn_g1* d_p, const bn_g2* d_q, size_t nt
 static int wide_prepared_set_dev(bn_ctx* c, const ProductsItem& st, const bn_g1* d_p, const bn_g2* d_qf,
                                  const bn_g2_prepared* h, bn_gt* d_out, hipStream_t s) {
     const size_t nt = st.nf + st.np;
-    if (nt > c->prod_gq_cap) return fail(c, BN_ERR_INTERNAL, "launch set exceeds the gathered points");
+    if (nt > c->prod_gq.cap()) return fail(c, BN_ERR_INTERNAL, "launch set exceeds the gathered points");
     if (nt) {
-        launch_g2_gather(d_qf, st.nf, h->points, (uint32_t)h->nq, c->prod_map_d + st.map_at, nt, c->prod_gq, s);
+        launch_g2_gather(d_qf, st.nf, h->points, (uint32_t)h->nq, c->prod_map.d + st.map_at, nt, c->prod_gq, s);
         HIPCHK(c, hipGetLastError());
     }
-    return wide_set_dev(c, d_p, c->prod_gq, nt, c->prod_off_d + st.off_at, st.j1 - st.j0, d_out, s);
+    return wide_set_dev(c, d_p, c->prod_gq, nt, c->prod_off.d + st.off_at, st.j1 - st.j0, d_out, s);
 }
 // prod_gq for the largest wide set of a plan of the prepared form
 static int wide_gather_reserve(bn_ctx* c, const ProductsPlan& plan) {
     size_t ntmax = 0;
     for (const ProductsItem& st : plan.items)
         if (st.wide) ntmax = std::max(ntmax, st.nf + st.np);
-    return grow_dev(c, &c->prod_gq, &c->prod_gq_cap, ntmax, 4096, true);
+    return c->prod_gq.grow(c, ntmax, 4096, true);
 }
 // The host forms: every item in turn through the context's stage.  run_set stages a packed
 // (or wide) item's pairs and its products' Gt, copies the pairs in and runs the set, leaving the
@@ -186,9 +179,9 @@ int bn_pairing_batch_many_dev(bn_ctx* c, const bn_g1* d_p, const bn_g2* d_q, con
     for (const ProductsItem& it : plan.items) {
         const size_t lo = offsets[it.j0], nt = offsets[it.j1] - lo;
         if (it.wide)
-            RET_IF(wide_set_dev(c, d_p + lo, d_q + lo, nt, c->prod_off_d + it.off_at, it.j1 - it.j0, d_out + it.j0, s));
+            RET_IF(wide_set_dev(c, d_p + lo, d_q + lo, nt, c->prod_off.d + it.off_at, it.j1 - it.j0, d_out + it.j0, s));
         else if (it.packed)
-            RET_IF(products_set_dev(c, d_p + lo, d_q + lo, nt, c->prod_off_d + it.off_at, it.j1 - it.j0, d_out + it.j0, s));
+            RET_IF(products_set_dev(c, d_p + lo, d_q + lo, nt, c->prod_off.d + it.off_at, it.j1 - it.j0, d_out + it.j0, s));
         else if (nt == 0)  // mod.rs:922-924
             HIPCHK(c, hipMemcpyAsync(d_out + it.j0, &kGtOne, sizeof(bn_gt), hipMemcpyHostToDevice, s));
         else
@@ -214,7 +207,7 @@ int bn_pairing_batch_many(bn_ctx* c, const bn_g1* p, const bn_g2* q, const size_
         }
         *d = (bn_gt*)at[2];
         return (it.wide ? wide_set_dev : products_set_dev)(c, (bn_g1*)at[0], (bn_g2*)at[1], nt,
-                                                           c->prod_off_d + it.off_at, mc, *d, c->stream);
+                                                           c->prod_off.d + it.off_at, mc, *d, c->stream);
     });
 }
 int bn_set_products_min(bn_ctx* c, size_t m) {
@@ -265,9 +258,9 @@ int bn_set_products_chunk(bn_ctx* c, size_t terms) {
 // caller holds the lock and has ordered s after the workspace's previous user.
 static int g2_prepare_fill(bn_ctx* c, bn_g2_prepared* h, const bn_g2* q, bool q_dev, hipStream_t s) {
     const size_t nq = h->nq;
-    HIPCHK(c, hipMalloc(&h->table, nq * (size_t)kPreparedWords * 4));
-    HIPCHK(c, hipMalloc(&h->zero, nq));
-    HIPCHK(c, hipMalloc(&h->points, nq * sizeof(bn_g2)));
+    RET_IF(h->table.alloc(c, nq * (size_t)kPreparedWords));
+    RET_IF(h->zero.alloc(c, nq));
+    RET_IF(h->points.alloc(c, nq));
     const size_t mmax = nq < kChunk ? nq : kChunk;
     RET_IF(reserve(c, mmax));
     void* at[2];
@@ -290,21 +283,10 @@ static int g2_prepare_fill(bn_ctx* c, bn_g2_prepared* h, const bn_g2* q, bool q_
     return BN_OK;
 }
 static int g2_prepare(bn_ctx* c, const bn_g2* q, bool q_dev, size_t nq, bn_g2_prepared** out, hipStream_t s) {
-    bn_g2_prepared* h = new bn_g2_prepared();
+    auto h = std::make_unique<bn_g2_prepared>();
     h->nq = nq;
-    int rc = g2_prepare_fill(c, h, q, q_dev, s);
-    if (rc == BN_OK && !q_dev && hipStreamSynchronize(s) != hipSuccess) rc = fail(c, BN_ERR_HIP, "hipStreamSynchronize");
-    if (rc != BN_OK) {
-        (void)hipStreamSynchronize(s);  // nothing queued may still write the table
-        if (h->table) (void)hipFree(h->table);
-        if (h->zero) (void)hipFree(h->zero);
-        if (h->points) (void)hipFree(h->points);
-        delete h;
-        return rc;
-    }
-    c->prepared.push_back(h);
-    *out = h;
-    return BN_OK;
+    const int rc = g2_prepare_fill(c, h.get(), q, q_dev, s);
+    return c->prepared.settle(c, std::move(h), rc, !q_dev, s, out);
 }
 // refused before anything is read: a NULL q or out, nq outside 1 .. 2^16
 static int g2_prepare_args(bn_ctx* c, const void* q, size_t nq, bn_g2_prepared** out) {
@@ -335,22 +317,9 @@ int bn_g2_prepare_dev(bn_ctx* c, const bn_g2* d_q, size_t nq, bn_g2_prepared** o
 
 size_t bn_g2_prepared_count(const bn_g2_prepared* h) { return h ? h->nq : 0; }
 
-// a live handle of this context (looked up, not dereferenced: another context's handle,
-// or a destroyed one, is refused)
-static bool prepared_live(const bn_ctx* c, const bn_g2_prepared* h) {
-    return h && std::find(c->prepared.begin(), c->prepared.end(), h) != c->prepared.end();
-}
-
 int bn_g2_prepared_destroy(bn_ctx* c, bn_g2_prepared* h) {
     CTX_GUARD(c);
-    if (!prepared_live(c, h)) return fail(c, BN_ERR_INVALID_ARGUMENT, "not a live prepared handle of this context");
-    RET_IF(ws_drain(c));  // every call that reads the table has recorded ws_event behind its work
-    c->prepared.erase(std::find(c->prepared.begin(), c->prepared.end(), h));
-    (void)hipFree(h->table);
-    (void)hipFree(h->zero);
-    (void)hipFree(h->points);
-    delete h;
-    return BN_OK;
+    return c->prepared.destroy(c, h, "not a live prepared handle of this context");
 }
 
 // n pairings (fe) or Miller values of device arrays against the handle on stream s, every n
@@ -373,7 +342,7 @@ static int prepared_dev_impl(bn_ctx* c, const bn_g1* d_p, const bn_g2_prepared* 
 }
 static int prepared_args(bn_ctx* c, const void* p, const bn_g2_prepared* h, const void* out) {
     if (!p || !out || !h) return fail(c, BN_ERR_INVALID_ARGUMENT, "null buffer");
-    if (!prepared_live(c, h)) return fail(c, BN_ERR_INVALID_ARGUMENT, "not a live prepared handle of this context");
+    if (!c->prepared.live(h)) return fail(c, BN_ERR_INVALID_ARGUMENT, "not a live prepared handle of this context");
     return BN_OK;
 }
 // the host forms: indices checked first, then per chunk stage, copy, launch, read back,
@@ -431,7 +400,7 @@ static int prepared_products_check(bn_ctx* c, const void* p, const void* q, cons
                                    const uint32_t* qidx, const size_t* off, size_t m, const void* out) {
     RET_IF(offsets_check(c, off, m));
     if (!qidx || !out || !h) return fail(c, BN_ERR_INVALID_ARGUMENT, "null buffer");
-    if (!prepared_live(c, h)) return fail(c, BN_ERR_INVALID_ARGUMENT, "not a live prepared handle of this context");
+    if (!c->prepared.live(h)) return fail(c, BN_ERR_INVALID_ARGUMENT, "not a live prepared handle of this context");
     if (off[m] && !p) return fail(c, BN_ERR_INVALID_ARGUMENT, "null buffer");
     size_t nf = 0;
     if (const char* why = products_terms_refusal(qidx, off, m, kProductLaneMax, h->nq, &nf))
@@ -454,7 +423,7 @@ int bn_pairing_batch_prepared_many_dev(bn_ctx* c, const bn_g1* d_p, const bn_g2*
     size_t nfmax = 0;
     for (const ProductsItem& st : plan.items)
         if (st.packed) nfmax = std::max(nfmax, st.nf);
-    RET_IF(grow_dev(c, &c->prod_fresh, &c->prod_fresh_cap, nfmax, 4096, true));
+    RET_IF(c->prod_fresh.grow(c, nfmax, 4096, true));
     RET_IF(wide_gather_reserve(c, plan));
     RET_IF(ws_acquire(c, s));
     WsUse use{c, s};
@@ -466,7 +435,7 @@ int bn_pairing_batch_prepared_many_dev(bn_ctx* c, const bn_g1* d_p, const bn_g2*
             continue;
         }
         if (st.nf) {
-            launch_g1_gather(d_p + lo, c->prod_map_d + st.map_at + st.nf + 3 * st.np, st.nf, c->prod_fresh, s);
+            launch_g1_gather(d_p + lo, c->prod_map.d + st.map_at + st.nf + 3 * st.np, st.nf, c->prod_fresh, s);
             HIPCHK(c, hipGetLastError());
         }
         RET_IF(prepared_set_dev(c, st, c->prod_fresh, d_q + st.f0, d_p + lo, h, d_out + st.j0, s));
