@@ -4,8 +4,9 @@
 // normalized.  The host sequence is one template over the point type; MsmGroup<P>
 // names the group's kernels, settings and buffers.  Behind it, the bn_g1_prepared handles
 // and bn_g1_msm_prepared_many (kernels_msm_fixed.hip; §8c), bn_g1_msm_many
-// (kernels_msm_many.hip, msm_many_plan.h; §8d), and the bn_g1_basis handles and
-// bn_g1_msm_basis (kernels_msm_basis.hip; §8e).
+// (kernels_msm_many.hip, msm_many_plan.h; §8d), and the bn_g1_basis and bn_g2_basis handles
+// with bn_g1_msm_basis and bn_g2_msm_basis (kernels_msm_basis.hip, kernels_msm_basis_g2.hip;
+// §8e, §8f), one template over the point type.
 #include <type_traits>
 
 #include "capi_internal.h"
@@ -364,43 +365,104 @@ static int msm_prepared_dev_impl(bn_ctx* c, const bn_g1_prepared* h, const bn_fr
     return BN_OK;
 }
 
-// ---------------------------------------------------------------- one large MSM over a fixed basis (DESIGN.md §8e)
+// ---------------------------------------------------------------- one large MSM over a fixed basis (DESIGN.md §8e, §8f)
+// One host sequence over the point type; MsmBasis<P> names the group's handle type and list,
+// its table element, its kernels and its default width (the grids take MsmGroup<P>::kLanes
+// lanes per element; the workspace is MsmGroup<P>::ws).
+template <class P>
+struct MsmBasis;
+template <>
+struct MsmBasis<bn_g1> {
+    using Handle = bn_g1_basis;
+    using Elem = bn_fq;  // an entry is two of them: x, y
+    static constexpr auto k_build = k_g1_basis_build;
+    static constexpr auto k_accumulate = k_msm_basis_accumulate;
+    static constexpr auto k_chunk = k_msm_basis_chunk;
+    static constexpr auto k_reduce = k_msm_basis_reduce;
+    static HandleList<Handle>& list(bn_ctx* c) { return c->g1_basis; }
+    static int auto_window(size_t nbases) { return msm_basis_auto_window(nbases); }
+};
+template <>
+struct MsmBasis<bn_g2> {
+    using Handle = bn_g2_basis;
+    using Elem = bn_fq2;  // an entry is two of them: the lane halves (x.c0, y.c0), (x.c1, y.c1)
+    static constexpr auto k_build = k_g2_basis_build;
+    static constexpr auto k_accumulate = k_msm_basis_accumulate_g2;
+    static constexpr auto k_chunk = k_msm_basis_chunk_g2;
+    static constexpr auto k_reduce = k_msm_basis_reduce_g2;
+    static HandleList<Handle>& list(bn_ctx* c) { return c->g2_basis; }
+    static int auto_window(size_t nbases) { return msm_basis_auto_window_g2(nbases); }
+};
+// entries of the table of nbases bases at width cw (0: the group's default); 0 for arguments
+// that the prepare call refuses
+template <class P>
+static uint64_t basis_entries(size_t nbases, int cw) {
+    return msm_basis_entries_at(nbases, cw ? cw : MsmBasis<P>::auto_window(nbases));
+}
+template <class P>
+static size_t basis_table_bytes(size_t nbases, int cw) {
+    const uint64_t nent = basis_entries<P>(nbases, cw);
+    return nent ? (size_t)(nent * 2 * sizeof(typename MsmBasis<P>::Elem) + nbases) : 0;
+}
 // refused before anything is read: a NULL bases or out, a width outside 2 .. 16 (0: the
 // default), an nbases that is 0, above 2^26 or whose nbases * W(c) exceeds the 32-bit positions
-static int g1_basis_args(bn_ctx* c, const void* bases, size_t nbases, int cw, bn_g1_basis** out) {
+template <class P>
+static int basis_args(bn_ctx* c, const void* bases, size_t nbases, int cw, typename MsmBasis<P>::Handle** out) {
     if (!bases || !out) return fail(c, BN_ERR_INVALID_ARGUMENT, "null buffer");
     if (cw != 0 && !msm_window_ok(cw)) return fail(c, BN_ERR_INVALID_ARGUMENT, "window width outside 2 .. 16 (0: default)");
-    if (!msm_basis_entries(nbases, cw))
+    if (!basis_entries<P>(nbases, cw))
         return fail(c, BN_ERR_INVALID_ARGUMENT, "nbases is 0, above 2^26, or nbases * windows exceeds 2^31 - 1");
     return BN_OK;
 }
 // Fills a new handle on stream s from the bases (host memory, or device memory when dev).
 // The caller holds the lock and has ordered s after the workspace's previous user (the host
 // form stages the bases).
-static int g1_basis_fill(bn_ctx* c, bn_g1_basis* h, const bn_g1* bases, bool dev, hipStream_t s) {
+template <class P>
+static int basis_fill(bn_ctx* c, typename MsmBasis<P>::Handle* h, const P* bases, bool dev, hipStream_t s) {
+    using B = MsmBasis<P>;
     const size_t nbases = h->nbases;
-    RET_IF(h->table.alloc(c, (size_t)msm_basis_entries(nbases, h->c) * 2));
+    RET_IF(h->table.alloc(c, (size_t)msm_basis_entries_at(nbases, h->c) * 2));
     RET_IF(h->zero.alloc(c, nbases));
-    const bn_g1* d = bases;
+    const P* d = bases;
     if (!dev) {
         void* at[1];
-        RET_IF(stage_regions(c, {nbases * sizeof(bn_g1)}, at));
-        HIPCHK(c, hipMemcpyAsync(at[0], bases, nbases * sizeof(bn_g1), hipMemcpyHostToDevice, s));
-        d = (const bn_g1*)at[0];
+        RET_IF(stage_regions(c, {nbases * sizeof(P)}, at));
+        HIPCHK(c, hipMemcpyAsync(at[0], bases, nbases * sizeof(P), hipMemcpyHostToDevice, s));
+        d = (const P*)at[0];
     }
-    k_g1_basis_build<<<grid_for(nbases), kBlock, 0, s>>>(d, (uint32_t)nbases, h->c, h->table, h->zero);
+    B::k_build<<<grid_for(MsmGroup<P>::kLanes * nbases), kBlock, 0, s>>>(d, (uint32_t)nbases, h->c, h->table, h->zero);
     HIPCHK(c, hipGetLastError());
     return BN_OK;
 }
-static int g1_basis_make(bn_ctx* c, const bn_g1* bases, bool dev, size_t nbases, int cw, bn_g1_basis** out, hipStream_t s) {
-    auto h = std::make_unique<bn_g1_basis>();
+template <class P>
+static int basis_make(bn_ctx* c, const P* bases, bool dev, size_t nbases, int cw, typename MsmBasis<P>::Handle** out,
+                      hipStream_t s) {
+    using B = MsmBasis<P>;
+    auto h = std::make_unique<typename B::Handle>();
     h->nbases = nbases;
-    h->c = cw ? cw : msm_basis_auto_window(nbases);
-    const int rc = g1_basis_fill(c, h.get(), bases, dev, s);
-    return c->g1_basis.settle(c, std::move(h), rc, !dev, s, out);
+    h->c = cw ? cw : B::auto_window(nbases);
+    const int rc = basis_fill<P>(c, h.get(), bases, dev, s);
+    return B::list(c).settle(c, std::move(h), rc, !dev, s, out);
 }
-static int msm_basis_args(bn_ctx* c, const bn_g1_basis* h, const void* k, size_t n, const void* out) {
-    if (!c->g1_basis.live(h)) return fail(c, BN_ERR_INVALID_ARGUMENT, "not a live basis handle of this context");
+// bn_g1_basis_prepare / bn_g2_basis_prepare (stream: the context's) and their _dev forms
+template <class P>
+static int basis_prepare(bn_ctx* c, const P* bases, bool dev, size_t nbases, int cw, typename MsmBasis<P>::Handle** out,
+                         void* stream) {
+    CTX_GUARD(c);
+    RET_IF(basis_args<P>(c, bases, nbases, cw, out));
+    const hipStream_t s = dev ? pick(c, stream) : c->stream;
+    RET_IF(ws_acquire(c, s));
+    WsUse use{c, s};
+    return basis_make<P>(c, bases, dev, nbases, cw, out, s);
+}
+template <class P>
+static int basis_destroy(bn_ctx* c, typename MsmBasis<P>::Handle* h) {
+    CTX_GUARD(c);
+    return MsmBasis<P>::list(c).destroy(c, h, "not a live basis handle of this context");
+}
+template <class P>
+static int msm_basis_args(bn_ctx* c, const typename MsmBasis<P>::Handle* h, const void* k, size_t n, const void* out) {
+    if (!MsmBasis<P>::list(c).live(h)) return fail(c, BN_ERR_INVALID_ARGUMENT, "not a live basis handle of this context");
     if (!out) return fail(c, BN_ERR_INVALID_ARGUMENT, "null buffer");
     if (n > h->nbases) return fail(c, BN_ERR_INVALID_ARGUMENT, "more terms than the handle has bases");
     if (n && !k) return fail(c, BN_ERR_INVALID_ARGUMENT, "null buffer");
@@ -408,35 +470,72 @@ static int msm_basis_args(bn_ctx* c, const bn_g1_basis* h, const void* k, size_t
 }
 // the plan of n terms over the handle: the bucket path's at the handle's width and the run
 // cap in force (bn_set_msm_window and bn_set_msm_min do not apply)
-static MsmPlan msm_basis_plan(bn_ctx* c, const bn_g1_basis* h, size_t n) { return msm_plan_at(c->msm_g1.run_max, n, h->c); }
+template <class P>
+static MsmPlan msm_basis_plan(bn_ctx* c, const typename MsmBasis<P>::Handle* h, size_t n) {
+    return msm_plan_at(MsmGroup<P>::ws(c).run_max, n, h->c);
+}
 // The device sequence on stream s over the first n bases; the caller holds the lock and the
 // workspace order.  n * W(c) <= nbases * W(c) <= 2^31 - 1 (the prepare call's check).
-static int msm_basis_dev_impl(bn_ctx* c, const bn_g1_basis* h, const bn_fr* d_k, size_t n, bn_g1* d_out, hipStream_t s) {
+template <class P>
+static int msm_basis_dev_impl(bn_ctx* c, const typename MsmBasis<P>::Handle* h, const bn_fr* d_k, size_t n, P* d_out,
+                              hipStream_t s) {
+    using G = MsmGroup<P>;
+    using B = MsmBasis<P>;
     if (n == 0) {
-        k_msm_finish<<<1, 64, 0, s>>>(nullptr, d_out);
+        G::k_finish<<<1, 64, 0, s>>>(nullptr, d_out);
         HIPCHK(c, hipGetLastError());
         return BN_OK;
     }
-    const MsmPlan m = msm_basis_plan(c, h, n);
-    RET_IF(msm_reserve<bn_g1>(c, n, m));
-    MsmGroupWs<bn_g1>& g = c->msm_g1;
+    const MsmPlan m = msm_basis_plan<P>(c, h, n);
+    RET_IF(msm_reserve<P>(c, n, m));
+    MsmGroupWs<P>& g = G::ws(c);
     const uint32_t nb = msm_buckets(m.c), nbases = (uint32_t)h->nbases;
     MsmKeys k;
     RET_IF(msm_sort(c, m, k_msm_count_basis, k_msm_scatter_basis, h->zero.get(), d_k, n, s, &k));
-    k_msm_basis_accumulate<<<grid_for(m.nkeys), kBlock, 0, s>>>(h->table, nbases, (uint32_t)n, m.c, c->msm_sorted, k.offsets,
-                                                                m.nkeys, k.nent, m.L, g.buckets);
-    msm_long_runs<bn_g1>(c, m, k, s, [&](auto grid, auto... a) {
-        k_msm_basis_chunk<<<grid, kBlock, 0, s>>>(h->table.get(), nbases, (uint32_t)n, m.c, a...);
+    B::k_accumulate<<<grid_for(G::kLanes * m.nkeys), kBlock, 0, s>>>(h->table, nbases, (uint32_t)n, m.c, c->msm_sorted,
+                                                                     k.offsets, m.nkeys, k.nent, m.L, g.buckets);
+    msm_long_runs<P>(c, m, k, s, [&](auto grid, auto... a) {
+        B::k_chunk<<<grid, kBlock, 0, s>>>(h->table.get(), nbases, (uint32_t)n, m.c, a...);
     });
     // Every window's bucket j weighs j + 1 but the top one's, whose slots are replicas: the rows
     // of the windows below it are added into window 0's row, and two windows are reduced.
     msm_tree(g.buckets.get(), m.nwin - 1, nb, s);
-    k_msm_basis_reduce<<<grid_for(2 * (size_t)m.nseg), kBlock, 0, s>>>(g.buckets, m.c, m.nkeys, m.nseg, g.parts);
+    B::k_reduce<<<grid_for(G::kLanes * 2 * (size_t)m.nseg), kBlock, 0, s>>>(g.buckets, m.c, m.nkeys, m.nseg, g.parts);
     msm_tree(g.parts.get(), m.nseg, 2, s);
     msm_tree(g.parts.get(), 2, 1, s);  // the two window sums: no weight between them, nothing is doubled
-    k_msm_finish<<<1, 64, 0, s>>>(g.parts, d_out);
+    G::k_finish<<<1, 64, 0, s>>>(g.parts, d_out);
     HIPCHK(c, hipGetLastError());
     return BN_OK;
+}
+template <class P>
+static int msm_basis_host(bn_ctx* c, const typename MsmBasis<P>::Handle* h, const bn_fr* k, size_t n, P* out) {
+    CTX_GUARD_HOST(c);
+    RET_IF(msm_basis_args<P>(c, h, k, n, out));
+    void* at[2];  // the sum, the scalars
+    RET_IF(stage_regions(c, {sizeof(P), n * sizeof(bn_fr)}, at));
+    if (n) HIPCHK(c, hipMemcpyAsync(at[1], k, n * sizeof(bn_fr), hipMemcpyHostToDevice, c->stream));
+    RET_IF(msm_basis_dev_impl<P>(c, h, (const bn_fr*)at[1], n, (P*)at[0], c->stream));
+    HIPCHK(c, hipMemcpyAsync(out, at[0], sizeof(P), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return BN_OK;
+}
+template <class P>
+static int msm_basis_dev(bn_ctx* c, const typename MsmBasis<P>::Handle* h, const bn_fr* d_k, size_t n, P* d_out,
+                         void* stream) {
+    CTX_GUARD(c);
+    RET_IF(msm_basis_args<P>(c, h, d_k, n, d_out));
+    hipStream_t s = pick(c, stream);
+    RET_IF(ws_acquire(c, s));
+    WsUse use{c, s};
+    return msm_basis_dev_impl<P>(c, h, d_k, n, d_out, s);
+}
+template <class P>
+static int msm_basis_reserve(bn_ctx* c, const typename MsmBasis<P>::Handle* h, size_t n) {
+    CTX_GUARD(c);
+    if (!MsmBasis<P>::list(c).live(h)) return fail(c, BN_ERR_INVALID_ARGUMENT, "not a live basis handle of this context");
+    if (n > h->nbases) return fail(c, BN_ERR_INVALID_ARGUMENT, "more terms than the handle has bases");
+    if (n == 0) return BN_OK;
+    return msm_reserve<P>(c, n, msm_basis_plan<P>(c, h, n));
 }
 
 // ---------------------------------------------------------------- many MSMs over fresh bases
@@ -571,57 +670,40 @@ int bn_g1_msm_prepared_many_dev(bn_ctx* c, const bn_g1_prepared* h, const bn_fr*
     WsUse use{c, s};
     return msm_prepared_dev_impl(c, h, d_k, m, d_out, out_stride, s);
 }
-size_t bn_g1_basis_table_bytes(size_t nbases, int cw) {
-    const uint64_t nent = msm_basis_entries(nbases, cw);
-    return nent ? (size_t)(nent * 2 * sizeof(bn_fq) + nbases) : 0;
-}
+size_t bn_g1_basis_table_bytes(size_t nbases, int cw) { return basis_table_bytes<bn_g1>(nbases, cw); }
 int bn_g1_basis_prepare(bn_ctx* c, const bn_g1* bases, size_t nbases, int cw, bn_g1_basis** out) {
-    CTX_GUARD(c);
-    RET_IF(g1_basis_args(c, bases, nbases, cw, out));
-    RET_IF(ws_acquire(c, c->stream));
-    WsUse use{c, c->stream};
-    return g1_basis_make(c, bases, false, nbases, cw, out, c->stream);
+    return basis_prepare(c, bases, false, nbases, cw, out, nullptr);
 }
 int bn_g1_basis_prepare_dev(bn_ctx* c, const bn_g1* d_bases, size_t nbases, int cw, bn_g1_basis** out, void* stream) {
-    CTX_GUARD(c);
-    RET_IF(g1_basis_args(c, d_bases, nbases, cw, out));
-    const hipStream_t s = pick(c, stream);
-    RET_IF(ws_acquire(c, s));
-    WsUse use{c, s};
-    return g1_basis_make(c, d_bases, true, nbases, cw, out, s);
+    return basis_prepare(c, d_bases, true, nbases, cw, out, stream);
 }
 size_t bn_g1_basis_count(const bn_g1_basis* h) { return h ? h->nbases : 0; }
 int bn_g1_basis_window(const bn_g1_basis* h) { return h ? h->c : 0; }
-int bn_g1_basis_destroy(bn_ctx* c, bn_g1_basis* h) {
-    CTX_GUARD(c);
-    return c->g1_basis.destroy(c, h, "not a live basis handle of this context");
-}
+int bn_g1_basis_destroy(bn_ctx* c, bn_g1_basis* h) { return basis_destroy<bn_g1>(c, h); }
 int bn_g1_msm_basis(bn_ctx* c, const bn_g1_basis* h, const bn_fr* k, size_t n, bn_g1* out) {
-    CTX_GUARD_HOST(c);
-    RET_IF(msm_basis_args(c, h, k, n, out));
-    void* at[2];  // the sum, the scalars
-    RET_IF(stage_regions(c, {sizeof(bn_g1), n * sizeof(bn_fr)}, at));
-    if (n) HIPCHK(c, hipMemcpyAsync(at[1], k, n * sizeof(bn_fr), hipMemcpyHostToDevice, c->stream));
-    RET_IF(msm_basis_dev_impl(c, h, (const bn_fr*)at[1], n, (bn_g1*)at[0], c->stream));
-    HIPCHK(c, hipMemcpyAsync(out, at[0], sizeof(bn_g1), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return BN_OK;
+    return msm_basis_host(c, h, k, n, out);
 }
 int bn_g1_msm_basis_dev(bn_ctx* c, const bn_g1_basis* h, const bn_fr* d_k, size_t n, bn_g1* d_out, void* stream) {
-    CTX_GUARD(c);
-    RET_IF(msm_basis_args(c, h, d_k, n, d_out));
-    hipStream_t s = pick(c, stream);
-    RET_IF(ws_acquire(c, s));
-    WsUse use{c, s};
-    return msm_basis_dev_impl(c, h, d_k, n, d_out, s);
+    return msm_basis_dev(c, h, d_k, n, d_out, stream);
 }
-int bn_g1_msm_basis_reserve(bn_ctx* c, const bn_g1_basis* h, size_t n) {
-    CTX_GUARD(c);
-    if (!c->g1_basis.live(h)) return fail(c, BN_ERR_INVALID_ARGUMENT, "not a live basis handle of this context");
-    if (n > h->nbases) return fail(c, BN_ERR_INVALID_ARGUMENT, "more terms than the handle has bases");
-    if (n == 0) return BN_OK;
-    return msm_reserve<bn_g1>(c, n, msm_basis_plan(c, h, n));
+int bn_g1_msm_basis_reserve(bn_ctx* c, const bn_g1_basis* h, size_t n) { return msm_basis_reserve<bn_g1>(c, h, n); }
+size_t bn_g2_basis_table_bytes(size_t nbases, int cw) { return basis_table_bytes<bn_g2>(nbases, cw); }
+int bn_g2_basis_prepare(bn_ctx* c, const bn_g2* bases, size_t nbases, int cw, bn_g2_basis** out) {
+    return basis_prepare(c, bases, false, nbases, cw, out, nullptr);
 }
+int bn_g2_basis_prepare_dev(bn_ctx* c, const bn_g2* d_bases, size_t nbases, int cw, bn_g2_basis** out, void* stream) {
+    return basis_prepare(c, d_bases, true, nbases, cw, out, stream);
+}
+size_t bn_g2_basis_count(const bn_g2_basis* h) { return h ? h->nbases : 0; }
+int bn_g2_basis_window(const bn_g2_basis* h) { return h ? h->c : 0; }
+int bn_g2_basis_destroy(bn_ctx* c, bn_g2_basis* h) { return basis_destroy<bn_g2>(c, h); }
+int bn_g2_msm_basis(bn_ctx* c, const bn_g2_basis* h, const bn_fr* k, size_t n, bn_g2* out) {
+    return msm_basis_host(c, h, k, n, out);
+}
+int bn_g2_msm_basis_dev(bn_ctx* c, const bn_g2_basis* h, const bn_fr* d_k, size_t n, bn_g2* d_out, void* stream) {
+    return msm_basis_dev(c, h, d_k, n, d_out, stream);
+}
+int bn_g2_msm_basis_reserve(bn_ctx* c, const bn_g2_basis* h, size_t n) { return msm_basis_reserve<bn_g2>(c, h, n); }
 int bn_g1_msm_many(bn_ctx* c, const bn_g1* p, const bn_fr* k, const size_t* offsets, size_t m, bn_g1* out,
                    size_t out_stride) {
     CTX_GUARD_HOST(c);

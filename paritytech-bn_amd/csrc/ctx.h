@@ -68,6 +68,16 @@ struct bn_g1_basis {
     bn::DevBuf<uint8_t> zero;  // zero[b] != 0: bases[b] had z == 0, its entries are never added
 };
 
+// bn_g2_basis_prepare's handle: the same for nbases G2 bases (two bn_fq2 per entry, stored as
+// the two lane halves [x.c0, y.c0 | x.c1, y.c1]: kernels_msm_basis_g2.hip), owned by the
+// single-device context whose `g2_basis` list holds it.
+struct bn_g2_basis {
+    size_t nbases = 0;
+    int c = 0;
+    bn::DevBuf<bn_fq2> table;
+    bn::DevBuf<uint8_t> zero;  // zero[b] != 0: bases[b] had z == 0, its entries are never added
+};
+
 #pragma GCC visibility pop
 
 struct bn_ctx {
@@ -187,6 +197,8 @@ struct bn_ctx {
     bn::HandleList<bn_g1_prepared> g1_prepared;
     // and for the bn_g1_basis handles (capi_msm.hip)
     bn::HandleList<bn_g1_basis> g1_basis;
+    // and for the bn_g2_basis handles (capi_msm.hip)
+    bn::HandleList<bn_g2_basis> g2_basis;
     // bn_g1_msm_many (capi_msm.hip, kernels_msm_many.hip).  Settings: 0 takes
     // the default (capi_msm.hip).  Its workspace is its own, like the MSM's: the digit bytes,
     // the multiples and the units' partial sums of one launch set, grown on first use or by

@@ -667,6 +667,15 @@ __global__ void __launch_bounds__(kBlock) k_msm_basis_chunk(const bn_fq* __restr
                                                             const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ longinfo, uint32_t nkeys, uint32_t nent, uint32_t L,
                                                             bn_g1* __restrict__ sums, uint32_t nslots);
 __global__ void __launch_bounds__(kBlock) k_msm_basis_reduce(const bn_g1* __restrict__ buckets, int c, uint32_t nkeys, uint32_t nseg, bn_g1* __restrict__ parts);
+// kernels_msm_basis_g2.hip: the same over G2, kPathLanes lanes per base, key, slot or part.  table: nbases * W(c)
+// entries of two bn_fq2, window major, each entry as two lane halves [x.c0, y.c0 | x.c1, y.c1]
+__global__ void __launch_bounds__(kBlock) k_g2_basis_build(const bn_g2* __restrict__ bases, uint32_t nbases, int c, bn_fq2* __restrict__ table, uint8_t* __restrict__ zero);
+__global__ void __launch_bounds__(kBlock) k_msm_basis_accumulate_g2(const bn_fq2* __restrict__ table, uint32_t nbases, uint32_t n, int c, const uint32_t* __restrict__ sorted,
+                                                                    const uint32_t* __restrict__ offsets, uint32_t nkeys, uint32_t nent, uint32_t L, bn_g2* __restrict__ buckets);
+__global__ void __launch_bounds__(kBlock) k_msm_basis_chunk_g2(const bn_fq2* __restrict__ table, uint32_t nbases, uint32_t n, int c, const uint32_t* __restrict__ sorted,
+                                                               const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ longinfo, uint32_t nkeys, uint32_t nent, uint32_t L,
+                                                               bn_g2* __restrict__ sums, uint32_t nslots);
+__global__ void __launch_bounds__(kBlock) k_msm_basis_reduce_g2(const bn_g2* __restrict__ buckets, int c, uint32_t nkeys, uint32_t nseg, bn_g2* __restrict__ parts);
 __global__ void __launch_bounds__(kPairBlock) k_gt_pow(const bn_gt* __restrict__ a, const bn_fr* __restrict__ k, size_t n,
                                                    bn_gt* __restrict__ out, uint32_t* __restrict__ ws);
 // kernels_codec.hip (codec.h): encodings, square roots, validation, decompression

@@ -1,7 +1,8 @@
 // msm_basis.h -- one large multi-scalar multiplication over a FIXED BASIS (bn_g1_basis,
-// bn_g1_msm_basis): the bodies shared by kernels_msm_basis.hip and the host
-// build of tests/native/msm_basis_emul.cpp, templates over the field F through curve.h's
-// F_* (Fq: G1) that take functors for every load and store.
+// bn_g1_msm_basis, bn_g2_basis, bn_g2_msm_basis): the bodies shared by
+// kernels_msm_basis.hip, kernels_msm_basis_g2.hip and the host builds of
+// tests/native/msm_basis_emul.cpp and msm_basis_g2_emul.cpp, templates over the field F
+// through curve.h's F_* (Fq: G1; Fq2: G2) that take functors for every load and store.
 //
 // The scalars are recoded exactly as for the bucket method (msm.h: W(c) signed digits of c
 // bits, the keys msm_key(c, w, d, index), the top window's replicas, the run split).  The
@@ -19,6 +20,13 @@
 // stores of neighbouring lanes contiguous, and keeps the entries a prefix call of n < nbases
 // terms can touch in W(c) dense ranges of n entries.  A base with z == 0 has a zero flag and
 // all-zero entries, which are never added.
+//
+// G2 (F = Fq2): the same index, 128 bytes per entry, stored as the two halves a lane pair
+// reads, [x.c0, y.c0 | x.c1, y.c1], so each lane's gather is again one aligned 64-byte read
+// (kernels_msm_basis_g2.hip).  A base may be any point of the twist, also one outside the
+// order-r subgroup, as everywhere in the G2 group API: the order of E'(Fq2) is r * (2p - r),
+// which is odd, so no point has even order, no doubling of the build turns a nonzero base
+// into zero, and every entry of an unflagged base is a real affine point.
 #pragma once
 #include "msm_fixed.h"
 
@@ -41,15 +49,34 @@ BN_INLINE int msm_basis_auto_window(uint64_t nbases) {
     if (nbases < 741455) return 14;  // 2^19.5
     return 16;
 }
-// entries of the table of nbases bases at width c (0: the default); 0 for arguments that the
-// prepare call refuses
-BN_INLINE uint64_t msm_basis_entries(uint64_t nbases, int c) {
+// The width bn_g2_basis_prepare takes for c = 0: the table of the G2 basis form's own width
+// sweep over 9 .. 16 (profiles/msm_basis_g2_widths.jsonl, tools/msm_bench.py --basis --group g2
+// --basis-windows), the steps at the geometric means between measured sizes
+// whose best width differs (measured at 1, 2^10, 2^12, 2^14 and 2^16 .. 2^20 bases).  It is
+// narrower than bn_g2_msm's table at both ends: 9 up to 2^10 (the buckets written, collapsed
+// and reduced whatever n is are the floor), 14 still at 2^19 and 15 at 2^20, where 16 is 0.19 ms
+// behind.
+BN_INLINE int msm_basis_auto_window_g2(uint64_t nbases) {
+    if (nbases < 2048) return 9;     // 2^11
+    if (nbases < 32768) return 11;   // 2^15
+    if (nbases < 92682) return 12;   // 2^16.5
+    if (nbases < 741455) return 14;  // 2^19.5
+    return 15;
+}
+// entries of the table of nbases bases at the width c itself, which no default stands in for
+// (the library resolves a group's default before it asks: capi_msm.hip MsmBasis<P>); 0 for an
+// nbases or c that the prepare call refuses, c == 0 among them
+BN_INLINE uint64_t msm_basis_entries_at(uint64_t nbases, int c) {
     if (nbases < 1 || nbases > kMsmBasisMaxBases) return 0;
-    if (c == 0) c = msm_basis_auto_window(nbases);
     if (!msm_window_ok(c)) return 0;
     const uint64_t nwin = (uint64_t)msm_windows(c);
     if (nbases > kMsmBasisMaxEntries / nwin) return 0;
     return nbases * nwin;
+}
+// the same with c == 0 taken as the G1 default: the G1 emulator's form (tests/native); the
+// library calls msm_basis_entries_at
+BN_INLINE uint64_t msm_basis_entries(uint64_t nbases, int c) {
+    return msm_basis_entries_at(nbases, c ? c : msm_basis_auto_window(nbases));
 }
 // index of entry (b, w)
 BN_INLINE uint32_t msm_basis_index(uint32_t nbases, uint32_t b, uint32_t w) { return w * nbases + b; }

@@ -26,7 +26,7 @@ pairing_prepared_many, miller_loop_prepared_many: the reference's G2Precomp held
 device; pairing_batch_prepared_many: many products whose terms mix fresh and prepared
 points), and many small MSMs over fixed G1 bases prepared once (G1Prepared,
 g1_msm_prepared_many), and one large MSM per call over a fixed basis prepared once
-(G1Basis, g1_msm_basis).  Values keep the reference's memory images (canonical
+(G1Basis, g1_msm_basis; G2Basis, g2_msm_basis).  Values keep the reference's memory images (canonical
 Montgomery, little-endian u64 limbs), so a Gt compares equal exactly when the
 reference's derived PartialEq would.  Every computation runs on the GPU; there
 is no CPU fallback.
@@ -655,37 +655,47 @@ def g1_msm_prepared_many(prepared, rows):
     return [G1(row) for row in prepared._ctx.g1_msm_prepared_many(h, s)]
 
 
-class G1Basis:
-    """A fixed G1 basis held on the device for large MSMs (bn_g1_basis_prepare): what a
-    committer builds once from its SRS, or a prover from its proving key's queries, and then
-    runs one MSM per call over (g1_msm_basis).  For every base and every window of the
-    recoding it holds the one point 2^(window * w) * base, so a call adds table points into
-    buckets and doubles nothing.  Built from a sequence of G1 or a (n, 12) image array of at
-    least one base, or from a device address (`bases` an int, `count` the number of bases, on
-    `stream`); zero bases are allowed.  `window` is the width in bits, 2 .. 16 (0: the engine's
-    default for that many bases); len() and `count` are the number of bases.  Release it with
-    close(), a `with` block, or by dropping it; it belongs to the engine context it was built
-    on (the process-wide one unless `ctx` is given)."""
+class _Basis:
+    """What G1Basis and G2Basis share: the argument checks, the handle's lifetime and the
+    `with` protocol.  A subclass names the words of a base's image and its five engine calls."""
+
+    _WORDS = 0
+
+    def _prepare(self, b, window):
+        raise NotImplementedError
+
+    def _prepare_dev(self, address, count, window, stream):
+        raise NotImplementedError
+
+    def _count(self, h):
+        raise NotImplementedError
+
+    def _window(self, h):
+        raise NotImplementedError
+
+    def _destroy(self, h):
+        raise NotImplementedError
 
     def __init__(self, bases, window=0, ctx=None, count=None, stream=None):
         self._h = None
+        name = type(self).__name__
         if window != 0 and not 2 <= window <= 16:
-            raise ValueError("G1Basis window must be 0 or 2 .. 16, not %r" % (window,))
+            raise ValueError("%s window must be 0 or 2 .. 16, not %r" % (name, window))
         if isinstance(bases, int):
             if count is None or count < 1:
-                raise ValueError("G1Basis from a device address takes count >= 1")
+                raise ValueError("%s from a device address takes count >= 1" % name)
             self._ctx = ctx if ctx is not None else context()
-            self._h = self._ctx.g1_basis_prepare_dev(bases, count, window, stream)
+            self._h = self._prepare_dev(bases, count, window, stream)
         else:
-            b = _images(bases, 12)
+            b = _images(bases, self._WORDS)
             if b.shape[0] < 1:
-                raise ValueError("G1Basis takes at least one base")
+                raise ValueError("%s takes at least one base" % name)
             if count is not None and count != b.shape[0]:
-                raise ValueError("G1Basis: count %d for %d bases" % (count, b.shape[0]))
+                raise ValueError("%s: count %d for %d bases" % (name, count, b.shape[0]))
             self._ctx = ctx if ctx is not None else context()
-            self._h = self._ctx.g1_basis_prepare(b, window)
-        self.count = self._ctx.g1_basis_count(self._h)
-        self.window = self._ctx.g1_basis_window(self._h)
+            self._h = self._prepare(b, window)
+        self.count = self._count(self._h)
+        self.window = self._window(self._h)
 
     def __len__(self):
         return self.count
@@ -696,14 +706,14 @@ class G1Basis:
 
     def _handle(self):
         if self._h is None:
-            raise ValueError("this G1Basis is closed")
+            raise ValueError("this %s is closed" % type(self).__name__)
         return self._h
 
     def close(self):
         h, self._h = getattr(self, "_h", None), None
         # (a context closed first has freed its handles itself)
         if h is not None and getattr(self._ctx, "handle", None):
-            self._ctx.g1_basis_destroy(h)
+            self._destroy(h)
 
     def __enter__(self):
         return self
@@ -718,6 +728,36 @@ class G1Basis:
             pass
 
 
+class G1Basis(_Basis):
+    """A fixed G1 basis held on the device for large MSMs (bn_g1_basis_prepare): what a
+    committer builds once from its SRS, or a prover from its proving key's queries, and then
+    runs one MSM per call over (g1_msm_basis).  For every base and every window of the
+    recoding it holds the one point 2^(window * w) * base, so a call adds table points into
+    buckets and doubles nothing.  Built from a sequence of G1 or a (n, 12) image array of at
+    least one base, or from a device address (`bases` an int, `count` the number of bases, on
+    `stream`); zero bases are allowed.  `window` is the width in bits, 2 .. 16 (0: the engine's
+    default for that many bases); len() and `count` are the number of bases.  Release it with
+    close(), a `with` block, or by dropping it; it belongs to the engine context it was built
+    on (the process-wide one unless `ctx` is given)."""
+
+    _WORDS = 12
+
+    def _prepare(self, b, window):
+        return self._ctx.g1_basis_prepare(b, window)
+
+    def _prepare_dev(self, address, count, window, stream):
+        return self._ctx.g1_basis_prepare_dev(address, count, window, stream)
+
+    def _count(self, h):
+        return self._ctx.g1_basis_count(h)
+
+    def _window(self, h):
+        return self._ctx.g1_basis_window(h)
+
+    def _destroy(self, h):
+        self._ctx.g1_basis_destroy(h)
+
+
 def g1_msm_basis(basis, scalars):
     """sum of basis[i] * scalars[i] over the first len(scalars) bases as a normalized G1
     (bn_g1_msm_basis), the same G1 as g1_msm over those bases.  scalars: a sequence of Fr or an
@@ -730,6 +770,43 @@ def g1_msm_basis(basis, scalars):
     if k.shape[0] == 0:
         return G1.zero()
     return G1(basis._ctx.g1_msm_basis(h, k))
+
+
+class G2Basis(_Basis):
+    """A fixed G2 basis held on the device for large MSMs (bn_g2_basis_prepare): a Groth16
+    prover's B query, the G2 powers of tau of an SRS.  As G1Basis in every respect, over G2
+    or (n, 24) image arrays; run MSMs over it with g2_msm_basis."""
+
+    _WORDS = 24
+
+    def _prepare(self, b, window):
+        return self._ctx.g2_basis_prepare(b, window)
+
+    def _prepare_dev(self, address, count, window, stream):
+        return self._ctx.g2_basis_prepare_dev(address, count, window, stream)
+
+    def _count(self, h):
+        return self._ctx.g2_basis_count(h)
+
+    def _window(self, h):
+        return self._ctx.g2_basis_window(h)
+
+    def _destroy(self, h):
+        self._ctx.g2_basis_destroy(h)
+
+
+def g2_msm_basis(basis, scalars):
+    """sum of basis[i] * scalars[i] over the first len(scalars) bases as a normalized G2
+    (bn_g2_msm_basis), the same G2 as g2_msm over those bases.  scalars: a sequence of Fr or an
+    (n, 4) image array.  More scalars than bases and a closed G2Basis raise ValueError before
+    any device call; no scalars give G2.zero() without one."""
+    h = basis._handle()
+    k = _images(scalars, 4)
+    if k.shape[0] > len(basis):
+        raise ValueError("g2_msm_basis: %d scalars for a basis of %d" % (k.shape[0], len(basis)))
+    if k.shape[0] == 0:
+        return G2.zero()
+    return G2(basis._ctx.g2_msm_basis(h, k))
 
 
 def g2_affine_new_many(x, y):

@@ -47,6 +47,8 @@ EXPORTS = [
     "bn_set_msm_many_chunk", "bn_g1_msm_many_reserve",
     "bn_g1_basis_table_bytes", "bn_g1_basis_prepare", "bn_g1_basis_prepare_dev", "bn_g1_basis_count",
     "bn_g1_basis_window", "bn_g1_basis_destroy", "bn_g1_msm_basis", "bn_g1_msm_basis_dev", "bn_g1_msm_basis_reserve",
+    "bn_g2_basis_table_bytes", "bn_g2_basis_prepare", "bn_g2_basis_prepare_dev", "bn_g2_basis_count",
+    "bn_g2_basis_window", "bn_g2_basis_destroy", "bn_g2_msm_basis", "bn_g2_msm_basis_dev", "bn_g2_msm_basis_reserve",
     "bn_pairing_batch_many", "bn_pairing_batch_many_dev", "bn_set_products_min", "bn_set_products_chunk",
     "bn_set_products_wide_max", "bn_get_products_routes",
     "bn_g2_prepare", "bn_g2_prepare_dev", "bn_g2_prepared_count", "bn_g2_prepared_destroy",
@@ -170,6 +172,15 @@ def load():
         "bn_g1_msm_basis": ([vp, vp, vp, sz, vp], i),
         "bn_g1_msm_basis_dev": ([vp, vp, vp, sz, vp, vp], i),
         "bn_g1_msm_basis_reserve": ([vp, vp, sz], i),
+        "bn_g2_basis_table_bytes": ([sz, i], sz),
+        "bn_g2_basis_prepare": ([vp, vp, sz, i, ctypes.POINTER(vp)], i),
+        "bn_g2_basis_prepare_dev": ([vp, vp, sz, i, ctypes.POINTER(vp), vp], i),
+        "bn_g2_basis_count": ([vp], sz),
+        "bn_g2_basis_window": ([vp], i),
+        "bn_g2_basis_destroy": ([vp, vp], i),
+        "bn_g2_msm_basis": ([vp, vp, vp, sz, vp], i),
+        "bn_g2_msm_basis_dev": ([vp, vp, vp, sz, vp, vp], i),
+        "bn_g2_msm_basis_reserve": ([vp, vp, sz], i),
         "bn_pairing_batch_many": ([vp, vp, vp, vp, sz, vp], i),
         "bn_pairing_batch_many_dev": ([vp, vp, vp, vp, sz, vp, vp], i),
         "bn_set_products_min": ([vp, sz], i),
@@ -707,6 +718,49 @@ class Context:
     def g1_msm_basis_reserve(self, handle, n):
         self._check(self._L.bn_g1_msm_basis_reserve(self._h, handle, n))
 
+    # ---- the same over G2 (bn_g2_basis)
+    def g2_basis_prepare(self, bases, c=0):
+        """bn_g2_basis_prepare: a handle (int) holding, for every row of `bases` (24 words) and
+        every window of width c (0: the default from the number of bases), the point
+        2^(c w) * base on the device; release it with g2_basis_destroy (substrate_bn.G2Basis does)."""
+        b = _arr(bases, 24)
+        h = ctypes.c_void_p()
+        self._check(self._L.bn_g2_basis_prepare(self._h, _ptr(b), b.shape[0], c, ctypes.byref(h)))
+        return h.value
+
+    def g2_basis_prepare_dev(self, d_bases, nbases, c=0, stream=None):
+        h = ctypes.c_void_p()
+        self._check(self._L.bn_g2_basis_prepare_dev(self._h, d_bases, nbases, c, ctypes.byref(h), stream))
+        return h.value
+
+    def g2_basis_count(self, handle):
+        return int(self._L.bn_g2_basis_count(handle))
+
+    def g2_basis_window(self, handle):
+        return int(self._L.bn_g2_basis_window(handle))
+
+    def g2_basis_destroy(self, handle):
+        self._check(self._L.bn_g2_basis_destroy(self._h, handle))
+
+    def g2_msm_basis(self, handle, k):
+        """bn_g2_msm_basis: the normalized image (24 words) of sum bases[i] * k[i] over the
+        first len(k) bases of the handle; G2::zero() when the sum is zero or k is empty.  More
+        scalars than the handle has bases raise ValueError before any native call."""
+        k = _arr(k, 4)
+        n = k.shape[0]
+        if n > self.g2_basis_count(handle):
+            raise ValueError("%d scalars for a basis of %d" % (n, self.g2_basis_count(handle)))
+        out = np.zeros(24, np.uint64)
+        self._check(self._L.bn_g2_msm_basis(self._h, handle, _ptr(k) if n else None, n, _ptr(out)))
+        return out
+
+    def g2_msm_basis_dev(self, handle, d_k, n, d_out, stream=None):
+        """bn_g2_msm_basis_dev: d_k and d_out are device addresses; only enqueues."""
+        self._check(self._L.bn_g2_msm_basis_dev(self._h, handle, d_k, n, d_out, stream))
+
+    def g2_msm_basis_reserve(self, handle, n):
+        self._check(self._L.bn_g2_msm_basis_reserve(self._h, handle, n))
+
     def fq12_op_many(self, op, a, b=None):
         a = _arr(a, 48)
         bb = _arr(b, 48) if b is not None else None
@@ -938,3 +992,8 @@ def g1_basis_table_bytes(nbases, c=0):
     """bn_g1_basis_table_bytes: device bytes of the fixed-basis table of nbases bases at width
     c (0: the default); 0 for arguments the prepare call refuses.  Host arithmetic, no device."""
     return load().bn_g1_basis_table_bytes(nbases, c)
+
+
+def g2_basis_table_bytes(nbases, c=0):
+    """bn_g2_basis_table_bytes: the same for a G2 basis (128 bytes per entry)."""
+    return load().bn_g2_basis_table_bytes(nbases, c)

@@ -26,7 +26,8 @@ seconds), split (the default cap) and small (the small path), after checking tha
 return the same bytes.
 
 With --basis the comparison is bn_g1_msm_dev (a context with untouched settings: its automatic
-width) against bn_g1_msm_basis_dev over a bn_g1_basis of the same n bases, by
+width) against bn_g1_msm_basis_dev over a bn_g1_basis of the same n bases, or with
+--group g2 bn_g2_msm_dev against bn_g2_msm_basis_dev over a bn_g2_basis, by
 the same protocol: HBM-resident inputs, workspace reserved, a warm-up of every form, --reps
 repetitions per form alternating in one process, torch events on the launch stream, median
 ms, and a check first that every form returns the same bytes.  The basis form runs at its
@@ -105,7 +106,7 @@ def main():
     ap.add_argument("--skew", type=int, default=1 << 18)
     ap.add_argument("--run-cap", action="store_true", help="sweep the run cap and the skew patterns instead of the window")
     ap.add_argument("--skew-reps", type=int, default=10)
-    ap.add_argument("--basis", action="store_true", help="bn_g1_msm against bn_g1_msm_basis over a fixed basis (g1)")
+    ap.add_argument("--basis", action="store_true", help="bn_g1_msm against bn_g1_msm_basis over a fixed basis (--group g2: the G2 forms)")
     ap.add_argument("--basis-windows", default="", help="widths of the basis form; empty: its default and the two on either side")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     args = ap.parse_args()
@@ -197,9 +198,7 @@ def main():
         return {"median_ms": round(statistics.median(ts), 4), "min_ms": round(min(ts), 4), "max_ms": round(max(ts), 4)}
 
     if args.basis:
-        if grp != "g1":
-            sys.exit("--basis is G1 only")
-        basis_sweep(args, sizes, dctx, P, K, k, out, stream, stats, emit, dev)
+        basis_sweep(args, grp, sizes, dctx, P, K, k, out, stream, stats, emit, dev)
         return
     if args.run_cap:
         run_cap_sweep(args, grp, sizes, run, stats, emit, k, K, dev)
@@ -311,11 +310,17 @@ def skew_patterns(k, n):
     return pats
 
 
-def basis_sweep(args, sizes, dctx, P, K, k, out, stream, stats, emit, dev):
+def basis_sweep(args, grp, sizes, dctx, P, K, k, out, stream, stats, emit, dev):
     import torch
 
     from substrate_bn import _native
     sh = stream.cuda_stream
+    # the group's calls: bn_<grp>_msm_dev, its reserve call, and the basis form's
+    msm_dev = getattr(dctx, grp + "_msm_dev")
+    msm_reserve = dctx.msm_reserve if grp == "g1" else dctx.g2_msm_reserve
+    basis_prepare_dev, basis_destroy = getattr(dctx, grp + "_basis_prepare_dev"), getattr(dctx, grp + "_basis_destroy")
+    basis_window, basis_reserve = getattr(dctx, grp + "_basis_window"), getattr(dctx, grp + "_msm_basis_reserve")
+    msm_basis_dev, table_bytes = getattr(dctx, grp + "_msm_basis_dev"), getattr(_native, grp + "_basis_table_bytes")
 
     def timed(call):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -332,26 +337,26 @@ def basis_sweep(args, sizes, dctx, P, K, k, out, stream, stats, emit, dev):
         made = []
         for _ in range(2):
             if made:
-                dctx.g1_basis_destroy(made.pop())
-            ms, _ = timed(lambda: made.append(dctx.g1_basis_prepare_dev(P.data_ptr(), n, c, sh)))
+                basis_destroy(made.pop())
+            ms, _ = timed(lambda: made.append(basis_prepare_dev(P.data_ptr(), n, c, sh)))
         return made[0], ms
 
     def compare(n, kd, handles, reps, what):
-        """-> {form: stats} of bn_g1_msm and the basis form at every width over the scalars kd,
+        """-> {form: stats} of the group's single MSM and the basis form at every width over the scalars kd,
         after a warm-up of every form that is also the agreement check"""
-        forms = {"msm": lambda: dctx.g1_msm_dev(P.data_ptr(), kd.data_ptr(), n, out.data_ptr(), sh)}
+        forms = {"msm": lambda: msm_dev(P.data_ptr(), kd.data_ptr(), n, out.data_ptr(), sh)}
         for c, h in handles.items():
-            forms["basis c=%d" % c] = lambda h=h: dctx.g1_msm_basis_dev(h, kd.data_ptr(), n, out.data_ptr(), sh)
-        dctx.msm_reserve(n)
+            forms["basis c=%d" % c] = lambda h=h: msm_basis_dev(h, kd.data_ptr(), n, out.data_ptr(), sh)
+        msm_reserve(n)
         for h in handles.values():
-            dctx.g1_msm_basis_reserve(h, n)
+            basis_reserve(h, n)
         want = None
         for f, call in forms.items():
             _, got = timed(call)
             if want is None:
                 want = got
             elif not np.array_equal(got, want):
-                print("MISMATCH at %s: %s differs from bn_g1_msm" % (what, f), file=sys.stderr)
+                print("MISMATCH at %s: %s differs from bn_%s_msm" % (what, f, grp), file=sys.stderr)
                 sys.exit(1)
         times = {f: [] for f in forms}
         for _ in range(reps):
@@ -370,7 +375,7 @@ def basis_sweep(args, sizes, dctx, P, K, k, out, stream, stats, emit, dev):
     def sized(n, body):
         """body(c0, {c: handle}, {width: prepare time and table bytes}) over handles of n bases"""
         h0, ms0 = prepared(n, 0)
-        c0 = dctx.g1_basis_window(h0)
+        c0 = basis_window(h0)
         handles, prep = {c0: h0}, {c0: ms0}
         try:
             others = [int(c) for c in args.basis_windows.split(",")] if args.basis_windows else [c0 - 1, c0 + 1]
@@ -378,15 +383,15 @@ def basis_sweep(args, sizes, dctx, P, K, k, out, stream, stats, emit, dev):
                 if 2 <= c <= 16 and c not in handles:
                     handles[c], prep[c] = prepared(n, c)
             handles = dict(sorted(handles.items()))
-            body(c0, handles, {"c=%d" % c: {"prepare_ms": round(prep[c], 3), "table_bytes": _native.g1_basis_table_bytes(n, c)}
+            body(c0, handles, {"c=%d" % c: {"prepare_ms": round(prep[c], 3), "table_bytes": table_bytes(n, c)}
                                for c in handles})
         finally:
             for h in handles.values():
-                dctx.g1_basis_destroy(h)
+                basis_destroy(h)
 
     for n in sizes:
         def body(c0, handles, prep, n=n):
-            rec = {"n": n, "reps": args.reps, "basis_default_c": c0, "msm_auto_c": auto_window("g1", n), "prepare": prep}
+            rec = {"n": n, "reps": args.reps, "basis_default_c": c0, "msm_auto_c": auto_window(grp, n), "prepare": prep}
             rec.update(compare(n, K, handles, args.reps, "n=%d" % n))
             verdict(rec, c0)
             rec["best_basis_c"] = min(handles, key=lambda c: rec["basis c=%d" % c]["median_ms"])
@@ -400,7 +405,7 @@ def basis_sweep(args, sizes, dctx, P, K, k, out, stream, stats, emit, dev):
         for name, kv in skew_patterns(k, n).items():
             kd = torch.from_numpy(np.ascontiguousarray(kv).view(np.int64)).to(dev)
             torch.cuda.synchronize(dev)
-            rec = {"skew": name, "n": n, "reps": args.skew_reps, "basis_default_c": c0, "msm_auto_c": auto_window("g1", n)}
+            rec = {"skew": name, "n": n, "reps": args.skew_reps, "basis_default_c": c0, "msm_auto_c": auto_window(grp, n)}
             rec.update(compare(n, kd, {c0: handles[c0]}, args.skew_reps, name))
             verdict(rec, c0)
             emit(rec)
