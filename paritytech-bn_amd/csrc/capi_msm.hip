@@ -6,11 +6,13 @@
 // and bn_g1_msm_prepared_many (kernels_msm_fixed.hip; §8c), bn_g1_msm_many
 // (kernels_msm_many.hip, msm_many_plan.h; §8d), and the bn_g1_basis and bn_g2_basis handles
 // with bn_g1_msm_basis and bn_g2_msm_basis (kernels_msm_basis.hip, kernels_msm_basis_g2.hip;
-// §8e, §8f), one template over the point type.
+// §8e, §8f), one template over the point type, and bn_g1_msm_basis_many
+// (kernels_msm_basis_many.hip, msm_basis_many.h; §8g).
 #include <type_traits>
 
 #include "capi_internal.h"
 #include "msm_basis.h"
+#include "msm_basis_many.h"
 #include "msm_fixed.h"
 #include "msm_many.h"
 #include "msm_many_plan.h"
@@ -379,6 +381,16 @@ struct MsmBasis<bn_g1> {
     static constexpr auto k_accumulate = k_msm_basis_accumulate;
     static constexpr auto k_chunk = k_msm_basis_chunk;
     static constexpr auto k_reduce = k_msm_basis_reduce;
+    // the batched form's kernels (bn_g1_msm_basis_many; G1 only so far)
+    static constexpr auto k_many_count = k_msm_basis_many_count;
+    static constexpr auto k_many_scan = k_msm_basis_many_scan;
+    static constexpr auto k_many_scatter = k_msm_basis_many_scatter;
+    static constexpr auto k_many_accumulate = k_msm_basis_many_accumulate;
+    static constexpr auto k_many_chunk = k_msm_basis_many_chunk;
+    static constexpr auto k_many_fold = k_msm_basis_many_fold;
+    static constexpr auto k_many_reduce = k_msm_basis_many_reduce;
+    static constexpr auto k_many_finish = k_g1_msm_fixed_finish;
+    static constexpr auto k_many_zero = k_msm_basis_many_zero;
     static HandleList<Handle>& list(bn_ctx* c) { return c->g1_basis; }
     static int auto_window(size_t nbases) { return msm_basis_auto_window(nbases); }
 };
@@ -538,6 +550,136 @@ static int msm_basis_reserve(bn_ctx* c, const typename MsmBasis<P>::Handle* h, s
     return msm_reserve<P>(c, n, msm_basis_plan<P>(c, h, n));
 }
 
+// ---------------------------------------------------------------- a batch of vectors over a fixed basis
+// The m vectors run in launch sets of S (msm_basis_many.h msm_basis_many_set; bn_set_msm_basis_many_set
+// forces S), one after another on the same stream through the shared workspace; a set costs the
+// launches of one single call.  One host sequence over the point type: MsmBasis<P> names the
+// kernels (G1 only so far).
+template <class P>
+static int msm_basis_many_args(bn_ctx* c, const typename MsmBasis<P>::Handle* h, const void* k, size_t k_stride, size_t m,
+                               size_t n, const void* out, size_t out_stride) {
+    if (!MsmBasis<P>::list(c).live(h)) return fail(c, BN_ERR_INVALID_ARGUMENT, "not a live basis handle of this context");
+    if (n > h->nbases) return fail(c, BN_ERR_INVALID_ARGUMENT, "more terms than the handle has bases");
+    if (k_stride < n) return fail(c, BN_ERR_INVALID_ARGUMENT, "k_stride is below n");
+    if (out_stride == 0) return fail(c, BN_ERR_INVALID_ARGUMENT, "out_stride is 0");
+    if (m > kMsmBasisManyMaxVectors) return fail(c, BN_ERR_INVALID_ARGUMENT, "more than 2^26 vectors");
+    if (!out || (m && n && !k)) return fail(c, BN_ERR_INVALID_ARGUMENT, "null buffer");
+    return BN_OK;
+}
+// one vector's plan and the vectors of a launch set of a call of m vectors of n terms
+struct MsmBasisManyPlan {
+    MsmPlan one;
+    size_t S;
+};
+template <class P>
+static MsmBasisManyPlan msm_basis_many_plan(bn_ctx* c, const typename MsmBasis<P>::Handle* h, size_t m, size_t n) {
+    MsmBasisManyPlan p{msm_basis_plan<P>(c, h, n), 1};
+    p.S = (size_t)msm_basis_many_set(m, n, p.one.c, 0, MsmGroup<P>::ws(c).basis_many_set);
+    return p;
+}
+template <class P>
+static int msm_basis_many_grow(bn_ctx* c, const MsmBasisManyPlan& p) {
+    MsmGroupWs<P>& g = MsmGroup<P>::ws(c);
+    const MsmPlan& m = p.one;
+    RET_IF(c->msm_keys.grow(c, p.S * (size_t)msm_basis_many_words(m.nkeys)));
+    RET_IF(c->msm_sorted.grow(c, p.S * m.nent));
+    RET_IF(g.buckets.grow(c, p.S * m.nkeys));
+    RET_IF(g.run_a.grow(c, p.S * m.slots_a));
+    RET_IF(g.run_b.grow(c, p.S * m.slots_b));
+    return g.parts.grow(c, (size_t)m.nseg * 2 * p.S);
+}
+// The device sequence on stream s; the caller holds the lock and the workspace order.  m > 0.
+template <class P>
+static int msm_basis_many_dev_impl(bn_ctx* c, const typename MsmBasis<P>::Handle* h, const bn_fr* d_k, size_t k_stride,
+                                   size_t m, size_t n, P* d_out, size_t out_stride, hipStream_t s) {
+    using G = MsmGroup<P>;
+    using B = MsmBasis<P>;
+    if (n == 0) {
+        B::k_many_zero<<<grid_for(m), kBlock, 0, s>>>(m, d_out, out_stride);
+        HIPCHK(c, hipGetLastError());
+        return BN_OK;
+    }
+    const MsmBasisManyPlan plan = msm_basis_many_plan<P>(c, h, m, n);
+    RET_IF(msm_basis_many_grow<P>(c, plan));
+    const MsmPlan& pl = plan.one;
+    MsmGroupWs<P>& g = G::ws(c);
+    const uint32_t nb = msm_buckets(pl.c), nbases = (uint32_t)h->nbases, nent = (uint32_t)pl.nent;
+    const uint32_t sa = (uint32_t)pl.slots_a, sb = (uint32_t)pl.slots_b;
+    const size_t words = (size_t)msm_basis_many_words(pl.nkeys);
+    uint32_t* keys = c->msm_keys;
+    for (size_t off = 0; off < m; off += plan.S) {
+        const size_t sc = std::min(m - off, plan.S);
+        const MsmBasisManyShape shape{(uint32_t)sc, (uint32_t)n, pl.nkeys, nent, pl.c};
+        const bn_fr* k = d_k + off * k_stride;
+        // every vector's counts (the head of its block)
+        HIPCHK(c, hipMemset2DAsync(keys, words * 4, 0, (size_t)pl.nkeys * 4, sc, s));
+        B::k_many_count<<<grid_for(sc * n), kBlock, 0, s>>>(h->zero, nbases, k, k_stride, shape, keys);
+        B::k_many_scan<<<(unsigned)sc, kMsmScanBlock, 0, s>>>(keys, pl.nkeys, (uint32_t)sc, pl.L);
+        B::k_many_scatter<<<grid_for(sc * n), kBlock, 0, s>>>(h->zero, nbases, k, k_stride, shape, keys, c->msm_sorted);
+        B::k_many_accumulate<<<grid_for(G::kLanes * sc * pl.nkeys), kBlock, 0, s>>>(h->table, nbases, shape, keys,
+                                                                                   c->msm_sorted, pl.L, g.buckets);
+        if (pl.levels) {
+            B::k_many_chunk<<<grid_for(G::kLanes * sc * sa), kBlock, 0, s>>>(h->table, nbases, shape, keys, c->msm_sorted,
+                                                                             pl.L, g.run_a, sa);
+            // even levels write run_a, odd ones run_b; the last level writes buckets only
+            for (int lv = 1; lv <= pl.levels; ++lv) {
+                const bool odd = lv & 1;
+                const uint32_t slots = msm_level_slots(nent, pl.nkeys, pl.L, lv);
+                B::k_many_fold<<<grid_for(G::kLanes * sc * slots), kBlock, 0, s>>>(
+                    shape, keys, pl.L, lv, odd ? g.run_a.get() : g.run_b.get(), odd ? sa : sb,
+                    odd ? g.run_b.get() : g.run_a.get(), lv == pl.levels ? 0u : (odd ? sb : sa), slots, g.buckets);
+            }
+        }
+        // as the single call: the rows of the windows below the top one added into window 0's
+        // (a row is every vector's slots), two windows reduced, the trees, the returned images
+        msm_tree(g.buckets.get(), pl.nwin - 1, sc * nb, s);
+        B::k_many_reduce<<<grid_for(G::kLanes * 2 * (size_t)pl.nseg * sc), kBlock, 0, s>>>(g.buckets, pl.c, pl.nkeys, pl.nseg,
+                                                                                          (uint32_t)sc, g.parts);
+        msm_tree(g.parts.get(), pl.nseg, 2 * sc, s);
+        msm_tree(g.parts.get(), 2, sc, s);
+        B::k_many_finish<<<grid_for(sc), kBlock, 0, s>>>(g.parts, sc, d_out + off * out_stride, out_stride);
+        HIPCHK(c, hipGetLastError());
+    }
+    return BN_OK;
+}
+template <class P>
+static int msm_basis_many_host(bn_ctx* c, const typename MsmBasis<P>::Handle* h, const bn_fr* k, size_t k_stride, size_t m,
+                               size_t n, P* out, size_t out_stride) {
+    CTX_GUARD_HOST(c);
+    RET_IF(msm_basis_many_args<P>(c, h, k, k_stride, m, n, out, out_stride));
+    if (m == 0) return BN_OK;
+    void* at[2];  // the sums, the rows' first n scalars (the padding of a wider row is not read)
+    RET_IF(stage_regions(c, {m * sizeof(P), m * n * sizeof(bn_fr)}, at));
+    if (n)
+        HIPCHK(c, hipMemcpy2DAsync(at[1], n * sizeof(bn_fr), k, k_stride * sizeof(bn_fr), n * sizeof(bn_fr), m,
+                                   hipMemcpyHostToDevice, c->stream));
+    RET_IF(msm_basis_many_dev_impl<P>(c, h, (const bn_fr*)at[1], n, m, n, (P*)at[0], 1, c->stream));
+    HIPCHK(c, hipMemcpy2DAsync(out, out_stride * sizeof(P), at[0], sizeof(P), sizeof(P), m, hipMemcpyDeviceToHost,
+                               c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return BN_OK;
+}
+template <class P>
+static int msm_basis_many_dev(bn_ctx* c, const typename MsmBasis<P>::Handle* h, const bn_fr* d_k, size_t k_stride, size_t m,
+                              size_t n, P* d_out, size_t out_stride, void* stream) {
+    CTX_GUARD(c);
+    RET_IF(msm_basis_many_args<P>(c, h, d_k, k_stride, m, n, d_out, out_stride));
+    if (m == 0) return BN_OK;
+    hipStream_t s = pick(c, stream);
+    RET_IF(ws_acquire(c, s));
+    WsUse use{c, s};
+    return msm_basis_many_dev_impl<P>(c, h, d_k, k_stride, m, n, d_out, out_stride, s);
+}
+template <class P>
+static int msm_basis_many_reserve(bn_ctx* c, const typename MsmBasis<P>::Handle* h, size_t m, size_t n) {
+    CTX_GUARD(c);
+    if (!MsmBasis<P>::list(c).live(h)) return fail(c, BN_ERR_INVALID_ARGUMENT, "not a live basis handle of this context");
+    if (n > h->nbases) return fail(c, BN_ERR_INVALID_ARGUMENT, "more terms than the handle has bases");
+    if (m > kMsmBasisManyMaxVectors) return fail(c, BN_ERR_INVALID_ARGUMENT, "more than 2^26 vectors");
+    if (m == 0 || n == 0) return BN_OK;
+    return msm_basis_many_grow<P>(c, msm_basis_many_plan<P>(c, h, m, n));
+}
+
 // ---------------------------------------------------------------- many MSMs over fresh bases
 // The settings a 0 stands for, read off profiles/msm_many_sweep.jsonl: width
 // 4; the automatic T of a launch set is the smallest that keeps the set at 2^16 lanes (one
@@ -687,6 +829,25 @@ int bn_g1_msm_basis_dev(bn_ctx* c, const bn_g1_basis* h, const bn_fr* d_k, size_
     return msm_basis_dev(c, h, d_k, n, d_out, stream);
 }
 int bn_g1_msm_basis_reserve(bn_ctx* c, const bn_g1_basis* h, size_t n) { return msm_basis_reserve<bn_g1>(c, h, n); }
+int bn_g1_msm_basis_many(bn_ctx* c, const bn_g1_basis* h, const bn_fr* k, size_t k_stride, size_t m, size_t n, bn_g1* out,
+                         size_t out_stride) {
+    return msm_basis_many_host(c, h, k, k_stride, m, n, out, out_stride);
+}
+int bn_g1_msm_basis_many_dev(bn_ctx* c, const bn_g1_basis* h, const bn_fr* d_k, size_t k_stride, size_t m, size_t n,
+                             bn_g1* d_out, size_t out_stride, void* stream) {
+    return msm_basis_many_dev(c, h, d_k, k_stride, m, n, d_out, out_stride, stream);
+}
+int bn_g1_msm_basis_many_reserve(bn_ctx* c, const bn_g1_basis* h, size_t m, size_t n) {
+    return msm_basis_many_reserve<bn_g1>(c, h, m, n);
+}
+int bn_set_msm_basis_many_set(bn_ctx* c, size_t vectors) {
+    if (c && vectors > kMsmBasisManyMaxVectors)
+        return fail(c, BN_ERR_INVALID_ARGUMENT, "at most 2^26 vectors per launch set (0: default)");
+    if (is_multi(c)) return for_each_sub(c, [&](bn_ctx* d) { return bn_set_msm_basis_many_set(d, vectors); });
+    CTX_GUARD(c);
+    c->msm_g1.basis_many_set = vectors;
+    return BN_OK;
+}
 size_t bn_g2_basis_table_bytes(size_t nbases, int cw) { return basis_table_bytes<bn_g2>(nbases, cw); }
 int bn_g2_basis_prepare(bn_ctx* c, const bn_g2* bases, size_t nbases, int cw, bn_g2_basis** out) {
     return basis_prepare(c, bases, false, nbases, cw, out, nullptr);

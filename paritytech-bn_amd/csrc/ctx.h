@@ -32,6 +32,9 @@ struct MsmGroupWs {
     bn::DevBuf<P> run_a, run_b;
     int fixed_lanes = 0;  // lanes per output of the lookup kernel; 0: chosen from m and k (msm_fixed.h)
     bn::DevBuf<P> fixed;
+    // vectors per launch set of the batched fixed-basis MSM (bn_g1_msm_basis_many); 0: from the
+    // bound on bucket memory (msm_basis_many.h)
+    size_t basis_many_set = 0;
 };
 
 // bn_g2_prepare's handle: the 87 line coefficients of each of nq affine G2 points

@@ -667,6 +667,22 @@ __global__ void __launch_bounds__(kBlock) k_msm_basis_chunk(const bn_fq* __restr
                                                             const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ longinfo, uint32_t nkeys, uint32_t nent, uint32_t L,
                                                             bn_g1* __restrict__ sums, uint32_t nslots);
 __global__ void __launch_bounds__(kBlock) k_msm_basis_reduce(const bn_g1* __restrict__ buckets, int c, uint32_t nkeys, uint32_t nseg, bn_g1* __restrict__ parts);
+// kernels_msm_basis_many.hip (msm_basis_many.h): a launch set of S scalar vectors over one fixed G1 basis.  keys: S blocks
+// of counts | cursors | offsets | long keys; sorted: S regions of n * W(c) entries; buckets, sums, parts: indexed by msm_basis_many.h
+struct MsmBasisManyShape;  // msm_basis_many.h: the set's S, n, nkeys, nent and c
+__global__ void __launch_bounds__(kBlock) k_msm_basis_many_count(const uint8_t* __restrict__ zero, uint32_t nbases, const bn_fr* __restrict__ k, size_t k_stride,
+                                                                 MsmBasisManyShape g, uint32_t* __restrict__ keys);
+__global__ void __launch_bounds__(kBlock) k_msm_basis_many_scatter(const uint8_t* __restrict__ zero, uint32_t nbases, const bn_fr* __restrict__ k, size_t k_stride,
+                                                                   MsmBasisManyShape g, uint32_t* __restrict__ keys, uint32_t* __restrict__ sorted);
+__global__ void __launch_bounds__(kMsmScanBlock) k_msm_basis_many_scan(uint32_t* __restrict__ keys, uint32_t nkeys, uint32_t S, uint32_t L);
+__global__ void __launch_bounds__(kBlock) k_msm_basis_many_accumulate(const bn_fq* __restrict__ table, uint32_t nbases, MsmBasisManyShape g, const uint32_t* __restrict__ keys,
+                                                                      const uint32_t* __restrict__ sorted, uint32_t L, bn_g1* __restrict__ buckets);
+__global__ void __launch_bounds__(kBlock) k_msm_basis_many_chunk(const bn_fq* __restrict__ table, uint32_t nbases, MsmBasisManyShape g, const uint32_t* __restrict__ keys,
+                                                                 const uint32_t* __restrict__ sorted, uint32_t L, bn_g1* __restrict__ sums, uint32_t slots);
+__global__ void __launch_bounds__(kBlock) k_msm_basis_many_fold(MsmBasisManyShape g, const uint32_t* __restrict__ keys, uint32_t L, int level, const bn_g1* __restrict__ src,
+                                                                uint32_t src_slots, bn_g1* __restrict__ dst, uint32_t dst_slots, uint32_t slots, bn_g1* __restrict__ buckets);
+__global__ void __launch_bounds__(kBlock) k_msm_basis_many_reduce(const bn_g1* __restrict__ buckets, int c, uint32_t nkeys, uint32_t nseg, uint32_t S, bn_g1* __restrict__ parts);
+__global__ void __launch_bounds__(kBlock) k_msm_basis_many_zero(size_t m, bn_g1* __restrict__ out, size_t stride);
 // kernels_msm_basis_g2.hip: the same over G2, kPathLanes lanes per base, key, slot or part.  table: nbases * W(c)
 // entries of two bn_fq2, window major, each entry as two lane halves [x.c0, y.c0 | x.c1, y.c1]
 __global__ void __launch_bounds__(kBlock) k_g2_basis_build(const bn_g2* __restrict__ bases, uint32_t nbases, int c, bn_fq2* __restrict__ table, uint8_t* __restrict__ zero);

@@ -26,7 +26,7 @@ pairing_prepared_many, miller_loop_prepared_many: the reference's G2Precomp held
 device; pairing_batch_prepared_many: many products whose terms mix fresh and prepared
 points), and many small MSMs over fixed G1 bases prepared once (G1Prepared,
 g1_msm_prepared_many), and one large MSM per call over a fixed basis prepared once
-(G1Basis, g1_msm_basis; G2Basis, g2_msm_basis).  Values keep the reference's memory images (canonical
+(G1Basis, g1_msm_basis, g1_msm_basis_many; G2Basis, g2_msm_basis).  Values keep the reference's memory images (canonical
 Montgomery, little-endian u64 limbs), so a Gt compares equal exactly when the
 reference's derived PartialEq would.  Every computation runs on the GPU; there
 is no CPU fallback.
@@ -770,6 +770,29 @@ def g1_msm_basis(basis, scalars):
     if k.shape[0] == 0:
         return G1.zero()
     return G1(basis._ctx.g1_msm_basis(h, k))
+
+
+def g1_msm_basis_many(basis, scalars_2d):
+    """One MSM per row of scalars_2d over the first (row length) bases of the G1Basis, in one
+    call (bn_g1_msm_basis_many): an (m, 12) array whose row j is the image g1_msm_basis returns
+    for row j.  scalars_2d: a sequence of m equally long sequences of Fr, or an (m, n, 4) image
+    array.  Rows longer than the basis, ragged rows and a closed G1Basis raise ValueError
+    before any device call; no rows give an empty (0, 12) array without one."""
+    h = basis._handle()
+    if isinstance(scalars_2d, np.ndarray):
+        k = np.ascontiguousarray(scalars_2d, dtype=np.uint64)
+    else:
+        rows = [_images(r, 4) for r in scalars_2d]
+        if len({r.shape[0] for r in rows}) > 1:
+            raise ValueError("g1_msm_basis_many: rows of different lengths")
+        k = np.stack(rows) if rows else np.zeros((0, 0, 4), np.uint64)
+    if k.ndim != 3 or k.shape[2] != 4:
+        raise ValueError("g1_msm_basis_many: scalars of shape %s are not rows of Fr images" % (k.shape,))
+    if k.shape[1] > len(basis):
+        raise ValueError("g1_msm_basis_many: %d scalars per row for a basis of %d" % (k.shape[1], len(basis)))
+    if k.shape[0] == 0:
+        return np.zeros((0, 12), np.uint64)
+    return basis._ctx.g1_msm_basis_many(h, k)
 
 
 class G2Basis(_Basis):

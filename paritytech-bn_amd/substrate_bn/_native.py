@@ -47,6 +47,7 @@ EXPORTS = [
     "bn_set_msm_many_chunk", "bn_g1_msm_many_reserve",
     "bn_g1_basis_table_bytes", "bn_g1_basis_prepare", "bn_g1_basis_prepare_dev", "bn_g1_basis_count",
     "bn_g1_basis_window", "bn_g1_basis_destroy", "bn_g1_msm_basis", "bn_g1_msm_basis_dev", "bn_g1_msm_basis_reserve",
+    "bn_g1_msm_basis_many", "bn_g1_msm_basis_many_dev", "bn_g1_msm_basis_many_reserve", "bn_set_msm_basis_many_set",
     "bn_g2_basis_table_bytes", "bn_g2_basis_prepare", "bn_g2_basis_prepare_dev", "bn_g2_basis_count",
     "bn_g2_basis_window", "bn_g2_basis_destroy", "bn_g2_msm_basis", "bn_g2_msm_basis_dev", "bn_g2_msm_basis_reserve",
     "bn_pairing_batch_many", "bn_pairing_batch_many_dev", "bn_set_products_min", "bn_set_products_chunk",
@@ -172,6 +173,10 @@ def load():
         "bn_g1_msm_basis": ([vp, vp, vp, sz, vp], i),
         "bn_g1_msm_basis_dev": ([vp, vp, vp, sz, vp, vp], i),
         "bn_g1_msm_basis_reserve": ([vp, vp, sz], i),
+        "bn_g1_msm_basis_many": ([vp, vp, vp, sz, sz, sz, vp, sz], i),
+        "bn_g1_msm_basis_many_dev": ([vp, vp, vp, sz, sz, sz, vp, sz, vp], i),
+        "bn_g1_msm_basis_many_reserve": ([vp, vp, sz, sz], i),
+        "bn_set_msm_basis_many_set": ([vp, sz], i),
         "bn_g2_basis_table_bytes": ([sz, i], sz),
         "bn_g2_basis_prepare": ([vp, vp, sz, i, ctypes.POINTER(vp)], i),
         "bn_g2_basis_prepare_dev": ([vp, vp, sz, i, ctypes.POINTER(vp), vp], i),
@@ -717,6 +722,48 @@ class Context:
 
     def g1_msm_basis_reserve(self, handle, n):
         self._check(self._L.bn_g1_msm_basis_reserve(self._h, handle, n))
+
+    # ---- a batch of scalar vectors over a fixed basis (bn_g1_msm_basis_many)
+    def g1_msm_basis_many(self, handle, scalars, n=None, out_stride=1):
+        """bn_g1_msm_basis_many: scalars is an (m, k_stride, 4) array of Fr images; row j of the
+        (m, 12) result is the normalized image of sum bases[i] * scalars[j, i] over the first n
+        (default: k_stride) bases of the handle, G1::zero() for a zero sum or n == 0.  With
+        out_stride > 1 the result is the (m * out_stride, 12) strided buffer itself: row
+        j * out_stride holds output j and the other rows stay zero.  Scalars that are not such
+        rows, an n above the row length or the handle's count and an out_stride below 1 raise
+        ValueError before any native call."""
+        s = np.ascontiguousarray(scalars, dtype=np.uint64)
+        if s.ndim != 3 or s.shape[2] != 4:
+            raise ValueError("scalars of shape %s are not rows of Fr images" % (s.shape,))
+        m, k_stride = s.shape[0], s.shape[1]
+        n = k_stride if n is None else n
+        if n < 0 or n > k_stride:
+            raise ValueError("n = %d outside rows of %d scalars" % (n, k_stride))
+        if n > self.g1_basis_count(handle):
+            raise ValueError("%d scalars for a basis of %d" % (n, self.g1_basis_count(handle)))
+        if out_stride < 1:
+            raise ValueError("out_stride must be at least 1, not %d" % out_stride)
+        out = np.zeros((m * out_stride, 12), np.uint64)
+        if m == 0:
+            return out
+        self._check(self._L.bn_g1_msm_basis_many(self._h, handle, _ptr(s) if n else None, k_stride, m, n, _ptr(out),
+                                                 out_stride))
+        return out
+
+    def g1_msm_basis_many_dev(self, handle, d_k, k_stride, m, n, d_out, out_stride=1, stream=None):
+        """bn_g1_msm_basis_many_dev: d_k and d_out are device addresses; only enqueues."""
+        if out_stride < 1:
+            raise ValueError("out_stride must be at least 1, not %d" % out_stride)
+        if k_stride < n:
+            raise ValueError("k_stride = %d below n = %d" % (k_stride, n))
+        self._check(self._L.bn_g1_msm_basis_many_dev(self._h, handle, d_k, k_stride, m, n, d_out, out_stride, stream))
+
+    def g1_msm_basis_many_reserve(self, handle, m, n):
+        self._check(self._L.bn_g1_msm_basis_many_reserve(self._h, handle, m, n))
+
+    def set_msm_basis_many_set(self, vectors):
+        """Vectors per launch set of bn_g1_msm_basis_many: at most 2^26; 0: the default."""
+        self._check(self._L.bn_set_msm_basis_many_set(self._h, vectors))
 
     # ---- the same over G2 (bn_g2_basis)
     def g2_basis_prepare(self, bases, c=0):

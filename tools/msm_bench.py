@@ -36,6 +36,20 @@ JSON line per size with the prepare time (events around the _dev prepare call, i
 allocation included) and table bytes of every width, then at --skew terms
 the four skewed patterns of --run-cap.  `gain_outside_spread`: the default-width basis form's
 median is below bn_g1_msm's by more than the wider of the two forms' own min .. max spreads.
+
+With --basis-many the comparison is bn_g1_msm_basis_many_dev against a loop of m
+bn_g1_msm_basis_dev calls on the same handle (n bases at its default width) and the same m x n
+scalars, by the same protocol: HBM-resident inputs, the workspace reserved, a warm-up of both
+forms that is also the byte-equality check of all m outputs, --reps repetitions alternating
+the two forms in one process, events on the launch stream, median ms.  One JSON line per
+(m, n) of --many-m x --sizes (default 2,8,32,128 x 2^10,2^12,2^14,2^16,2^18) and per shape of
+--many-shapes (default 9x65536, the PLONK shape); a shape whose scalars, table or workspace
+do not fit is skipped with a line that says so.  `gain_outside_spread`: the batched form's
+median is below the loop's by more than the wider of the two forms' own min .. max spreads.
+--many-set-keys lists bounds on S * nkeys (the launch set's bucket memory) to sweep at every
+shape instead, each forced through bn_set_msm_basis_many_set.  --many-loop-only times the loop
+alone (a library that predates the batched call, through BN254MI_LIB; or a profiler run of
+that form alone), --many-only the batched form alone, without the check.
 """
 import argparse
 import json
@@ -108,6 +122,12 @@ def main():
     ap.add_argument("--skew-reps", type=int, default=10)
     ap.add_argument("--basis", action="store_true", help="bn_g1_msm against bn_g1_msm_basis over a fixed basis (--group g2: the G2 forms)")
     ap.add_argument("--basis-windows", default="", help="widths of the basis form; empty: its default and the two on either side")
+    ap.add_argument("--basis-many", action="store_true", help="bn_g1_msm_basis_many against a loop of bn_g1_msm_basis calls")
+    ap.add_argument("--many-m", default="2,8,32,128")
+    ap.add_argument("--many-shapes", default="9x65536", help="further shapes m x n; empty: none")
+    ap.add_argument("--many-set-keys", default="", help="bounds on S * nkeys to sweep, e.g. 2097152,4194304,8388608")
+    ap.add_argument("--many-loop-only", action="store_true")
+    ap.add_argument("--many-only", action="store_true", help="the batched form alone, unchecked (a profiler run of its own)")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
     args = ap.parse_args()
     import torch
@@ -130,12 +150,15 @@ def main():
     ctx, dctx = Context(0), Context(0)
     if args.sizes:
         sizes = [int(s) for s in args.sizes.split(",")]
+    elif args.basis_many:
+        sizes = [1 << e for e in (10, 12, 14, 16, 18)]
     elif args.basis:
         sizes = [1, 1 << 10, 1 << 12, 1 << 14] + [1 << e for e in range(16, 21)]
     else:
         sizes = [1, 16, 128, 512] + [1 << e for e in range(10, 21)]
     cs = [int(c) for c in args.windows.split(",")]
-    nmax = max(sizes + [args.skew])
+    many_shapes = [tuple(int(v) for v in t.split("x")) for t in args.many_shapes.split(",") if t] if args.basis_many else []
+    nmax = max(sizes + [n for _, n in many_shapes]) if args.basis_many else max(sizes + [args.skew])
     s = synth.fr_images_raw(nmax, 0x6d736d31)
     k = synth.fr_images_raw(nmax, 0x6d736d32, lo=0)
     one = synth.g1_one_image() if grp == "g1" else synth.g2_one_image()
@@ -197,6 +220,10 @@ def main():
     def stats(ts):
         return {"median_ms": round(statistics.median(ts), 4), "min_ms": round(min(ts), 4), "max_ms": round(max(ts), 4)}
 
+    if args.basis_many:
+        shapes = [(m, n) for n in sizes for m in (int(v) for v in args.many_m.split(","))] + many_shapes
+        basis_many_sweep(args, shapes, dctx, P, stream, stats, emit, dev)
+        return
     if args.basis:
         basis_sweep(args, grp, sizes, dctx, P, K, k, out, stream, stats, emit, dev)
         return
@@ -410,6 +437,104 @@ def basis_sweep(args, grp, sizes, dctx, P, K, k, out, stream, stats, emit, dev):
             verdict(rec, c0)
             emit(rec)
     sized(n, body)
+
+
+def basis_many_sweep(args, shapes, ctx, P, stream, stats, emit, dev):
+    import torch
+
+    sh = stream.cuda_stream
+    set_keys = [int(v) for v in args.many_set_keys.split(",") if v]
+
+    def timed(call):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        with torch.cuda.stream(stream):
+            e0.record()
+            call()
+            e1.record()
+        torch.cuda.synchronize(dev)
+        return e0.elapsed_time(e1)
+
+    def scalars(m, n):
+        """m x n Fr images on the device: uniform 253-bit values (every value below r is an image)"""
+        g = torch.Generator(device=dev)
+        g.manual_seed(0x6d616e79 + m * 31 + n)
+        k = torch.randint(-2 ** 63, 2 ** 63 - 1, (m * n, 4), dtype=torch.int64, device=dev, generator=g)
+        k[:, 3] &= (1 << 61) - 1
+        return k
+
+    handles = {}
+    try:
+        for m, n in shapes:
+            rec = {"m": m, "n": n, "reps": args.reps}
+            try:
+                if n not in handles:
+                    for h in handles.values():
+                        ctx.g1_basis_destroy(h)
+                    handles.clear()
+                    handles[n] = ctx.g1_basis_prepare_dev(P.data_ptr(), n, 0, sh)
+                h = handles[n]
+                c = ctx.g1_basis_window(h)
+                nkeys = (254 // c + 1) << (c - 1)
+                rec["c"] = c
+                K = scalars(m, n)
+                out_many = torch.zeros((m, 12), dtype=torch.int64, device=dev)
+                out_loop = torch.zeros((m, 12), dtype=torch.int64, device=dev)
+                torch.cuda.synchronize(dev)
+                ctx.g1_msm_basis_reserve(h, n)
+                if not args.many_loop_only:
+                    ctx.set_msm_basis_many_set(max(1, max(set_keys) // nkeys) if set_keys else 0)
+                    ctx.g1_msm_basis_many_reserve(h, m, n)
+            except Exception as e:  # the scalars, the table or the workspace do not fit
+                rec["skipped"] = str(e)[:200]
+                emit(rec)
+                continue
+
+            def loop():
+                for j in range(m):
+                    ctx.g1_msm_basis_dev(h, K.data_ptr() + j * n * 32, n, out_loop.data_ptr() + j * 96, sh)
+
+            def many():
+                ctx.g1_msm_basis_many_dev(h, K.data_ptr(), n, m, n, out_many.data_ptr(), 1, sh)
+
+            forms = {} if args.many_only else {"loop": loop}
+            if args.many_loop_only:
+                pass
+            elif set_keys:
+                for b in set_keys:
+                    def f(b=b):
+                        ctx.set_msm_basis_many_set(max(1, b // nkeys))
+                        many()
+                    forms["many keys=%d" % b] = f
+                rec["S"] = {"keys=%d" % b: min(m, max(1, b // nkeys)) for b in set_keys}
+            else:
+                forms["many"] = many
+                rec["S"] = min(m, max(1, min((1 << 23) // nkeys, (2 ** 31 - 1) // (n * (254 // c + 1)))))
+            for f, call in forms.items():  # the warm-up, which is also the byte-equality check
+                out_many.zero_()
+                timed(call)
+                if f != "loop" and "loop" in forms and not torch.equal(out_many, out_loop):
+                    print("MISMATCH at m=%d n=%d: %s differs from the loop of single calls" % (m, n, f), file=sys.stderr)
+                    sys.exit(1)
+            times = {f: [] for f in forms}
+            for _ in range(args.reps):
+                for f, call in forms.items():
+                    times[f].append(timed(call))
+            for f, ts in times.items():
+                rec[f] = stats(ts)
+            a = rec.get("loop")
+            for f in forms:
+                if f == "loop" or a is None:
+                    continue
+                b = rec[f]
+                spread = max(a["max_ms"] - a["min_ms"], b["max_ms"] - b["min_ms"])
+                b["loop_over_many"] = round(a["median_ms"] / b["median_ms"], 3)
+                b["spread_ms"] = round(spread, 4)
+                b["gain_outside_spread"] = a["median_ms"] - b["median_ms"] > spread
+            emit(rec)
+            del K, out_many, out_loop
+    finally:
+        for h in handles.values():
+            ctx.g1_basis_destroy(h)
 
 
 if __name__ == "__main__":
