@@ -189,6 +189,23 @@ __device__ __forceinline__ void st_ref2(bn_fq2& a, const Fq2<B>& x) {
     st_ref(a.c1, x.c1);
 }
 #endif
+// a point's reference image (of G2 in the unit's layout: this lane's coordinates, or both)
+__device__ __forceinline__ G1J ld_g1(const bn_g1& a) {
+    return {widen<kPt>(ld_ref(a.x)), widen<kPt>(ld_ref(a.y)), widen<kPt>(ld_ref(a.z))};
+}
+__device__ __forceinline__ void st_g1(bn_g1& o, const G1J& r) {
+    st_ref(o.x, r.x);
+    st_ref(o.y, r.y);
+    st_ref(o.z, r.z);
+}
+__device__ __forceinline__ G2J ld_g2(const bn_g2& a) {
+    return {widen<kPt>(ld_ref2(a.x)), widen<kPt>(ld_ref2(a.y)), widen<kPt>(ld_ref2(a.z))};
+}
+__device__ __forceinline__ void st_g2(bn_g2& o, const G2J& r) {
+    st_ref2(o.x, r.x);
+    st_ref2(o.y, r.y);
+    st_ref2(o.z, r.z);
+}
 #if BN_SPLIT
 // Gt image: coefficient 2k + (lane parity) is the lane's coordinate of Fq2 k in
 // the order c0.c0, c0.c1, c0.c2, c1.c0, c1.c1, c1.c2 (fq12.rs:52-55)

@@ -23,11 +23,9 @@ __global__ void __launch_bounds__(kPairBlock) k_g1_mul(const bn_g1* __restrict__
     if (i >= n) return;
     uint32_t s[8];
     fr_to_canonical(k[i], s);
-    G1J a = {widen<kPt>(ld_ref(p[i].x)), widen<kPt>(ld_ref(p[i].y)), widen<kPt>(ld_ref(p[i].z))};
+    G1J a = ld_g1(p[i]);
     G1J r = jac_mul(a, s, [&](int t) { balance_step(bal, (uint32_t)t); });
-    st_ref(out[i].x, r.x);
-    st_ref(out[i].y, r.y);
-    st_ref(out[i].z, r.z);
+    st_g1(out[i], r);
 }
 // Two chains per lane (curve.h jac_mul2): lane i multiplies elements i and i + h,
 // h = ceil(n / 2); the odd tail's second chain has the zero scalar.  The two bases
@@ -58,8 +56,8 @@ __global__ void __launch_bounds__(kPairBlock) k_g1_mul2(const bn_g1* __restrict_
         for (int t = 0; t < 8; ++t) s1[t] = has1 ? s1[t] : 0u;
         top0 = scalar_top_bit(s0);
         top1 = scalar_top_bit(s1);
-        const G1J a0 = {widen<kPt>(ld_ref(p[i].x)), widen<kPt>(ld_ref(p[i].y)), widen<kPt>(ld_ref(p[i].z))};
-        const G1J a1 = {widen<kPt>(ld_ref(p[j1].x)), widen<kPt>(ld_ref(p[j1].y)), widen<kPt>(ld_ref(p[j1].z))};
+        const G1J a0 = ld_g1(p[i]);
+        const G1J a1 = ld_g1(p[j1]);
         z0 = jac_is_zero(a0);
         z1 = jac_is_zero(a1);
 #pragma unroll
@@ -92,14 +90,8 @@ __global__ void __launch_bounds__(kPairBlock) k_g1_mul2(const bn_g1* __restrict_
     auto bit = [&](int c, int pos) { return ((lds[2 * kMul2Words + 8 * c + (pos >> 5)][tid] >> (pos & 31)) & 1u) != 0; };
     G1J r0, r1;
     jac_mul2<Fq>(base, bit, z0, z1, top0, top1, r0, r1, [&](int t) { balance_step(bal, (uint32_t)t); });
-    st_ref(out[i].x, r0.x);
-    st_ref(out[i].y, r0.y);
-    st_ref(out[i].z, r0.z);
-    if (has1) {
-        st_ref(out[j].x, r1.x);
-        st_ref(out[j].y, r1.y);
-        st_ref(out[j].z, r1.z);
-    }
+    st_g1(out[i], r0);
+    if (has1) st_g1(out[j], r1);
 }
 // ---------------------------------------------------------------- group law
 // PartialEq for G<P> (mod.rs:169-195): both zero, or neither and
@@ -131,34 +123,30 @@ __global__ void __launch_bounds__(kBlock) k_g1_op(int op, const bn_g1* a, const 
     fold_table_init();
     const size_t i = lane_id();
     if (i >= n) return;
-    const G1J x = {widen<kPt>(ld_ref(a[i].x)), widen<kPt>(ld_ref(a[i].y)), widen<kPt>(ld_ref(a[i].z))};
+    const G1J x = ld_g1(a[i]);
     G1J y = x;
-    if (b) y = {widen<kPt>(ld_ref(b[i].x)), widen<kPt>(ld_ref(b[i].y)), widen<kPt>(ld_ref(b[i].z))};
+    if (b) y = ld_g1(b[i]);
     if (op == kGroupEq) {
         eq[i] = jac_eq(x, y) ? 1 : 0;
         return;
     }
     const G1J r = group_apply(op, x, y);
-    st_ref(out[i].x, r.x);
-    st_ref(out[i].y, r.y);
-    st_ref(out[i].z, r.z);
+    st_g1(out[i], r);
 }
 __global__ void __launch_bounds__(kBlock) k_g2_op(int op, const bn_g2* a, const bn_g2* b, size_t n, bn_g2* out,
                                                   uint8_t* __restrict__ eq) {
     fold_table_init();
     const size_t i = lane_id();
     if (i >= n) return;
-    const G2J x = {widen<kPt>(ld_ref2(a[i].x)), widen<kPt>(ld_ref2(a[i].y)), widen<kPt>(ld_ref2(a[i].z))};
+    const G2J x = ld_g2(a[i]);
     G2J y = x;
-    if (b) y = {widen<kPt>(ld_ref2(b[i].x)), widen<kPt>(ld_ref2(b[i].y)), widen<kPt>(ld_ref2(b[i].z))};
+    if (b) y = ld_g2(b[i]);
     if (op == kGroupEq) {
         eq[i] = jac_eq(x, y) ? 1 : 0;
         return;
     }
     const G2J r = group_apply(op, x, y);
-    st_ref2(out[i].x, r.x);
-    st_ref2(out[i].y, r.y);
-    st_ref2(out[i].z, r.z);
+    st_g2(out[i], r);
 }
 
 }  // namespace bn

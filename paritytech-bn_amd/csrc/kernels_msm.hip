@@ -1,8 +1,9 @@
 // kernels_msm.hip -- G1 multi-scalar multiplication by the bucket method:
 // S = sum_i k[i] * P[i], normalized (and the recoding, histogram and scatter of the
 // G2 one, whose group-law kernels are kernels_msm_g2.hip, and of the fixed-basis one of
-// kernels_msm_basis.hip; the group-law bodies of both are msm_group.h's).  The phases pass data only across kernel boundaries on one
-// stream (no block waits for another):
+// kernels_msm_basis.hip).  The recoding and the scan are defined here; the group-law
+// kernels instantiate msm_kernels.h's bodies over Fq, one lane per element.  The phases
+// pass data only across kernel boundaries on one stream (no block waits for another):
 //   k_msm_count       signed-digit recoding (msm.h), histogram of the (window, bucket) keys
 //   k_msm_scan        exclusive scan of the histogram -> bucket offsets and scatter cursors,
 //                     and the list of the long keys (runs above the run cap, msm.h)
@@ -20,19 +21,10 @@
 #define BN_FOLD_LDS 1
 #endif
 #include "kernels.h"
-#include "msm_group.h"
+#include "msm_kernels.h"
 #include "msm_sort.h"
 
 namespace bn {
-
-__device__ __forceinline__ G1J ld_g1(const bn_g1& a) {
-    return {widen<kPt>(ld_ref(a.x)), widen<kPt>(ld_ref(a.y)), widen<kPt>(ld_ref(a.z))};
-}
-__device__ __forceinline__ void st_g1(bn_g1& o, const G1J& r) {
-    st_ref(o.x, r.x);
-    st_ref(o.y, r.y);
-    st_ref(o.z, r.z);
-}
 
 // ---------------------------------------------------------------- recoding, histogram, scatter
 // One lane per term.  kScatter = false counts the keys; true claims a position in
@@ -113,30 +105,15 @@ __global__ void __launch_bounds__(kMsmScanBlock) k_msm_scan(const uint32_t* __re
     msm_scan_block(counts, nkeys, offsets, cursors, L, longinfo);
 }
 
-// ---------------------------------------------------------------- bucket accumulation
-// One lane per (window, bucket): the sum of its run of sorted entries
-// (msm_group.h msm_bucket_sum).  An empty bucket is zero.  A run of more than L entries is
-// left to k_msm_chunk / k_msm_fold, which write its bucket.
+// ---------------------------------------------------------------- the group-law phases
+// msm_kernels.h's bodies over Fq, one lane per element
 __global__ void __launch_bounds__(kBlock) k_msm_accumulate(const bn_g1* __restrict__ p, size_t n,
                                                            const uint32_t* __restrict__ sorted,
                                                            const uint32_t* __restrict__ offsets, uint32_t nkeys,
                                                            uint32_t nent, uint32_t L, bn_g1* __restrict__ buckets) {
     fold_table_init();
-    const size_t key = lane_id();
-    if (key >= nkeys) return;
-    uint32_t hi = offsets[key + 1];
-    hi = hi < nent ? hi : nent;
-    uint32_t lo = offsets[key];
-    lo = lo < hi ? lo : hi;
-    if (hi - lo > L) return;
-    const G1J acc = msm_bucket_sum<Fq>([&](uint32_t idx) { return ld_g1(p[idx]); }, n, sorted, lo, hi);
-    st_g1(buckets[key], acc);
+    msm_accumulate_body<Fq>(lane_id(), p, n, sorted, offsets, nkeys, nent, L, buckets);
 }
-
-// ---------------------------------------------------------------- overlong runs (msm.h)
-// One lane per level-0 slot: the sum of one chunk of at most L entries of a long key's run
-// (msm_run_task finds the key and the chunk from the slot).  A slot no key holds does
-// nothing; with no long key every lane returns after one load.
 __global__ void __launch_bounds__(kBlock) k_msm_chunk(const bn_g1* __restrict__ p, size_t n,
                                                       const uint32_t* __restrict__ sorted,
                                                       const uint32_t* __restrict__ offsets,
@@ -144,63 +121,29 @@ __global__ void __launch_bounds__(kBlock) k_msm_chunk(const bn_g1* __restrict__ 
                                                       uint32_t nent, uint32_t L, bn_g1* __restrict__ sums,
                                                       uint32_t nslots) {
     fold_table_init();
-    const size_t t = lane_id();
-    if (t >= nslots) return;
-    const MsmRunTask task = msm_run_task(longinfo + 1, offsets, longinfo[0], nkeys, nent, L, 0, (uint32_t)t);
-    if (!task.some) return;
-    const G1J acc = msm_bucket_sum<Fq>([&](uint32_t idx) { return ld_g1(p[idx]); }, n, sorted, task.lo, task.hi);
-    st_g1(sums[t], acc);
+    msm_chunk_body<Fq>(lane_id(), p, n, sorted, offsets, longinfo, nkeys, nent, L, sums, nslots);
 }
-// One lane per slot of fold level `level` >= 1: the sum of up to kMsmFoldFan consecutive
-// partial sums of one long key at the level below (src[0 .. nsrc)), into the key's bucket
-// when it is the key's only group, else into dst[slot] (dst[0 .. ndst)).
 __global__ void __launch_bounds__(kBlock) k_msm_fold(const bn_g1* __restrict__ src, uint32_t nsrc,
                                                      const uint32_t* __restrict__ offsets,
                                                      const uint32_t* __restrict__ longinfo, uint32_t nkeys,
                                                      uint32_t nent, uint32_t L, int level, bn_g1* __restrict__ dst,
                                                      uint32_t ndst, uint32_t nslots, bn_g1* __restrict__ buckets) {
     fold_table_init();
-    const size_t t = lane_id();
-    if (t >= nslots) return;
-    const MsmRunTask task = msm_run_task(longinfo + 1, offsets, longinfo[0], nkeys, nent, L, level, (uint32_t)t);
-    if (!task.some || task.hi > nsrc || (!task.last && t >= ndst)) return;
-    const G1J acc = msm_fold_sum<Fq>([&](uint32_t i) { return ld_g1(src[i]); }, task.lo, task.hi);
-    st_g1(task.last ? buckets[task.key] : dst[t], acc);
+    msm_fold_body<Fq>(lane_id(), src, nsrc, offsets, longinfo, nkeys, nent, L, level, dst, ndst, nslots, buckets);
 }
-
-// ---------------------------------------------------------------- bucket reduction
-// One lane per (segment, window): the segment's weighted sum (msm_group.h
-// msm_segment_sum).  parts[s * nwin + w], so that the addition tree over the
-// segments is k_g1_op on contiguous halves.
 __global__ void __launch_bounds__(kBlock) k_msm_reduce(const bn_g1* __restrict__ buckets, int c, uint32_t nkeys,
                                                        uint32_t nseg, bn_g1* __restrict__ parts) {
     fold_table_init();
-    const size_t t = lane_id();
-    const uint32_t nwin = (uint32_t)msm_windows(c);
-    if (t >= (size_t)nseg * nwin) return;
-    const uint32_t s = (uint32_t)(t / nwin), w = (uint32_t)(t % nwin);
-    st_g1(parts[t], msm_segment_sum<Fq>([&](uint32_t key) { return ld_g1(buckets[key]); }, c, nkeys, s, w));
+    msm_reduce_body<Fq>(lane_id(), buckets, c, nkeys, nseg, parts);
 }
-
-// ---------------------------------------------------------------- window combination
-// One lane: Horner over the window sums win[0 .. nwin) (msm_group.h msm_horner_sum).
-// finish != 0: the normalized image (msm_finish_point); 0: the Jacobian partial sum
-// as it stands (a multi-device context adds the partials first).
 __global__ void __launch_bounds__(64) k_msm_horner(const bn_g1* __restrict__ win, int c, int finish,
                                                    bn_g1* __restrict__ out) {
     fold_table_init();
-    if (lane_id() != 0) return;
-    G1J acc = msm_horner_sum<Fq>([&](int w) { return ld_g1(win[w]); }, c);
-    if (finish) acc = msm_finish_point(acc);
-    st_g1(*out, acc);
+    msm_horner_body<Fq>(lane_id(), win, c, finish, out);
 }
-// *out = the returned image of *in (msm_finish_point); in == nullptr: of zero (n == 0)
 __global__ void __launch_bounds__(64) k_msm_finish(const bn_g1* in, bn_g1* out) {
     fold_table_init();
-    if (lane_id() != 0) return;
-    G1J a = jac_zero<Fq>();
-    if (in) a = ld_g1(*in);
-    st_g1(*out, msm_finish_point(a));
+    msm_finish_body<Fq>(lane_id(), in, out);
 }
 
 }  // namespace bn

@@ -20,19 +20,12 @@
 #define BN_FOLD_LDS 1
 #endif
 #include "kernels.h"
+#include "msm_kernels.h"
 #include "msm_basis_many.h"
 #include "msm_sort.h"
 
 namespace bn {
 
-__device__ __forceinline__ G1J ld_g1(const bn_g1& a) {
-    return {widen<kPt>(ld_ref(a.x)), widen<kPt>(ld_ref(a.y)), widen<kPt>(ld_ref(a.z))};
-}
-__device__ __forceinline__ void st_g1(bn_g1& o, const G1J& r) {
-    st_ref(o.x, r.x);
-    st_ref(o.y, r.y);
-    st_ref(o.z, r.z);
-}
 // a set's lane indices are 32-bit (msm_basis_many.h); S: no such lane
 __device__ __forceinline__ MsmBasisManyLane many_lane(uint32_t per, uint32_t S) {
     const size_t t = lane_id();
@@ -95,30 +88,6 @@ __global__ void __launch_bounds__(kMsmScanBlock) k_msm_basis_many_scan(uint32_t*
 }
 
 // ---------------------------------------------------------------- bucket accumulation
-struct BasisRaw {
-    uint4 q[4];
-};
-__device__ __forceinline__ void basis_decode(const BasisRaw& e, Fq<2>& x, Fq<2>& y) {
-    const uint32_t wx[8] = {e.q[0].x, e.q[0].y, e.q[0].z, e.q[0].w, e.q[1].x, e.q[1].y, e.q[1].z, e.q[1].w};
-    const uint32_t wy[8] = {e.q[2].x, e.q[2].y, e.q[2].z, e.q[2].w, e.q[3].x, e.q[3].y, e.q[3].z, e.q[3].w};
-    x = fq_load_ref(wx);
-    y = fq_load_ref(wy);
-}
-// The sum of the entries [lo, hi) of a vector's region, which starts at word `first` of
-// sorted (a set's positions are 32-bit, so the loop keeps one index and the uniform base), of
-// a key of window w < W(c) over the first n <= nbases bases.
-__device__ __forceinline__ G1J basis_run_sum(const bn_fq* __restrict__ table, uint32_t nbases, uint32_t n, uint32_t w,
-                                             const uint32_t* __restrict__ sorted, uint32_t first, uint32_t lo,
-                                             uint32_t hi) {
-    const bn_fq* row = table + 2 * (size_t)msm_basis_index(nbases, 0, w);
-    lo += first, hi += first;
-    return msm_basis_run_sum<Fq>([&](uint32_t e) { return sorted[e]; },
-                                 [&](uint32_t idx) {
-                                     const uint4* p = reinterpret_cast<const uint4*>(row + 2 * (size_t)(idx < n ? idx : 0));
-                                     return BasisRaw{{p[0], p[1], p[2], p[3]}};
-                                 },
-                                 basis_decode, n, lo, hi);
-}
 // One lane per (vector, key): the sum of the key's run in the vector's region, into the
 // vector's bucket of that key (k_msm_basis_accumulate with the vector index around it).  A
 // run above L entries is left to the chunk and fold kernels.
@@ -132,16 +101,12 @@ __global__ void __launch_bounds__(kBlock) k_msm_basis_many_accumulate(const bn_f
     const MsmBasisManyLane at = many_lane(g.nkeys, g.S);
     if (at.v >= g.S) return;
     const uint32_t key = at.i;
-    const uint32_t* offsets = keys + msm_basis_many_offsets_at(g.nkeys, at.v);
-    uint32_t hi = offsets[key + 1];
-    hi = hi < g.nent ? hi : g.nent;
-    uint32_t lo = offsets[key];
-    lo = lo < hi ? lo : hi;
-    if (hi - lo > L) return;
+    const MsmRun run = msm_key_run(keys + msm_basis_many_offsets_at(g.nkeys, at.v), key, g.nent);
+    if (run.hi - run.lo > L) return;
     // the bucket's index is 32-bit (S * nkeys < 2^30): all the loop keeps of (vector, key)
     const uint32_t dst = (uint32_t)msm_basis_many_bucket(g.c, g.S, at.v, key);
-    st_g1(buckets[dst], basis_run_sum(table, nbases, g.n, (uint32_t)msm_key_window(g.c, key), sorted,
-                                      (uint32_t)msm_basis_many_sorted_at(g.nent, at.v), lo, hi));
+    st_g1(buckets[dst], basis_run_sum<Fq, bn_g1>(table, nbases, g.n, (uint32_t)msm_key_window(g.c, key), sorted,
+                                                 (uint32_t)msm_basis_many_sorted_at(g.nent, at.v), run.lo, run.hi));
 }
 // One lane per (vector, level-0 slot): the sum of one chunk of at most L entries of a long
 // key's run of that vector (msm.h msm_run_task on the vector's block), into slot
@@ -159,8 +124,8 @@ __global__ void __launch_bounds__(kBlock) k_msm_basis_many_chunk(const bn_fq* __
                                          g.nkeys, g.nent, L, 0, at.i);
     if (!task.some) return;
     st_g1(sums[(size_t)at.v * slots + at.i],
-          basis_run_sum(table, nbases, g.n, (uint32_t)msm_key_window(g.c, task.key),
-                        sorted, (uint32_t)msm_basis_many_sorted_at(g.nent, at.v), task.lo, task.hi));
+          basis_run_sum<Fq, bn_g1>(table, nbases, g.n, (uint32_t)msm_key_window(g.c, task.key), sorted,
+                                   (uint32_t)msm_basis_many_sorted_at(g.nent, at.v), task.lo, task.hi));
 }
 // One lane per (vector, slot of fold level `level` >= 1): k_msm_fold on the vector's slots.
 // src holds src_slots slots per vector, dst dst_slots (0 at the last level, which writes

@@ -16,15 +16,6 @@
 
 namespace bn {
 
-__device__ __forceinline__ G1J ld_g1(const bn_g1& a) {
-    return {widen<kPt>(ld_ref(a.x)), widen<kPt>(ld_ref(a.y)), widen<kPt>(ld_ref(a.z))};
-}
-__device__ __forceinline__ void st_g1(bn_g1& o, const G1J& r) {
-    st_ref(o.x, r.x);
-    st_ref(o.y, r.y);
-    st_ref(o.z, r.z);
-}
-
 // ---------------------------------------------------------------- table build
 // Lane t = b * W(c) + w builds entries (b, w, 0 .. 2^(c-1)) as reference images (x, y); the
 // lane of window 0 writes the base's zero flag.  A zero base's entries are written as

@@ -16,15 +16,6 @@
 
 namespace bn {
 
-__device__ __forceinline__ G1J ld_g1(const bn_g1& a) {
-    return {widen<kPt>(ld_ref(a.x)), widen<kPt>(ld_ref(a.y)), widen<kPt>(ld_ref(a.z))};
-}
-__device__ __forceinline__ void st_g1(bn_g1& o, const G1J& r) {
-    st_ref(o.x, r.x);
-    st_ref(o.y, r.y);
-    st_ref(o.z, r.z);
-}
-
 // ---------------------------------------------------------------- digits and multiples
 // Lane t: term t of the set's nt.  digits: W(c) * nt bytes; table: nt << (c - 1) points.
 __global__ void __launch_bounds__(kBlock) k_g1_msm_many_table(const bn_g1* __restrict__ p, const bn_fr* __restrict__ k,

@@ -509,11 +509,9 @@ __global__ void BN_PATH_ATTR __launch_bounds__(kPairBlock) k_g2_mul_split(const 
     if (i >= n) return;
     uint32_t s[8];
     fr_to_canonical(k[i], s);
-    const G2J a = {widen<kPt>(ld_ref2(p[i].x)), widen<kPt>(ld_ref2(p[i].y)), widen<kPt>(ld_ref2(p[i].z))};
+    const G2J a = ld_g2(p[i]);
     const G2J r = jac_mul(a, s, [&](int t) { balance_step(bal, (uint32_t)t); });
-    st_ref2(out[i].x, r.x);
-    st_ref2(out[i].y, r.y);
-    st_ref2(out[i].z, r.z);
+    st_g2(out[i], r);
 }
 
 }  // namespace bn

@@ -2,7 +2,7 @@
 // templates over the field F (Fq: G1, Fq2: G2) that take a functor loading a point
 // by index: the sum of one bucket's run of sorted entries, the weighted sum of one
 // segment of a window's buckets, Horner over the window sums, and the returned
-// image.  kernels_msm_g2.hip wraps them on the two-lane layout (fq2_split.h: every
+// image.  msm_kernels.h wraps them for both groups, G2 on the two-lane layout (fq2_split.h: every
 // argument must then hold the same value on both lanes of a pair, so that both
 // take every branch and leave every loop together); tests/native/msm_g2_emul.cpp
 // compiles them for the host with g++ alone.
